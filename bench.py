@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- blob_to_kzg_commitment throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (blob bytes -> 48-byte commitments: parse, fixed-base MSM, compress) over one batch
 of synthetic 4096-element blobs that is already resident in HBM. Each GPU works on its own shard (weak scaling: 1024
 blobs per GPU per step); the only collective is the one broadcast of the prepared trusted setup before the timed region.
+
+A plain run does only what the headline needs: load, build the timed region's table, W untimed steps, exactly K timed steps,
+the outputs of the last timed step if --dump-outputs is given, the result line. Every other measurement (the engine, host-ABI
+and config legs, the CPU baseline, the clock probe) runs with --full only.
 
 Rank 0 prints ONE JSON line of at most 8,000 bytes (compact_line below: the contract's fields first, numbers only, no prose --
 the driver keeps a bounded tail of stdout and round 3's 21 KB line lost its head there) and writes everything else -- every
@@ -636,6 +640,28 @@ def compact_line(res, detail_path=None):
     return text
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # all files of one --dump-outputs together
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every named output of the last timed step as out_dir/<name>.npy, float32, one row per item (a byte of a
+    compressed point, a status code or a verdict is exact in float32). An output above its share of DUMP_LIMIT_BYTES keeps a
+    fixed, seeded sample of its rows, whose indices go beside it as <name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        a = a.reshape(len(a), -1) if a.ndim else a.reshape(1, 1)
+        row_bytes = a.shape[1] * a.itemsize
+        if a.nbytes > share:
+            keep = share // (row_bytes + 8)
+            rows = np.sort(np.random.default_rng(0x4B5A47).choice(len(a), keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes through torch.distributed.run --
     BEFORE this process has touched the GPU (nothing has imported torch yet) -- relay their stdout (rank 0's one line) and exit with
@@ -661,9 +687,14 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BLOBS_PER_GPU, help="blobs per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement besides the headline: the default-engine, bucket-engine, host-ABI, API-latency and "
+                         "config legs, the CPU baseline and the clock probe (the --no-* options below leave some of them out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the short untimed-region legs of the commit bench: default engine, bucket engine, host-pointer ABI")
+                    help="--full: skip the short untimed-region legs of the commit bench: default engine, bucket engine, host-pointer ABI")
     ap.add_argument("--op", default="commit", choices=["commit", "blob_proof", "commit_prove", "verify_batch", "tiled_msm"],
                     help="commit = the headline (BASELINE configs[1]); blob_proof = configs[2]; commit_prove = commitment AND blob proof of every blob in one pass (lwkzg_commit_and_prove_batch_device); verify_batch = configs[3], host-pointer ABI; tiled_msm = configs[4], one 2^20-term MSM split over the GPUs (strong scaling)")
     ap.add_argument("--mode", default="reference", choices=["reference", "ckzg"],
@@ -686,7 +717,7 @@ def main():
                     help="initialise the process group and take every collective branch (setup broadcast, barriers, max over ranks) "
                          "at --gpus 1 too: the RCCL code path on a one-GPU box")
     ap.add_argument("--no-config-legs", action="store_true",
-                    help="skip the short legs for BASELINE configs[2]-[4] and the Fr transform (they run at --gpus 1 only)")
+                    help="--full: skip the short legs for BASELINE configs[2]-[4] and the Fr transform (they run at --gpus 1 only)")
     ap.add_argument("--hbm-headroom-gib", type=float, default=6.0,
                     help="--direct-bits auto: device memory the chosen table must leave free on this rank (workspaces of the other "
                          "legs, RCCL's buffers, the caller's own tensors)")
@@ -706,7 +737,10 @@ def main():
     # library reads its environment), so that the timed region's table is this process's first large allocation and `direct_table_build_s`
     # reports a build that does not follow the bench's own free of a 41 GB default table (r05: 6.5 s of which 5.5 were hipMalloc waiting for the
     # driver's scrub). The default engine's leg -- the table a plain load selects -- and the bucket engine's follow the headline and the config legs.
-    headline_first = (args.op == "commit" and not args.no_extra_legs and args.direct_bits == "auto" and "LWKZG_DIRECT_BITS" not in os.environ)
+    # A plain run loads the same way; only --full --no-extra-legs keeps the load's own table.
+    extra_legs = args.full and args.op == "commit" and not args.no_extra_legs
+    headline_first = (args.op == "commit" and not (args.full and args.no_extra_legs) and args.direct_bits == "auto"
+                      and "LWKZG_DIRECT_BITS" not in os.environ)
     if headline_first:
         os.environ["LWKZG_DIRECT_BITS"] = "0"
 
@@ -782,6 +816,7 @@ def main():
     couts = [torch.empty(48 * n, dtype=torch.uint8, device=dev) for _ in range(n_cs)] if n_cs > 1 else []
     cstats = [torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(n_cs)] if n_cs > 1 else []
     step_no = [0]
+    host_result = [None]                   # what tiled_msm / verify_batch hand back to the host (the last step's, for --dump-outputs)
 
     h_blobs = h_comms = h_proofs = None
     d_tiles = None
@@ -789,9 +824,10 @@ def main():
 
     def step():
         if args.op == "tiled_msm":      # each rank sums its share of the tiles, one all_gather of 48-byte partial sums
-            D.msm_tiled_sharded(d_tiles, int(d_tiles.numel()) // 32, ts, dev)
+            host_result[0] = D.msm_tiled_sharded(d_tiles, int(d_tiles.numel()) // 32, ts, dev)
         elif args.op == "verify_batch":   # ONE batch over all ranks: one transcript, one r, one pairing check (dist.py)
-            assert D.verify_blob_kzg_proof_batch_sharded(h_blobs, h_comms, h_proofs, n, ts)
+            host_result[0] = D.verify_blob_kzg_proof_batch_sharded(h_blobs, h_comms, h_proofs, n, ts)
+            assert host_result[0]
         elif n_cs > 1:                    # step k on caller stream k mod N, into that stream's own output buffer
             k = step_no[0] % n_cs
             step_no[0] += 1
@@ -869,7 +905,7 @@ def main():
     extra = {}
     DEFAULT_LABEL = ("what load_trusted_setup* selects by itself (LWKZG_DIRECT_BITS unset): the widest direct table of 13..10 bits within a quarter "
                      "of the free HBM, else buckets")
-    if args.op == "commit" and not args.no_extra_legs and not headline_first:
+    if extra_legs and not headline_first:
         # (a) what a consumer of the nine reference symbols gets: the engine the load selected, untouched
         extra["default_engine"] = engine_leg(default_bits, DEFAULT_LABEL)
         extra["default_engine"]["setup_load_s_incl_table_build"] = t_load
@@ -944,18 +980,44 @@ def main():
     elapsed, prof = timed_region(args.steps, args.warmup)
     headline_spread = step_spread[0]
 
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: per-blob results (this rank's shard; rank 0 writes all ranks'
+        # in rank order, i.e. blob order), or the one host-side result of tiled_msm / verify_batch, which every rank holds
+        def rows(t, width):
+            return t.cpu().numpy().reshape(n, width)
+        last = couts[(step_no[0] - 1) % n_cs] if cstats else d_out
+        last_status = cstats[(step_no[0] - 1) % n_cs] if cstats else d_status
+        if args.op == "tiled_msm":
+            outs = {"msm": np.frombuffer(host_result[0], dtype=np.uint8).reshape(1, 48)}
+        elif args.op == "verify_batch":
+            outs = {"verdict": np.array([[1.0 if host_result[0] else 0.0]])}
+        elif args.op == "commit":
+            outs = {"commitments": rows(last, 48), "status": rows(last_status, 1)}
+        elif args.op == "commit_prove":
+            outs = {"commitments": rows(d_comm, 48), "proofs": rows(last, 48), "status": rows(last_status, 1)}
+        else:
+            outs = {"proofs": rows(last, 48), "status": rows(last_status, 1)}
+        if distributed and args.op not in ("tiled_msm", "verify_batch"):
+            parts = [None] * world
+            dist.all_gather_object(parts, outs)
+            outs = {k: np.concatenate([p[k] for p in parts]) for k in outs}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
+
     # who ran where, and how fast each rank was by its own clock (the contract's `value` uses the slowest): rank, device ordinal, a hash
     # of the device's uuid, the shader clock it holds under a short multiply-add stream, its own ops/s -- so that a SCALE record shows
     # that N ranks on N devices took part, and a profiles/ summary can be matched to the box a line came from
     import hashlib
     props = torch.cuda.get_device_properties(dev)
     uuid = str(getattr(props, "uuid", "")) or "%s/%d" % (props.name, dev_index)
-    try:
-        clock_mhz = capi.clock_probe_mhz()
-    except Exception:       # noqa: BLE001 -- a measurement aid must not take the run down
-        clock_mhz = 0.0
+    clock_mhz = None
+    if args.full:
+        try:
+            clock_mhz = round(capi.clock_probe_mhz(), 1)
+        except Exception:       # noqa: BLE001 -- a measurement aid must not take the run down
+            clock_mhz = 0.0
     me = {"rank": rank, "device": dev_index, "gpu": props.name, "gpu_uuid_sha256_12": hashlib.sha256(uuid.encode()).hexdigest()[:12],
-          "clock_mhz_under_mad_probe": round(clock_mhz, 1), "elapsed_s": local_elapsed[0],
+          "clock_mhz_under_mad_probe": clock_mhz, "elapsed_s": local_elapsed[0],
           "value": (n * args.steps / local_elapsed[0]) if local_elapsed[0] > 0 and args.op != "tiled_msm" else None}
     per_rank = [me]
     if distributed:
@@ -963,7 +1025,7 @@ def main():
         dist.all_gather_object(gathered, me)
         per_rank = gathered
 
-    if args.op == "commit" and not args.no_extra_legs and rank == 0:
+    if extra_legs and rank == 0:
         # (c) the same batch through the host-pointer C ABI (blobs in pageable host memory: H2D of 128 KiB per blob and D2H
         # of the 48-byte results inside the clock). Never `value`.
         hb = host.tobytes()
@@ -981,11 +1043,11 @@ def main():
                              "note": "PCIe-inclusive wall clock on rank 0: pageable host blobs in, 48-byte commitments out, one GPU; "
                                      "results equal to the device-resident path's"}
 
-    if args.op == "commit" and world == 1 and not args.no_config_legs and not args.no_extra_legs and args.mode == "reference":
+    if extra_legs and world == 1 and not args.no_config_legs and args.mode == "reference":
         extra["configs"] = config_legs(K, capi, D, B, ts, dev, torch, np, direct_bits)
 
     timed_row_bytes = ts.direct_row_bytes() if direct_bits else None
-    if args.op == "commit" and not args.no_extra_legs:
+    if extra_legs:
         # the table of the timed region is not rebuilt afterwards (nothing below needs it)
         ts.enable_direct_table(0)
         ts.set_mode(-1)      # (the config legs' last ones left the settings object in c-kzg mode; no table is left to move)
@@ -1079,9 +1141,12 @@ def main():
                 direct_bits, nwin, timed_row_bytes, capi.direct_table_bytes(direct_bits, timed_row_bytes) / 1e9)) if direct_bits else "bucket (Pippenger, 13-bit signed windows, 9 MB table)",
             "engine_note": "the timed region runs on the widest direct table that fits (--direct-bits auto, an explicit lwkzg_enable_direct_table "
                            "call); `default_engine` is the same workload on the engine a plain load selects, `bucket_engine` on the low-memory fallback",
-            "leg_order": ("load (no direct table: bench.py sets LWKZG_DIRECT_BITS=0) -> the timed region's table, this process's first large allocation -> "
-                          "timed region -> host_abi -> config legs -> default engine (its table built behind the free of the headline's) + api_latency -> bucket engine"
-                          if headline_first else "load -> default engine -> the timed region's table -> timed region -> config legs -> bucket engine"),
+            "leg_order": (("load (no direct table: bench.py sets LWKZG_DIRECT_BITS=0) -> the timed region's table, this process's first large allocation -> "
+                           "timed region" + (" -> host_abi -> config legs -> default engine (its table built behind the free of the headline's) + api_latency -> "
+                                             "bucket engine" if extra_legs else ""))
+                          if headline_first else
+                          ("load -> default engine -> the timed region's table -> timed region -> config legs -> bucket engine" if extra_legs
+                           else "load -> the timed region's table -> timed region")),
             "direct_table_build_s": t_table if direct_bits else None,
             "direct_table_build_s_max_over_ranks": t_table_max if direct_bits else None,
             "direct_table_build_breakdown_ms": table_breakdown,
@@ -1101,7 +1166,7 @@ def main():
         res.update(extra)
         if world > 1:
             res["scaling_note"] = "per-GPU work is fixed (weak scaling); multi-GPU throughput is unmeasured on hardware by the builder (one-GPU boxes only)"
-        if world == 1 and not args.no_cpu_baseline and args.mode == "reference" and args.scalars == "31byte":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "reference" and args.scalars == "31byte":
             outs = bytes(d_out.cpu().numpy().tobytes()) if args.op == "commit" else b""
             res["cpu_baseline"] = cpu_baseline([outs[48 * i:48 * i + 48] for i in range(len(outs) // 48)], ts.g2_values_bytes())
         detail_path = os.environ.get("LWKZG_BENCH_DETAIL") or os.path.join(ROOT, "bench_detail.json")

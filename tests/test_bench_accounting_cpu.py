@@ -165,3 +165,27 @@ def test_launcher_free_multi_gpu_command(monkeypatch):
     assert cmd[cmd.index("--master-port") + 2].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     assert "torch" not in b.__dict__                         # bench.py imports torch inside main(), after the spawn decision
+
+
+def test_dump_outputs_writes_float32_rows_and_samples_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output, every byte exact; an output above its share of the limit keeps the same seeded
+    sample of rows in every run, with the row indices beside it"""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(1)
+    comm = rng.integers(0, 256, size=(300, 48), dtype=np.uint8)
+    status = np.zeros((300, 1), dtype=np.int32)
+    b.dump_outputs(str(tmp_path / "a"), {"commitments": comm, "status": status})
+    got = np.load(tmp_path / "a" / "commitments.npy")
+    assert got.dtype == np.float32 and got.shape == (300, 48) and np.array_equal(got.astype(np.uint8), comm)
+    assert np.load(tmp_path / "a" / "status.npy").shape == (300, 1)
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 2 * 100 * (48 * 4 + 8))        # room for 100 rows of each of two outputs
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), {"commitments": comm, "proofs": comm[::-1]})
+    total = sum(os.path.getsize(p) for p in (tmp_path / "b").iterdir())
+    assert total <= b.DUMP_LIMIT_BYTES + 4 * 128                             # (+ the .npy headers)
+    rows = np.load(tmp_path / "b" / "commitments_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "commitments.npy"), comm[rows.astype(int)].astype(np.float32))
+    for name in ("commitments.npy", "commitments_rows.npy", "proofs.npy", "proofs_rows.npy"):
+        assert np.array_equal(np.load(tmp_path / "b" / name), np.load(tmp_path / "c" / name))

@@ -211,16 +211,16 @@ def test_rccl_path_at_world_size_1(K, gpu_setup, tmp_path):
     assert bytes.fromhex(res["comms"]) == b"".join(K.blob_to_kzg_commitment_batch(vdata, gpu_setup))
 
 
-def test_bench_gpus_2_without_a_launcher(tmp_path):
+def test_bench_gpus_2_without_a_launcher(tmp_path, K, gpu_setup):
     """`python bench.py --gpus 2` with NO torch.distributed.run in front of it must start its ranks itself (fresh child
     processes, created before the parent touches the GPU) and print the one parseable line: two ranks on this one device over gloo
     (RCCL refuses two ranks on one device), small batch, the bucket-free 10-bit table. The launcher form is what the rehearsal above
-    and the driver use."""
+    and the driver use. --dump-outputs gathers both ranks' commitments of the last timed step, in blob order."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", LWKZG_BENCH_DETAIL=str(tmp_path / "detail.json"))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LWKZG_MODE"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-                        "--batch", "64", "--direct-bits", "10", "--no-extra-legs", "--no-cpu-baseline"],
+                        "--batch", "64", "--direct-bits", "10", "--no-extra-legs", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-4000:]
     lines = [l for l in p.stdout.decode().split("\n") if l.strip()]
@@ -232,6 +232,12 @@ def test_bench_gpus_2_without_a_launcher(tmp_path):
     assert line["roofline"]["kernel"].startswith("k_direct_accumulate") and line["roofline"]["avg_launch_ms"] > 0
     detail = json.load(open(env["LWKZG_BENCH_DETAIL"]))
     assert detail["value"] == pytest.approx(line["value"], rel=1e-5) and "scaling_note" in detail
+    import numpy as np
+    got = np.load(tmp_path / "out" / "commitments.npy")
+    assert got.dtype == np.float32 and got.shape == (128, 48)
+    assert got.astype(np.uint8).tobytes() == b"".join(K.blob_to_kzg_commitment_batch(B.synthetic_batch(0, 128), gpu_setup))
+    status = np.load(tmp_path / "out" / "status.npy")
+    assert status.shape == (128, 1) and not status.any()
 
 
 def test_bench_gpus_8_rehearsal_on_one_device(tmp_path):

@@ -25,7 +25,7 @@ def per_kernel(path):
 def main():
     f, w, tag = per_kernel(sys.argv[1]), per_kernel(sys.argv[2]), sys.argv[3]
     out = {"round": tag,
-           "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline (every leg)",
+           "command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline (every leg)",
            "unit": "bytes per launch: average over every launch of the kernel in the run, and the largest launch (launch sizes differ between legs)",
            "kernels": {}}
     for k in sorted(set(f) | set(w)):
