@@ -350,6 +350,27 @@ void lwkzg_verify_shard_free(LwkzgVerifyShard *shard);
 C_KZG_RET lwkzg_verify_shards_finish(bool *ok, const uint8_t *partials /* n_shards * 328 */, size_t n_shards, size_t n_total,
                                      const KZGSettings *s);
 
+/* Per-item verification: n independent verify_blob_kzg_proof calls (src/lib.rs:456-505) in one. For every i, ok_out[i] (0/1) and
+ * rc_out[i] (a C_KZG_RET) are exactly what verify_blob_kzg_proof(&ok, &blobs[i], &commitments[i], &proofs[i], s) gives, in the mode the
+ * settings answer in. A bad item is an answer, not a failure: the call returns C_KZG_OK once every item is decided, C_KZG_BADARGS for
+ * NULL pointers, C_KZG_MALLOC / C_KZG_ERROR only when the device work itself fails. n == 0: C_KZG_OK, nothing written. Synchronous, like
+ * lwkzg_verify_blob_kzg_proof_batch_device. Every step runs on the GPU, the pairing check of each item included.
+ * Verify a batch with verify_blob_kzg_proof_batch first; this call is for a batch that answered false, or where every item needs its
+ * own answer. */
+C_KZG_RET lwkzg_verify_blob_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const Blob *blobs, const Bytes48 *commitments,
+                                           const Bytes48 *proofs, size_t n, const KZGSettings *s);
+/* the same for inputs already in HBM (device pointers produced on `stream`, NULL = already complete); the verdicts come to the host */
+C_KZG_RET lwkzg_verify_blob_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_out, const void *blobs_dev,
+                                                  const void *commitments48_dev, const void *proofs48_dev, size_t n,
+                                                  const KZGSettings *s, void *stream);
+/* n independent verify_kzg_proof calls (src/lib.rs:407-453): item i is (commitments[i], zs[i], ys[i], proofs[i]); same contract */
+C_KZG_RET lwkzg_verify_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const Bytes48 *commitments, const Bytes32 *zs,
+                                      const Bytes32 *ys, const Bytes48 *proofs, size_t n, const KZGSettings *s);
+
+/* Host-only test hook for the per-item pairing: the 68 lines of the Miller loop of a ZCash-compressed G2 point (not at infinity) as the
+ * device takes them, canonical big-endian lambda.c0 | lambda.c1 | c0.c0 | c0.c1 per line (out: 68 x 192 bytes). No GPU, no settings. */
+C_KZG_RET lwkzg_pairing_line_table(uint8_t *out, const uint8_t *g2_compressed);
+
 /* Host-only test hook for the verify side: prod_i e(P_i, Q_i) == 1 for up to 4 pairs of ZCash-compressed
  * points (G1 48 bytes, G2 96 bytes; a pair with a point at infinity contributes 1). No GPU, no settings. */
 C_KZG_RET lwkzg_pairing_product_is_one(bool *ok, const uint8_t *g1_compressed, const uint8_t *g2_compressed, size_t n);

@@ -12,6 +12,7 @@ from .capi import (  # noqa: F401
     compute_kzg_proof, compute_kzg_proof_batch, get_mode, knob_report, lib, set_device, set_mode,
     VerifyShard, verify_shards_finish,
     verify_blob_kzg_proof, verify_blob_kzg_proof_batch, verify_blob_kzg_proof_batch_device, verify_kzg_proof,
+    verify_blob_kzg_proof_each, verify_blob_kzg_proof_each_device, verify_kzg_proof_each,
 )
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_verify_blob_kzg_proof_batch_device", "lwkzg_verify_shard_begin_device", "lwkzg_shard_range",
     "lwkzg_multi_blob_to_kzg_commitment_batch_device", "lwkzg_multi_compute_blob_kzg_proof_batch_device",
     "lwkzg_multi_verify_blob_kzg_proof_batch_device", "lwkzg_clock_probe_mhz",
+    "lwkzg_verify_blob_kzg_proof_each", "lwkzg_verify_blob_kzg_proof_each_device", "lwkzg_verify_kzg_proof_each",
+    "lwkzg_pairing_line_table",
 ]
 
 _lib = None
@@ -99,6 +101,11 @@ def lib():
     l.lwkzg_compute_blob_kzg_proof_batch_device.argtypes = [vp, vp, vp, sz, ps, vp, vp]
     l.lwkzg_compute_challenges_device.argtypes = [vp, vp, vp, sz, ps, vp]
     l.lwkzg_verify_blob_kzg_proof_batch_device.argtypes = [C.POINTER(C.c_bool), vp, vp, vp, sz, ps, vp]
+    pu8, pi32 = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+    l.lwkzg_verify_blob_kzg_proof_each.argtypes = [pu8, pi32, C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_verify_blob_kzg_proof_each_device.argtypes = [pu8, pi32, vp, vp, vp, sz, ps, vp]
+    l.lwkzg_verify_kzg_proof_each.argtypes = [pu8, pi32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_pairing_line_table.argtypes = [C.c_char_p, C.c_char_p]
     l.lwkzg_shard_range.argtypes = [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]
     pvp, psz = C.POINTER(vp), C.POINTER(sz)
     l.lwkzg_multi_blob_to_kzg_commitment_batch_device.argtypes = [pvp, pvp, psz, vp, psz]
@@ -519,6 +526,43 @@ def verify_blob_kzg_proof_batch_device(blobs_ptr, comm_ptr, proofs_ptr, n, ts, s
     _check("lwkzg_verify_blob_kzg_proof_batch_device",
            lib().lwkzg_verify_blob_kzg_proof_batch_device(C.byref(ok), blobs_ptr, comm_ptr, proofs_ptr, n, ts.ref(), stream))
     return bool(ok.value)
+
+
+def _each(fn, n, call):
+    ok = (C.c_uint8 * max(n, 1))()
+    rc = (C.c_int32 * max(n, 1))()
+    _check(fn, call(ok, rc))
+    return [(rc[i], bool(ok[i])) for i in range(n)]
+
+
+def verify_blob_kzg_proof_each(blobs, commitments, proofs, ts):
+    """n independent verify_blob_kzg_proof calls in one (lwkzg_verify_blob_kzg_proof_each): a list of (rc, ok), item i exactly what
+    the single call on item i answers. Inputs: the concatenated blobs, commitments and proofs (bytes)."""
+    n = len(commitments) // 48
+    assert len(commitments) == 48 * n and len(proofs) == 48 * n and len(blobs) == BYTES_PER_BLOB * n
+    return _each("lwkzg_verify_blob_kzg_proof_each", n,
+                 lambda ok, rc: lib().lwkzg_verify_blob_kzg_proof_each(ok, rc, blobs, commitments, proofs, n, ts.ref()))
+
+
+def verify_blob_kzg_proof_each_device(blobs_ptr, comm_ptr, proofs_ptr, n, ts, stream=None):
+    """the same on DEVICE pointers (produced on `stream`); the verdicts come to the host, the call is synchronous"""
+    return _each("lwkzg_verify_blob_kzg_proof_each_device", n,
+                 lambda ok, rc: lib().lwkzg_verify_blob_kzg_proof_each_device(ok, rc, blobs_ptr, comm_ptr, proofs_ptr, n, ts.ref(), stream))
+
+
+def verify_kzg_proof_each(commitments, zs, ys, proofs, ts):
+    """n independent verify_kzg_proof calls in one (lwkzg_verify_kzg_proof_each): a list of (rc, ok)"""
+    n = len(commitments) // 48
+    assert len(commitments) == 48 * n and len(proofs) == 48 * n and len(zs) == 32 * n and len(ys) == 32 * n
+    return _each("lwkzg_verify_kzg_proof_each", n,
+                 lambda ok, rc: lib().lwkzg_verify_kzg_proof_each(ok, rc, commitments, zs, ys, proofs, n, ts.ref()))
+
+
+def pairing_line_table(g2_compressed):
+    """the 68 Miller-loop lines of a compressed G2 point as the device takes them (host-only test hook): 68 x 192 bytes"""
+    out = C.create_string_buffer(68 * 192)
+    _check("lwkzg_pairing_line_table", lib().lwkzg_pairing_line_table(out, g2_compressed))
+    return out.raw
 
 
 # ---- sharded batch verification (one batch, one r, one pairing check; include/lambdaworks_kzg_amd.h) ---------

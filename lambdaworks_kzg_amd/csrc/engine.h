@@ -301,6 +301,9 @@ struct Ctx {
     size_t vblobs_cap = 0;         // blobs
     uint8_t *host_res = nullptr;   // results / verdicts / digests of a long host-pointer batch on the device (grow-only, under mu):
     size_t host_res_cap = 0;       // r05 allocated and freed them per call, 6 ms of a 52 ms call of 4096 blobs (profiles/r06_experiments.md section 6)
+    void *each_lines = nullptr;    // verify_each.hip: the line tables of g2_values[0] and [1] on the device (2 x 68 PairingLine), made on first use; under mu
+    uint8_t *each_buf = nullptr;   // verify_each.hip: per-item points and verdicts (grow-only, under mu)
+    size_t each_cap = 0;           // items each_buf holds
     VerifyBuffers vs;   // verify-side scratch, sized for vs_cap blobs
     size_t vs_cap;
     std::mutex verify_mu;
@@ -335,9 +338,15 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
 // the same for device-resident inputs (d_ pointers; z32 .. canon_p are host memory)
 // records_out (r06; 160 n host bytes, C | z | y | pi per blob): when given, the transcript is assembled on the device and comes back in ONE
 // copy through pinned memory; z32 .. canon_p are then not written
+// keep (verify_each.hip): every item's status, z and y bytes stay on the device (vb.status_all, vb.d_rz, vb.d_r) with the decompressed
+// points, enqueued on c->stream; nothing is copied back and no status stops the call
 C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_comm, const uint8_t *d_proofs, size_t n, int mode,
                                 uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p, VerifyBuffers &vb, hipStream_t caller,
-                                uint8_t *records_out = nullptr);
+                                uint8_t *records_out = nullptr, bool keep = false);
+// the same front for n openings (C, z, y, pi) already on the device (verify_each.hip): both point sets validated, z / y checked and
+// written canonical in the mode's byte order to vb.d_rz / vb.d_r, the status words in vb.status_all; enqueued on c->stream
+C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const uint8_t *d_proofs, const uint8_t *d_z, const uint8_t *d_y,
+                                         size_t n, int mode, VerifyBuffers &vb);
 C_KZG_RET lincomb3_device_host(Ctx *c, VerifyBuffers &vb, const uint8_t *sc_r, const uint8_t *sc_rz, size_t n,
                                uint8_t sums[3][96], int infs[3]);
 // r06: the same three sums from r alone (vmsm.hip). pw33: r^(2^k), k = 0..31, then r^first, Montgomery form. vmsm_begin only

@@ -474,6 +474,8 @@ static void ctx_destroy(Ctx *c) {
     if (c->comb.pinned_blobs) hipHostFree(c->comb.pinned_blobs);
     dev_free(c->host_res);
     dev_free(c->vblobs);
+    dev_free(c->each_lines);
+    dev_free(c->each_buf);
     if (c->prio_copy) hipStreamDestroy(c->prio_copy);
     if (c->one_pin) hipHostFree(c->one_pin);
     for (int k = 0; k < 2; k++) {
@@ -1858,7 +1860,7 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
 // exits at once otherwise. Then chunk by chunk: parse, y = p(z). `caller`: the stream the inputs were produced on (may be null).
 C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_comm, const uint8_t *d_proofs, size_t n, int mode,
                                 uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p, VerifyBuffers &vb, hipStream_t caller,
-                                uint8_t *records_out) {
+                                uint8_t *records_out, bool keep) {
     if (!vb.owned) vb.hold = std::unique_lock<std::mutex>(c->verify_mu);
     std::lock_guard<std::mutex> lk(c->mu);
     LWK_HIP(hipSetDevice(c->device));
@@ -1957,6 +1959,7 @@ C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d
             launch_fr_mont_to_bytes(z + off, vb.d_rz + 32 * off, le, m, st);
         }
     }
+    if (keep) return C_KZG_OK;   // per-item verification (verify_each.hip) reads the statuses, z and y where they are
     if (records_out && vb.d_rec && vb.h_rec && vb.rec_cap >= n) {
         // r06: the transcript C | z | y | pi per blob assembled by a kernel and ONE copy into pinned memory, the lowest rejected index in its
         // last word -- where r05 made four copies into pageable vectors, a fifth for the status words, and the host interleaved
@@ -1981,6 +1984,27 @@ C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d
     LWK_HIP(hipMemcpyAsync(z32, vb.d_rz, n * 32, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(y32, vb.d_r, n * 32, hipMemcpyDeviceToHost, st));
     return first_status(c, vb.status_all, n, st);  // the validation's verdicts and the parser's
+}
+
+C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const uint8_t *d_proofs, const uint8_t *d_z, const uint8_t *d_y,
+                                         size_t n, int mode, VerifyBuffers &vb) {
+    vb.hold = std::unique_lock<std::mutex>(c->verify_mu);
+    std::lock_guard<std::mutex> lk(c->mu);
+    LWK_HIP(hipSetDevice(c->device));
+    const int le = mode == LWKZG_MODE_CKZG;
+    const int bad = le ? kStatusBadArgs : kStatusError;
+    hipStream_t st = c->stream;
+    WsUse wsu(c, st);
+    C_KZG_RET rc = vs_reserve(c, n);
+    if (rc != C_KZG_OK) return rc;
+    verify_buffers_lend(vb, c->vs);
+    LWK_HIP(hipMemsetAsync(vb.status_all, 0, n * 4, st));
+    launch_decompress_points2(d_proofs, vb.pts_p, vb.kind_p, d_comm, vb.pts_c, vb.kind_c, n, st);
+    launch_subgroup_canon2(vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c,
+                           vb.status_all, bad, n, st);
+    launch_each_openings(d_z, d_y, vb.d_rz, vb.d_r, vb.status_all, bad, le, n, st);
+    LWK_HIP(hipGetLastError());
+    return C_KZG_OK;
 }
 
 // sums[0] = sum r_i pi_i, sums[1] = sum r_i z_i pi_i, sums[2] = sum r_i C_i on the points verify_prepare_host kept

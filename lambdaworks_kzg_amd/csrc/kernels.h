@@ -183,6 +183,10 @@ void launch_vmsm_reduce(const G1Xyzz29 *partial, G1Xyzz29 *bsum, uint8_t *out96,
 // records[160 i] = C_i | z_i | y_i | pi_i from the device-resident pieces; *first_bad = lowest index with a status word set (pre-set to 0xffffffff)
 void launch_verify_records(const uint8_t *canon_c, const uint8_t *z32, const uint8_t *y32, const uint8_t *canon_p, const int32_t *status,
                            uint8_t *records, uint32_t *first_bad, size_t n, hipStream_t st);
+// verify_each.hip: z / y of n openings checked (c-kzg: little-endian, < r; reference: big-endian, reduced) and written canonical in the
+// mode's byte order; a rejected item gets bad_code in status
+void launch_each_openings(const uint8_t *z_in, const uint8_t *y_in, uint8_t *z_out, uint8_t *y_out, int32_t *status, int bad_code, int le,
+                          size_t n, hipStream_t st);
 void launch_xyzz29_to_affine_be(const G1Xyzz29 *in, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st);
 void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, int le, size_t n, hipStream_t st,
                       const uint8_t *only_if_differs_from = nullptr);

@@ -398,6 +398,18 @@ std::shared_ptr<const FixedQ> fixed_q_lines(const G2A &q) {
 
 }  // namespace
 
+// the 68 lines of Q's Miller loop (in the order the loop consumes them) as the device tower takes them: out[2 k] = lambda,
+// out[2 k + 1] = c0 (fp12.cuh: PairingLine; verify_each.hip uploads them once per context). Q: affine, of order r.
+void pairing_line_table_host(const Fp2 &qx, const Fp2 &qy, Fp2 *out) {
+    const G2A q = {{HFp::from_fe(qx.c0), HFp::from_fe(qx.c1)}, {HFp::from_fe(qy.c0), HFp::from_fe(qy.c1)}};
+    std::shared_ptr<const FixedQ> fq = fixed_q_lines(q);
+    for (size_t k = 0; k < fq->lines.size(); k++) {
+        const LineCoeff &lc = fq->lines[k];
+        out[2 * k] = {lc.lambda.c0.to_fe(), lc.lambda.c1.to_fe()};
+        out[2 * k + 1] = {lc.c0.c0.to_fe(), lc.c0.c1.to_fe()};
+    }
+}
+
 // prod_i e(P_i, Q_i) == 1 for affine, non-infinity inputs (callers drop pairs with an infinity: e = 1)
 bool pairing_product_is_one(const G1Affine *ps, const Fp2 *qx, const Fp2 *qy, int n) {
     init_consts();
