@@ -367,6 +367,38 @@ C_KZG_RET lwkzg_verify_blob_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_o
 C_KZG_RET lwkzg_verify_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const Bytes48 *commitments, const Bytes32 *zs,
                                       const Bytes32 *ys, const Bytes48 *proofs, size_t n, const KZGSettings *s);
 
+/* EIP-7594 (PeerDAS) cells and cell proofs. The blob stands for the polynomial p the settings' mode reads (reference mode: big-endian
+ * coefficients reduced mod r; c-kzg mode: little-endian evaluations on the bit-reversed 4096 domain, each < r). With w = 7^((r-1)/8192)
+ * and the extended domain D[j] = w^bitrev13(j), cell k (k < 128) holds p(D[64 k + t]) for t < 64, 32 bytes each in the mode's byte
+ * order: cells 0 .. 63 are the evaluations on the 4096 domain (in c-kzg mode, the blob's own bytes), cells 64 .. 127 those of
+ * p(w X). Proof k is [q_k(tau)]G1 compressed, q_k = p div (X^64 - c_k) with c_k = D[64 k]^64: the quotient by the vanishing
+ * polynomial of cell k's coset. DESIGN.md section 4h. */
+#ifndef FIELD_ELEMENTS_PER_EXT_BLOB
+#define FIELD_ELEMENTS_PER_EXT_BLOB (2 * FIELD_ELEMENTS_PER_BLOB)
+#endif
+#ifndef FIELD_ELEMENTS_PER_CELL
+#define FIELD_ELEMENTS_PER_CELL 64
+#endif
+#ifndef CELLS_PER_EXT_BLOB
+#define CELLS_PER_EXT_BLOB (FIELD_ELEMENTS_PER_EXT_BLOB / FIELD_ELEMENTS_PER_CELL)
+#endif
+#ifndef BYTES_PER_CELL
+#define BYTES_PER_CELL (FIELD_ELEMENTS_PER_CELL * BYTES_PER_FIELD_ELEMENT)
+#endif
+typedef struct { uint8_t bytes[BYTES_PER_CELL]; } Cell;
+/* The 128 cells and 128 proofs of one blob (c-kzg-4844 2.x's argument order). Either output may be NULL: with proofs == NULL only the
+ * cells are computed and no MSM runs; both NULL is an argument error. Synchronous. */
+C_KZG_RET lwkzg_compute_cells_and_kzg_proofs(Cell *cells, KZGProof *proofs, const Blob *blob, const KZGSettings *s);
+/* n blobs: cells and proofs are n x 128 each. The return code as the other host batches: a c-kzg-mode blob with an element >= r fails
+ * the call (C_KZG_BADARGS; first_bad, if given, gets its index) and nothing is written. n == 0: C_KZG_OK, nothing written. */
+C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch(Cell *cells, KZGProof *proofs, const Blob *blobs, size_t n, const KZGSettings *s,
+                                                   size_t *first_bad);
+/* the same on device pointers (cells_dev: n x 128 x 2048 bytes, proofs48_dev: n x 128 x 48 bytes, either NULL), asynchronous on `stream`
+ * (NULL = the context's own). status_dev (optional): one word per blob, 0 or the mode's rejection code; a good blob's outputs are correct
+ * whatever its neighbours' status. A call of 8 blobs or more fills whole MSM launch sets. */
+C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch_device(void *cells_dev, void *proofs48_dev, const void *blobs_dev, size_t n,
+                                                          const KZGSettings *s, void *stream, int32_t *status_dev);
+
 /* Host-only test hook for the per-item pairing: the 68 lines of the Miller loop of a ZCash-compressed G2 point (not at infinity) as the
  * device takes them, canonical big-endian lambda.c0 | lambda.c1 | c0.c0 | c0.c1 per line (out: 68 x 192 bytes). No GPU, no settings. */
 C_KZG_RET lwkzg_pairing_line_table(uint8_t *out, const uint8_t *g2_compressed);

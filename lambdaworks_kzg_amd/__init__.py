@@ -13,6 +13,8 @@ from .capi import (  # noqa: F401
     VerifyShard, verify_shards_finish,
     verify_blob_kzg_proof, verify_blob_kzg_proof_batch, verify_blob_kzg_proof_batch_device, verify_kzg_proof,
     verify_blob_kzg_proof_each, verify_blob_kzg_proof_each_device, verify_kzg_proof_each,
+    BYTES_PER_CELL, CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_CELL, FIELD_ELEMENTS_PER_EXT_BLOB,
+    compute_cells_and_kzg_proofs, compute_cells_and_kzg_proofs_batch, compute_cells_and_kzg_proofs_batch_device,
 )
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -20,6 +20,11 @@ FIELD_ELEMENTS_PER_BLOB = 4096
 BYTES_PER_BLOB = 4096 * 32
 BYTES_PER_COMMITMENT = 48
 BYTES_PER_PROOF = 48
+# EIP-7594
+FIELD_ELEMENTS_PER_EXT_BLOB = 8192
+FIELD_ELEMENTS_PER_CELL = 64
+CELLS_PER_EXT_BLOB = 128
+BYTES_PER_CELL = 2048
 
 
 class KZGSettings(C.Structure):
@@ -61,6 +66,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_multi_verify_blob_kzg_proof_batch_device", "lwkzg_clock_probe_mhz",
     "lwkzg_verify_blob_kzg_proof_each", "lwkzg_verify_blob_kzg_proof_each_device", "lwkzg_verify_kzg_proof_each",
     "lwkzg_pairing_line_table",
+    "lwkzg_compute_cells_and_kzg_proofs", "lwkzg_compute_cells_and_kzg_proofs_batch", "lwkzg_compute_cells_and_kzg_proofs_batch_device",
 ]
 
 _lib = None
@@ -106,6 +112,9 @@ def lib():
     l.lwkzg_verify_blob_kzg_proof_each_device.argtypes = [pu8, pi32, vp, vp, vp, sz, ps, vp]
     l.lwkzg_verify_kzg_proof_each.argtypes = [pu8, pi32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
     l.lwkzg_pairing_line_table.argtypes = [C.c_char_p, C.c_char_p]
+    l.lwkzg_compute_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, ps]
+    l.lwkzg_compute_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, sz, ps, C.POINTER(sz)]
+    l.lwkzg_compute_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, vp, sz, ps, vp, vp]
     l.lwkzg_shard_range.argtypes = [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]
     pvp, psz = C.POINTER(vp), C.POINTER(sz)
     l.lwkzg_multi_blob_to_kzg_commitment_batch_device.argtypes = [pvp, pvp, psz, vp, psz]
@@ -556,6 +565,45 @@ def verify_kzg_proof_each(commitments, zs, ys, proofs, ts):
     assert len(commitments) == 48 * n and len(proofs) == 48 * n and len(zs) == 32 * n and len(ys) == 32 * n
     return _each("lwkzg_verify_kzg_proof_each", n,
                  lambda ok, rc: lib().lwkzg_verify_kzg_proof_each(ok, rc, commitments, zs, ys, proofs, n, ts.ref()))
+
+
+def _cells_split(cells_raw, proofs_raw, n):
+    """n x 128 cells / proofs as returned by the library -> [(cells, proofs)] per blob, each a list of 128 bytes objects (or None)"""
+    out = []
+    for b in range(n):
+        cs = None if cells_raw is None else [cells_raw[(128 * b + k) * BYTES_PER_CELL:(128 * b + k + 1) * BYTES_PER_CELL] for k in range(128)]
+        ps = None if proofs_raw is None else [proofs_raw[(128 * b + k) * 48:(128 * b + k + 1) * 48] for k in range(128)]
+        out.append((cs, ps))
+    return out
+
+
+def compute_cells_and_kzg_proofs(blob, ts, cells=True, proofs=True):
+    """EIP-7594 compute_cells_and_kzg_proofs (lwkzg_compute_cells_and_kzg_proofs): (cells, proofs), 128 cells of 2048 bytes and
+    128 compressed proofs, in the settings' mode; cells=False / proofs=False leave that output out (None)."""
+    assert len(blob) == BYTES_PER_BLOB
+    cb = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL) if cells else None
+    pb = C.create_string_buffer(CELLS_PER_EXT_BLOB * 48) if proofs else None
+    _check("lwkzg_compute_cells_and_kzg_proofs", lib().lwkzg_compute_cells_and_kzg_proofs(cb, pb, blob, ts.ref()))
+    return _cells_split(cb.raw if cells else None, pb.raw if proofs else None, 1)[0]
+
+
+def compute_cells_and_kzg_proofs_batch(blobs, ts, cells=True, proofs=True):
+    """the same for n concatenated blobs in one call: a list of (cells, proofs) per blob"""
+    n = len(blobs) // BYTES_PER_BLOB
+    assert len(blobs) == n * BYTES_PER_BLOB
+    cb = C.create_string_buffer(max(n, 1) * CELLS_PER_EXT_BLOB * BYTES_PER_CELL) if cells else None
+    pb = C.create_string_buffer(max(n, 1) * CELLS_PER_EXT_BLOB * 48) if proofs else None
+    bad = C.c_size_t(0)
+    _check("lwkzg_compute_cells_and_kzg_proofs_batch",
+           lib().lwkzg_compute_cells_and_kzg_proofs_batch(cb, pb, blobs, n, ts.ref(), C.byref(bad)))
+    return _cells_split(cb.raw if cells else None, pb.raw if proofs else None, n)
+
+
+def compute_cells_and_kzg_proofs_batch_device(cells_ptr, proofs_ptr, blobs_ptr, n, ts, stream=None, status_ptr=None):
+    """cells (n x 128 x 2048 bytes) and proofs (n x 128 x 48 bytes) of n device-resident blobs, asynchronous on `stream`; either output
+    pointer may be None"""
+    _check("lwkzg_compute_cells_and_kzg_proofs_batch_device",
+           lib().lwkzg_compute_cells_and_kzg_proofs_batch_device(cells_ptr, proofs_ptr, blobs_ptr, n, ts.ref(), stream, status_ptr))
 
 
 def pairing_line_table(g2_compressed):

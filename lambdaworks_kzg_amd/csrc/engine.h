@@ -313,6 +313,22 @@ struct Ctx {
     LoadTiming load_timing;
 };
 
+// Every call that touches the shared workspace on stream `st` brackets its enqueues with this: the stream first waits
+// for whatever used the workspace last (a no-op on the same stream), and leaves the event for the next user.
+struct WsUse {
+    Ctx *c;
+    hipStream_t st;
+    WsUse(Ctx *c_, hipStream_t st_) : c(c_), st(st_) {
+        if (c->ws_last != st) hipStreamWaitEvent(st, c->ws_done, 0);
+        for (int k = 0; k < kCombineLanes; k++) hipStreamWaitEvent(st, c->lane_done[k], 0);  // (never recorded: no-op)
+    }
+    ~WsUse() {
+        hipEventRecord(c->ws_done, st);
+        c->ws_last = st;
+        c->ws_recorded.store(true, std::memory_order_release);
+    }
+};
+
 Ctx *ctx_of(const KZGSettings *s);  // resolves fs, or the registry for hand-built settings; nullptr + error otherwise
 // is `c` still the live context that was given generation `gen`? Looks only at the registry, never at a caller's KZGSettings
 bool ctx_is_live(const Ctx *c, uint64_t gen);
@@ -320,6 +336,18 @@ bool ctx_is_live(const Ctx *c, uint64_t gen);
 int mode_of(const KZGSettings *s);    // the semantics a call on `s` answers in: its own mode if it has one, else the default
 
 C_KZG_RET ctx_reserve(Ctx *c, size_t n);
+// In reference mode every failure is C_KZG_ERROR; c-kzg mode keeps the code
+C_KZG_RET map_rc(C_KZG_RET rc, int mode);
+// c-kzg mode: the Lagrange form of the setup exists (built on first use, once per settings object)
+void ensure_lagrange(Ctx *c, int mode);
+
+// MSM stages of one launch set (n <= kMaxChunk scalar sets at scalars_raw, workspace slots base ..): the compressed results at out48.
+// lagrange: the scalars are evaluations on the bit-reversed domain and the MSM runs over the Lagrange form of the setup
+void msm_stages(Ctx *c, const uint32_t *scalars_raw, uint8_t *out48, size_t n, hipStream_t st, size_t base = 0, bool shared_chip = false,
+                bool lagrange = false);
+// n monomial-form scalar sets in ws.scalars2 (slots base ..) -> the form their MSM runs on (evaluations when the settings' only
+// direct table is over the Lagrange form; ws.scalars and ws.fr of the same slots serve as scratch); returns true for that form
+bool coefficients_to_msm_form(Ctx *c, int mode, size_t n, hipStream_t st, size_t base = 0);
 
 // device-resident pipelines; all pointers device, async on st
 C_KZG_RET commit_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, size_t n, int mode, hipStream_t st,

@@ -200,4 +200,15 @@ double host_hash_rate();   // bytes per second the host threads hashed in their 
 void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n);   // 8 words per blob: the hash state k_challenge_finish continues from
 void sha256_blocks_portable(uint32_t h[8], const uint8_t *blocks, size_t n_blocks);
 
+// ---- EIP-7594 cells (cells.hip)
+constexpr int kCellElems = 64;        // field elements per cell
+constexpr int kCellsPerBlob = 128;    // cells (and cell proofs) per blob: 8192 extended evaluations
+// canonical coefficients of n_blobs blobs -> their 128 cells each (n_blobs x 256 KiB), 32-byte elements little-endian (le) or
+// big-endian; scratch, scratch2: 2 n_blobs x 4096 Fr each
+void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr28 *tw28_fwd, Fr *scratch, Fr *scratch2, uint8_t *cells,
+                         int le, size_t n_blobs, hipStream_t st);
+// canonical coefficients of n_cells / 128 blobs -> the monomial quotient q_k = p div (X^64 - c_k) of every cell, canonical limbs in
+// scalar set (blob * 128 + k), zero-padded to 4096
+void launch_cells_quotients(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, size_t n_cells, hipStream_t st);
+
 }  // namespace lwk
