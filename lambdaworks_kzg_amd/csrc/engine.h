@@ -344,7 +344,7 @@ void ensure_lagrange(Ctx *c, int mode);
 // MSM stages of one launch set (n <= kMaxChunk scalar sets at scalars_raw, workspace slots base ..): the compressed results at out48.
 // lagrange: the scalars are evaluations on the bit-reversed domain and the MSM runs over the Lagrange form of the setup
 void msm_stages(Ctx *c, const uint32_t *scalars_raw, uint8_t *out48, size_t n, hipStream_t st, size_t base = 0, bool shared_chip = false,
-                bool lagrange = false);
+                bool lagrange = false, bool redo_cleared = false);
 // n monomial-form scalar sets in ws.scalars2 (slots base ..) -> the form their MSM runs on (evaluations when the settings' only
 // direct table is over the Lagrange form; ws.scalars and ws.fr of the same slots serve as scratch); returns true for that form
 bool coefficients_to_msm_form(Ctx *c, int mode, size_t n, hipStream_t st, size_t base = 0);

@@ -41,6 +41,7 @@ const char *get_error() { return g_err; }
 struct ProfRec {
     const char *name;
     hipEvent_t e0, e1;
+    int dev;
 };
 static std::atomic<bool> g_prof_on{false};
 static std::mutex g_prof_mu;
@@ -51,9 +52,38 @@ struct ProfAgg {
 };
 static std::map<std::string, ProfAgg> g_prof_agg;
 
-ProfScope::ProfScope(const char *n, hipStream_t s) : name(n), st(s), e0(nullptr), e1(nullptr), on(g_prof_on.load(std::memory_order_relaxed)) {
+// events come from a pool and go back to it when their pair has been read: a profiled step creates and destroys none (two
+// hipEventCreate per scope and two hipEventDestroy per drain used to sit between the launches of the region being timed).
+// One pool per device: an event belongs to the device it was created on (multi.hip drives several devices from one process).
+// lwkzg_profile_reset destroys what the pools hold.
+static std::map<int, std::vector<hipEvent_t>> g_prof_pool;
+
+static bool prof_event(hipEvent_t *e, int dev) {
+    {
+        std::lock_guard<std::mutex> lk(g_prof_mu);
+        auto &pool = g_prof_pool[dev];
+        if (!pool.empty()) {
+            *e = pool.back();
+            pool.pop_back();
+            return true;
+        }
+    }
+    return hipEventCreate(e) == hipSuccess;
+}
+
+static void prof_pool_free() {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    for (auto &kv : g_prof_pool)
+        for (hipEvent_t e : kv.second) hipEventDestroy(e);
+    g_prof_pool.clear();
+}
+
+ProfScope::ProfScope(const char *n, hipStream_t s)
+    : name(n), st(s), e0(nullptr), e1(nullptr), dev(0), on(g_prof_on.load(std::memory_order_relaxed)) {
     if (!on) return;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+    if (hipGetDevice(&dev) != hipSuccess || !prof_event(&e0, dev) || !prof_event(&e1, dev)) {
+        if (e0) hipEventDestroy(e0);
+        e0 = nullptr;
         on = false;
         return;
     }
@@ -63,7 +93,7 @@ ProfScope::~ProfScope() {
     if (!on) return;
     hipEventRecord(e1, st);
     std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof_pending.push_back({name, e0, e1});
+    g_prof_pending.push_back({name, e0, e1, dev});
 }
 
 static void prof_drain() {
@@ -75,8 +105,9 @@ static void prof_drain() {
             a.launches++;
             a.total_ms += ms;
         }
-        hipEventDestroy(r.e0);
-        hipEventDestroy(r.e1);
+        auto &pool = g_prof_pool[r.dev];
+        pool.push_back(r.e0);
+        pool.push_back(r.e1);
     }
     g_prof_pending.clear();
 }
@@ -751,8 +782,22 @@ static G1Xyzz29 *msm_sums_stage(Ctx *c, const uint32_t *scalars_raw, size_t n, h
     return sums;
 }
 
+// redo_cleared: the caller's parse kernel, in front on `st`, has cleared the n redo flags of slot `base` (coefficients_stage: zero2)
 void msm_stages(Ctx *c, const uint32_t *scalars_raw, uint8_t *out48, size_t n, hipStream_t st, size_t base, bool shared_chip,
-                bool lagrange) {
+                bool lagrange, bool redo_cleared) {
+    Workspace &w = c->ws;
+    if (lagrange ? c->lag.direct_table : c->direct_table) {
+        // the direct table with one workgroup per blob folds, inverts and compresses in one launch (direct.hip: k_commit_tail); every other
+        // geometry leaves the sums as msm_sums_stage does and the finalize launch follows (same workspace roles as there)
+        G1Xyzz29 *sums = w.sums + base;
+        uint32_t *redo = w.bucket_start + base * (size_t)(kNumBuckets + 1);
+        if (!launch_direct_msm_compressed(lagrange ? c->lag.direct_bits : c->direct_bits, lagrange ? c->lag.direct_tab.win_dev : c->direct_tab.win_dev,
+                                          lagrange ? c->lag.direct_row_bytes : c->direct_row_bytes, scalars_raw, w.buckets + base * (size_t)kNumBuckets,
+                                          (G1Xyzz29 *)(w.sorted + base * (size_t)kMaxEntries), redo, sums, out48, n, st,
+                                          (shared_chip || peer_busy(c)) ? 2048 : 0, redo_cleared))
+            launch_finalize_compress(sums, out48, n, st);
+        return;
+    }
     launch_finalize_compress(msm_sums_stage(c, scalars_raw, n, st, base, shared_chip, lagrange), out48, n, st);
 }
 
@@ -859,11 +904,12 @@ bool coefficients_to_msm_form(Ctx *c, int mode, size_t n, hipStream_t st, size_t
 // form (proof_in_evaluation_form; quotient_stage reads what this function left) -- the blob's own evaluations, copied and
 // range-checked with no transform at all. Returns true in that case: an MSM of these scalars must run on the Lagrange form.
 static bool coefficients_stage(Ctx *c, const uint8_t *blobs, size_t n, int mode, int32_t *status, hipStream_t st,
-                               size_t base = 0, bool evaluations_ok = false, uint32_t *zero = nullptr, uint32_t zero_words = 0) {
+                               size_t base = 0, bool evaluations_ok = false, uint32_t *zero = nullptr, uint32_t zero_words = 0,
+                               uint32_t *zero2 = nullptr, uint32_t zero2_words = 0) {
     Workspace &w = c->ws;
     uint32_t *scalars = w.scalars + base * (size_t)kBlobElems * 8;
     if (mode == LWKZG_MODE_REFERENCE) {
-        launch_parse_be_reduce(blobs, scalars, n * kBlobElems, st, zero, zero_words);   // (zero: reference mode only -- the caller checks)
+        launch_parse_be_reduce(blobs, scalars, n * kBlobElems, st, zero, zero_words, zero2, zero2_words);   // (zero, zero2: reference mode only -- the caller checks)
     } else if (evaluations_ok ? commit_on_lagrange(c, mode) : proof_in_evaluation_form(c, mode)) {
         launch_copy_le_check(blobs, scalars, status, n, st);
         return true;
@@ -898,11 +944,18 @@ C_KZG_RET commit_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, size
     for (size_t off = 0; off < n; off += kMaxChunk) {
         size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
         int32_t *stt = status ? status + off : c->ws.status;
-        LWK_HIP(hipMemsetAsync(stt, 0, m * 4, st));
-        const int ways = m >= 256 ? split_ways((commit_on_lagrange(c, mode) ? c->lag.direct_table : c->direct_table) != nullptr) : 1;
+        const bool direct = (commit_on_lagrange(c, mode) ? c->lag.direct_table : c->direct_table) != nullptr;
+        const int ways = m >= 256 ? split_ways(direct) : 1;
+        // reference mode on one stream: the parse kernel is the first launch of the chunk, and it clears the chunk's status words and the redo
+        // flags of its MSM on its way -- no fill launch in front of the parse and none in front of the accumulation (LWKZG_COMMIT_TAIL=0: both).
+        // (The c-kzg front kernels write status words themselves and keep the fill in front of them.)
+        const bool parse_clears = ways == 1 && mode == LWKZG_MODE_REFERENCE && knobs().commit_tail;
+        if (!parse_clears) LWK_HIP(hipMemsetAsync(stt, 0, m * 4, st));
         if (ways == 1) {
-            const bool lg = coefficients_stage(c, blobs + off * (size_t)kBlobBytes, m, mode, stt, st, 0, true);
-            msm_stages(c, c->ws.scalars, out48 + 48 * off, m, st, 0, false, lg);
+            const bool redo_cleared = parse_clears && direct;
+            const bool lg = coefficients_stage(c, blobs + off * (size_t)kBlobBytes, m, mode, stt, st, 0, true, parse_clears ? (uint32_t *)stt : nullptr,
+                                               parse_clears ? (uint32_t)m : 0, redo_cleared ? c->ws.bucket_start : nullptr, redo_cleared ? (uint32_t)m : 0);
+            msm_stages(c, c->ws.scalars, out48 + 48 * off, m, st, 0, false, lg, redo_cleared);
             continue;
         }
         LWK_HIP(hipEventRecord(c->ev_fork, st));
@@ -2169,6 +2222,7 @@ void lwkzg_profile_enable(int on) {
 }
 void lwkzg_profile_reset(void) {
     prof_drain();
+    prof_pool_free();
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_agg.clear();
 }

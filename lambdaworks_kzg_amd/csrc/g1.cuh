@@ -360,25 +360,52 @@ LWK_HD bool g1_in_subgroup(const G1Affine &p) {
 
 // compress_g1_point, /root/reference/src/compression.rs:33-60 (ZCash format):
 // bit7 = compressed, bit6 = infinity (x = 0), bit5 = (p - y < y).
-LWK_HD void g1_compress_affine(uint8_t out[48], const G1Affine &a) {
+// The 48 bytes as twelve little-endian words, o[k] = bytes 4k .. 4k + 3 (what a kernel that stores words wants: k_commit_tail);
+// the byte forms below are this one unpacked.
+LWK_HD void g1_compress_affine_words(uint32_t o[12], const G1Affine &a) {
     uint32_t rx[12], ry[12], ryn[12];
     fe_to_raw<FpParams>(rx, a.x);
     fe_to_raw<FpParams>(ry, a.y);
     fe_to_raw<FpParams>(ryn, neg(a.y));
-    raw_to_be<12>(out, rx);
-    out[0] |= 0x80;
+#pragma unroll
+    for (int k = 0; k < 12; k++) o[k] = __builtin_bswap32(rx[11 - k]);   // big-endian bytes of x, most significant limb first
+    o[0] |= 0x80u;
     // y_neg.representative() < y.representative()
-    if (!raw_geq<12>(ryn, ry)) out[0] |= 0x20;
+    if (!raw_geq<12>(ryn, ry)) o[0] |= 0x20u;
+}
+
+template <class X>
+LWK_HD void g1_compress_words(uint32_t o[12], const X &p) {
+    if (p.is_inf()) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) o[k] = 0;
+        o[0] = 0xc0u;
+        return;
+    }
+    g1_compress_affine_words(o, xyzz_to_affine(p));
+}
+
+LWK_HD void g1_words_to_bytes48(uint8_t out[48], const uint32_t o[12]) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        out[4 * k] = (uint8_t)o[k];
+        out[4 * k + 1] = (uint8_t)(o[k] >> 8);
+        out[4 * k + 2] = (uint8_t)(o[k] >> 16);
+        out[4 * k + 3] = (uint8_t)(o[k] >> 24);
+    }
+}
+
+LWK_HD void g1_compress_affine(uint8_t out[48], const G1Affine &a) {
+    uint32_t o[12];
+    g1_compress_affine_words(o, a);
+    g1_words_to_bytes48(out, o);
 }
 
 template <class X>
 LWK_HD void g1_compress(uint8_t out[48], const X &p) {
-    if (p.is_inf()) {
-        for (int i = 0; i < 48; i++) out[i] = 0;
-        out[0] = 0xc0;
-        return;
-    }
-    g1_compress_affine(out, xyzz_to_affine(p));
+    uint32_t o[12];
+    g1_compress_words(o, p);
+    g1_words_to_bytes48(out, o);
 }
 
 // decompress_g1_point, /root/reference/src/compression.rs:62-103, without the subgroup check

@@ -16,13 +16,16 @@ struct ProfScope {
     const char *name;
     hipStream_t st;
     hipEvent_t e0, e1;
+    int dev;   // the device current at the scope's start: its events were created on it and go back to that device's pool
     bool on;
 };
 
 // ---- scalar ingest (msm.hip)
 // Mode R: 32-byte big-endian elements -> canonical 8xu32 little-endian limbs, reduced mod r
 // (blob_to_polynomial, /root/reference/src/utils.rs:27-41).
-void launch_parse_be_reduce(const uint8_t *blobs, uint32_t *scalars_raw, size_t n_elems, hipStream_t st, uint32_t *zero = nullptr, uint32_t zero_words = 0);
+// zero / zero2: up to two regions of words the launch clears on its way (fewer words each than there are elements)
+void launch_parse_be_reduce(const uint8_t *blobs, uint32_t *scalars_raw, size_t n_elems, hipStream_t st, uint32_t *zero = nullptr, uint32_t zero_words = 0,
+                            uint32_t *zero2 = nullptr, uint32_t zero2_words = 0);
 // Mode C: 32-byte little-endian elements, must be canonical (else status[blob] = BADARGS) -> Montgomery Fr
 
 // ---- MSM (msm.hip)
@@ -69,6 +72,13 @@ void free_direct_table(DirectTable &table);
 void launch_direct_msm(int bits, const uint64_t *win_dev, size_t row_bytes, const uint32_t *scalars_raw, G1Xyzz29 *lane_scratch,
                        G1Xyzz29 *partials, uint32_t *redo, G1Xyzz29 *sums, size_t n_blobs, hipStream_t st, int fill = 0,
                        uint32_t *redo_flag_out = nullptr);
+// the same, with the compressed sums in out48 as well where the launch set can leave them itself (one workgroup per blob on the
+// hand-scheduled kernel: the fold, the inversion and the compression are one launch, k_commit_tail). Returns false where it could not:
+// sums[] are complete as after launch_direct_msm, out48 is untouched and launch_finalize_compress is the caller's.
+// redo_cleared: a kernel in front of this launch set on `st` has cleared redo[0 .. n_blobs) (launch_parse_be_reduce's second region)
+bool launch_direct_msm_compressed(int bits, const uint64_t *win_dev, size_t row_bytes, const uint32_t *scalars_raw, G1Xyzz29 *lane_scratch,
+                                  G1Xyzz29 *partials, uint32_t *redo, G1Xyzz29 *sums, uint8_t *out48, size_t n_blobs, hipStream_t st,
+                                  int fill = 0, bool redo_cleared = false);
 uint32_t direct_one_blob_counter_words(int bits);   // r06: see direct.hip
 // sums[b] recomputed for the blobs with only_if[b] != 0 (one workgroup each, complete branches; exits at once for the others)
 void launch_direct_msm_only(int bits, const uint64_t *win_dev, size_t row_bytes, const uint32_t *scalars_raw, G1Xyzz29 *sums,
