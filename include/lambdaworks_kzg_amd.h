@@ -9,7 +9,8 @@
  *
  * Everything after "extensions" is additive: batched and device-resident entry points (a
  * synchronous one-blob call cannot reach 10k ops/s), the R/C semantics switch, multi-GPU setup
- * hand-off, and profiling hooks used by bench.py.
+ * hand-off, EIP-7594 cells, cell proofs and their batch verification, and profiling hooks used
+ * by bench.py.
  *
  * Struct layouts follow the reference's #[repr(C)] types (src/lib.rs:45-232). NOTE the
  * reference's blst_fp convention, which this library reproduces bit for bit and which is NOT
@@ -398,6 +399,41 @@ C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch(Cell *cells, KZGProof *proofs
  * whatever its neighbours' status. A call of 8 blobs or more fills whole MSM launch sets. */
 C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch_device(void *cells_dev, void *proofs48_dev, const void *blobs_dev, size_t n,
                                                           const KZGSettings *s, void *stream, int32_t *status_dev);
+
+/* EIP-7594 verify_cell_kzg_proof_batch: do the n items (commitments[i], cell_indices[i], cells[i], proofs[i]) belong together?
+ * c-kzg-4844 2.x's argument order; the same commitment may appear many times and an item may repeat. cells are in the settings' mode's
+ * byte order, as lwkzg_compute_cells_and_kzg_proofs writes them. DESIGN.md section 4i has the definition: commitments de-duplicated by
+ * byte equality in order of first occurrence (m rows), a two-level transcript
+ *     d_i = SHA-256(le64(row_i) | le64(k_i) | cell_i | proof_i)                                    (on the GPU, one hash per cell)
+ *     r   = SHA-256("RCKZGCBATCH__V1_" | le64(4096) | le64(64) | le64(m) | le64(n) | the m distinct commitments | d_0 .. d_(n-1))
+ * read in the mode's byte order and reduced, and one pairing check e(RLC - RLI + RLP, G2) e(-P, g2_values[64]) == 1 over
+ * P = sum r^i pi_i, RLP = sum r^i c_(k_i) pi_i, RLC = sum_j (sum_(row_i = j) r^i) C_j and RLI = [sum r^i I_i(tau)]G1 (I_i: the
+ * interpolant of cell i on its coset). The settings must carry all 65 G2 points.
+ * Returns: C_KZG_BADARGS for ok == NULL, NULL pointers with n > 0 or an index >= 128 (decided on the host before any device work); the
+ * mode's code for a bad input (C_KZG_ERROR in reference mode, C_KZG_BADARGS in c-kzg mode) when a distinct commitment or a proof is
+ * not a compressed point of G1 (infinity allowed) or a cell element is not below r -- cell elements are never reduced, not in
+ * reference mode either: cells are this library's own outputs and always canonical. *ok is false on every error.
+ * n == 0: C_KZG_OK with *ok = true in BOTH modes (the consensus specs' and c-kzg-4844 2.x's rule for cells) -- unlike
+ * verify_blob_kzg_proof_batch, whose empty batch answers false in reference mode.
+ * Batch the columns of a slot into one call: the call's cost is mostly fixed. */
+C_KZG_RET lwkzg_verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
+                                            const Bytes48 *proofs, size_t n, const KZGSettings *s);
+/* the same for inputs already in HBM (16-byte aligned; produced on `stream`, NULL = the context's own); synchronous, *ok is a host bool,
+ * as lwkzg_verify_blob_kzg_proof_batch_device. The cells stay on the device: the commitments and the indices come down, the row and
+ * column lists go up, the digests and the status words come down. */
+C_KZG_RET lwkzg_verify_cell_kzg_proof_batch_device(bool *ok, const void *commitments48_dev, const void *cell_indices_dev,
+                                                   const void *cells_dev, const void *proofs48_dev, size_t n, const KZGSettings *s,
+                                                   void *stream);
+/* r and the four sums of the check, for tests and for a later sharded form, by the verdict call's own code path up to the pairing:
+ * out = r 32 (the mode's byte order) | P | RLC | RLI | RLP, each flag 1 (1 = infinity) | x 48 | y 48 big-endian. Host arguments and
+ * return codes as lwkzg_verify_cell_kzg_proof_batch; n == 0 writes nothing. */
+#define LWKZG_CELL_VERIFY_PARTIAL_BYTES (32 + 4 * 97)
+C_KZG_RET lwkzg_cell_verify_partials(uint8_t *out, const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
+                                     const Bytes48 *proofs, size_t n, const KZGSettings *s);
+/* the transcript alone, on the host (no GPU, no settings): r_out = the challenge of the batch in `mode`'s byte order. NULL pointers with
+ * n > 0, an index >= 128 or an unknown mode: C_KZG_BADARGS. */
+C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
+                                          const Bytes48 *proofs, size_t n, int mode);
 
 /* Host-only test hook for the per-item pairing: the 68 lines of the Miller loop of a ZCash-compressed G2 point (not at infinity) as the
  * device takes them, canonical big-endian lambda.c0 | lambda.c1 | c0.c0 | c0.c1 per line (out: 68 x 192 bytes). No GPU, no settings. */

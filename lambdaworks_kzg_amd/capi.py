@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_verify_blob_kzg_proof_each", "lwkzg_verify_blob_kzg_proof_each_device", "lwkzg_verify_kzg_proof_each",
     "lwkzg_pairing_line_table",
     "lwkzg_compute_cells_and_kzg_proofs", "lwkzg_compute_cells_and_kzg_proofs_batch", "lwkzg_compute_cells_and_kzg_proofs_batch_device",
+    "lwkzg_verify_cell_kzg_proof_batch", "lwkzg_verify_cell_kzg_proof_batch_device", "lwkzg_cell_verify_partials",
+    "lwkzg_cell_batch_challenge_host",
 ]
 
 _lib = None
@@ -115,6 +117,11 @@ def lib():
     l.lwkzg_compute_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, ps]
     l.lwkzg_compute_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, sz, ps, C.POINTER(sz)]
     l.lwkzg_compute_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, vp, sz, ps, vp, vp]
+    pu64 = C.POINTER(C.c_uint64)
+    l.lwkzg_verify_cell_kzg_proof_batch.argtypes = [C.POINTER(C.c_bool), C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_verify_cell_kzg_proof_batch_device.argtypes = [C.POINTER(C.c_bool), vp, vp, vp, vp, sz, ps, vp]
+    l.lwkzg_cell_verify_partials.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_cell_batch_challenge_host.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ci]
     l.lwkzg_shard_range.argtypes = [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]
     pvp, psz = C.POINTER(vp), C.POINTER(sz)
     l.lwkzg_multi_blob_to_kzg_commitment_batch_device.argtypes = [pvp, pvp, psz, vp, psz]
@@ -604,6 +611,55 @@ def compute_cells_and_kzg_proofs_batch_device(cells_ptr, proofs_ptr, blobs_ptr, 
     pointer may be None"""
     _check("lwkzg_compute_cells_and_kzg_proofs_batch_device",
            lib().lwkzg_compute_cells_and_kzg_proofs_batch_device(cells_ptr, proofs_ptr, blobs_ptr, n, ts.ref(), stream, status_ptr))
+
+
+CELL_VERIFY_PARTIAL_BYTES = 32 + 4 * 97
+
+
+def _cell_items(commitments, cell_indices, cells, proofs):
+    """lists (or concatenated bytes) of n commitments, cells and proofs and n indices -> the C arguments"""
+    n = len(cell_indices)
+    cm = commitments if isinstance(commitments, (bytes, bytearray)) else b"".join(commitments)
+    ce = cells if isinstance(cells, (bytes, bytearray)) else b"".join(cells)
+    pf = proofs if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
+    if len(cm) != 48 * n or len(ce) != BYTES_PER_CELL * n or len(pf) != 48 * n:
+        raise ValueError("commitments, cells and proofs must hold one entry per cell index")
+    return bytes(cm), (C.c_uint64 * max(n, 1))(*cell_indices), bytes(ce), bytes(pf), n
+
+
+def verify_cell_kzg_proof_batch(commitments, cell_indices, cells, proofs, ts):
+    """EIP-7594 verify_cell_kzg_proof_batch (lwkzg_verify_cell_kzg_proof_batch): do the cells belong to the commitments? Item i is
+    (commitments[i], cell_indices[i], cells[i], proofs[i]); cells in the settings' mode's byte order. The empty batch answers True."""
+    cm, idx, ce, pf, n = _cell_items(commitments, cell_indices, cells, proofs)
+    ok = C.c_bool(False)
+    _check("lwkzg_verify_cell_kzg_proof_batch", lib().lwkzg_verify_cell_kzg_proof_batch(C.byref(ok), cm, idx, ce, pf, n, ts.ref()))
+    return bool(ok.value)
+
+
+def verify_cell_kzg_proof_batch_device(comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, ts, stream=None):
+    """the same on DEVICE pointers (48 n commitment bytes, n uint64 indices, 2048 n cell bytes, 48 n proof bytes, produced on
+    `stream`); the verdict is a host bool, the call synchronous"""
+    ok = C.c_bool(False)
+    _check("lwkzg_verify_cell_kzg_proof_batch_device",
+           lib().lwkzg_verify_cell_kzg_proof_batch_device(C.byref(ok), comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, ts.ref(), stream))
+    return bool(ok.value)
+
+
+def cell_verify_partials(commitments, cell_indices, cells, proofs, ts):
+    """r (32 bytes, the mode's byte order) and the four sums P, RLC, RLI, RLP of the check (97 bytes each: flag | x | y), by the
+    verdict call's own code path up to the pairing"""
+    cm, idx, ce, pf, n = _cell_items(commitments, cell_indices, cells, proofs)
+    out = C.create_string_buffer(CELL_VERIFY_PARTIAL_BYTES)
+    _check("lwkzg_cell_verify_partials", lib().lwkzg_cell_verify_partials(out, cm, idx, ce, pf, n, ts.ref()))
+    return out.raw
+
+
+def cell_batch_challenge_host(commitments, cell_indices, cells, proofs, mode):
+    """the two-level transcript of the cell batch alone (host only): r, 32 bytes in `mode`'s byte order"""
+    cm, idx, ce, pf, n = _cell_items(commitments, cell_indices, cells, proofs)
+    out = C.create_string_buffer(32)
+    _check("lwkzg_cell_batch_challenge_host", lib().lwkzg_cell_batch_challenge_host(out, cm, idx, ce, pf, n, mode))
+    return out.raw
 
 
 def pairing_line_table(g2_compressed):

@@ -1,0 +1,272 @@
+// cells_verify.hip -- the kernels of EIP-7594 verify_cell_kzg_proof_batch that the blob batch verification does not already have
+// (the pipeline is cells_verify_api.hip). For n items (C_i, k_i, cell_i, pi_i) over m distinct commitments:
+//
+//  * Digests: d_i = SHA-256(le64(row_i) | le64(k_i) | cell_i | pi_i), 2112 bytes = 33 blocks and the padding block, one lane per
+//    cell, every cell in parallel; the range check of the cell's 64 elements rides on the same read.
+//  * Scalars behind r: a_i = r^i from the table of r^(2^k), b_i = a_i c_{k_i} (c_k = w128^bitrev7(k), a forward twiddle or its
+//    negative), both split as lo + hi z^2 for k_vmsm_accumulate; the weights w_j = sum_{row_i = j} a_i of the distinct commitments
+//    in the same form.
+//  * Column sums and interpolation: S_k[t] = sum_{k_i = k} a_i cell_i[t], a 64-point inverse transform of S_k in LDS (the cell's
+//    elements are the evaluations on the coset h_k <w64> in bit-reversed order: exactly the order a decimation-in-time transform
+//    consumes), coefficient t scaled by h_k^-t / 64, and the 128 columns summed into the 64 coefficients of I(X) = sum a_i I_i(X),
+//    written as canonical limbs into one 4096-scalar MSM slot whose other 4032 scalars are zero.
+//
+// Items are grouped by row and by column on the host (a counting sort over the indices it holds anyway): perm_* lists the items
+// of group g at [off[g], off[g + 1]).
+#include "kernels.h"
+#include "glv.cuh"
+#include "sha256_round.cuh"
+
+namespace lwk {
+
+// w8192^-1 and 1/64 in Montgomery form (w8192 = 7^((r-1)/8192); tests/test_cell_verify_cpu.py holds both against Python's pow)
+__device__ __constant__ uint32_t kInvOmega8192Mont[8] = {0xa1355e75u, 0x507dbef9u, 0x9b69cc1au, 0xeb71fd25u,
+                                                         0xee0557f8u, 0x6042c8dbu, 0x9dbce162u, 0x2415d770u};
+__device__ __constant__ uint32_t kInv64Mont[8] = {0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u,
+                                                  0x00000000u, 0x00000000u, 0x00000000u, 0x04000000u};
+
+namespace {
+
+// the canonical integer of a 32-byte element from its two 16-byte halves as they lie in memory
+__device__ __forceinline__ void element_limbs(uint32_t t[8], const uint4 &first, const uint4 &second, int le) {
+    if (le) {
+        t[0] = first.x, t[1] = first.y, t[2] = first.z, t[3] = first.w;
+        t[4] = second.x, t[5] = second.y, t[6] = second.z, t[7] = second.w;
+    } else {
+        t[7] = __builtin_bswap32(first.x), t[6] = __builtin_bswap32(first.y), t[5] = __builtin_bswap32(first.z), t[4] = __builtin_bswap32(first.w);
+        t[3] = __builtin_bswap32(second.x), t[2] = __builtin_bswap32(second.y), t[1] = __builtin_bswap32(second.z), t[0] = __builtin_bswap32(second.w);
+    }
+}
+
+__device__ __forceinline__ void absorb(uint32_t w[16], int j, const uint4 &c) {
+    w[4 * j] = __builtin_bswap32(c.x);
+    w[4 * j + 1] = __builtin_bswap32(c.y);
+    w[4 * j + 2] = __builtin_bswap32(c.z);
+    w[4 * j + 3] = __builtin_bswap32(c.w);
+}
+
+// c_k = w128^bitrev7(k) = w4096^(32 bitrev7(k)), Montgomery form, from the forward twiddles w^e, e < 2048 (w^2048 = -1)
+__device__ __forceinline__ Fr c_of_cell(const Fr *tw_fwd, uint32_t k) {
+    const uint32_t e = 32 * (__brev(k & 127u) >> 25);
+    return e < kBlobElems / 2 ? tw_fwd[e] : neg(tw_fwd[e - kBlobElems / 2]);
+}
+
+__device__ __forceinline__ void store_split(uint32_t *sc, size_t i, const uint32_t raw[8]) {
+    uint32_t lo[4], hi[4];
+    split_by_z2_barrett(lo, hi, raw);
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        sc[8 * i + q] = lo[q];
+        sc[8 * i + 4 + q] = hi[q];
+    }
+}
+
+}  // namespace
+
+// ---- the per-cell transcript digests and the range check -------------------------------------------------------------------------
+// The message as 132 16-byte chunks: 0 = le64(row) | le64(k), 1 .. 128 = the cell, 129 .. 131 = the proof; block b holds chunks
+// 4 b .. 4 b + 3, so an element (cell chunks 2 e, 2 e + 1 = message chunks 2 e + 1, 2 e + 2) is complete at every even message chunk
+// from 2 to 128. digests: 32 bytes per item; status[i] = bad_code where an element is not below r.
+__global__ __launch_bounds__(64) void k_cellv_digests(const uint4 *__restrict__ cells, const uint4 *__restrict__ proofs,
+                                                      const uint32_t *__restrict__ rows, const uint64_t *__restrict__ idx,
+                                                      uint32_t *__restrict__ digests, int32_t *__restrict__ status, int bad_code, int le,
+                                                      uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 *cell = cells + (size_t)2 * kCellElems * i;
+    const uint4 *pf = proofs + (size_t)3 * i;
+    const uint64_t k = idx[i];
+    uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+    uint32_t w[16], t[8];
+    bool bad = false;
+    uint4 prev = make_uint4(rows[i], 0u, (uint32_t)k, (uint32_t)(k >> 32));
+    // block 0: the header and cell chunks 0 .. 2
+    absorb(w, 0, prev);
+#pragma unroll
+    for (int j = 1; j < 4; j++) {
+        const uint4 c = cell[j - 1];
+        absorb(w, j, c);
+        if (j == 2) {
+            element_limbs(t, prev, c, le);
+            bad |= raw_geq<8>(t, FrParams::MOD);
+        }
+        prev = c;
+    }
+    sha256_compress(h, w);
+    // blocks 1 .. 31: cell chunks 4 b - 1 .. 4 b + 2
+#pragma unroll 1
+    for (int b = 1; b < 32; b++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint4 c = cell[4 * b - 1 + j];
+            absorb(w, j, c);
+            if (!(j & 1)) {
+                element_limbs(t, prev, c, le);
+                bad |= raw_geq<8>(t, FrParams::MOD);
+            }
+            prev = c;
+        }
+        sha256_compress(h, w);
+    }
+    // block 32: the last cell chunk and the proof
+    {
+        const uint4 c = cell[2 * kCellElems - 1];
+        absorb(w, 0, c);
+        element_limbs(t, prev, c, le);
+        bad |= raw_geq<8>(t, FrParams::MOD);
+#pragma unroll
+        for (int j = 1; j < 4; j++) absorb(w, j, pf[j - 1]);
+        sha256_compress(h, w);
+    }
+    // padding: 0x80, zeros, the length in bits (2112 * 8) big-endian
+    w[0] = 0x80000000u;
+#pragma unroll
+    for (int j = 1; j < 15; j++) w[j] = 0;
+    w[15] = 2112u * 8u;
+    sha256_compress(h, w);
+    uint4 *out = (uint4 *)(digests + 8 * (size_t)i);
+    out[0] = make_uint4(__builtin_bswap32(h[0]), __builtin_bswap32(h[1]), __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
+    out[1] = make_uint4(__builtin_bswap32(h[4]), __builtin_bswap32(h[5]), __builtin_bswap32(h[6]), __builtin_bswap32(h[7]));
+    if (bad) status[i] = bad_code;
+}
+
+void launch_cellv_digests(const uint8_t *cells, const uint8_t *proofs48, const uint32_t *rows, const uint64_t *idx, uint8_t *digests32,
+                          int32_t *status, int bad_code, int le, size_t n, hipStream_t st) {
+    ProfScope p("k_cellv_digests", st);
+    hipLaunchKernelGGL(k_cellv_digests, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const uint4 *)cells, (const uint4 *)proofs48, rows,
+                       idx, (uint32_t *)digests32, status, bad_code, le, (uint32_t)n);
+}
+
+// ---- behind r: a_i = r^i, b_i = a_i c_{k_i} ------------------------------------------------------------------------------------------
+// pw as k_vmsm_scalars takes it (r^(2^k), k < 32, then r^first; the cell batch starts at r^0). a_mont keeps a_i in Montgomery form
+// for the weights and the column sums; sc_a / sc_b are the split forms of a_i and b_i.
+__global__ __launch_bounds__(64) void k_cellv_scalars(const Fr *__restrict__ pw, const uint64_t *__restrict__ idx, const Fr *__restrict__ tw_fwd,
+                                                      Fr *__restrict__ a_mont, uint32_t *__restrict__ sc_a, uint32_t *__restrict__ sc_b,
+                                                      uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fr a = pw[32];
+#pragma unroll 1
+    for (int k = 0; k < 32; k++) {
+        if ((i >> k) == 0) break;
+        if ((i >> k) & 1u) a = a * pw[k];
+    }
+    a_mont[i] = a;
+    const Fr b = a * c_of_cell(tw_fwd, (uint32_t)idx[i]);
+    uint32_t raw[8];
+    fe_to_raw<FrParams>(raw, a);
+    store_split(sc_a, i, raw);
+    fe_to_raw<FrParams>(raw, b);
+    store_split(sc_b, i, raw);
+}
+
+// w_j = sum of a_i over the items of row j, one wave per row
+__global__ __launch_bounds__(64) void k_cellv_row_weights(const Fr *__restrict__ a_mont, const uint32_t *__restrict__ perm_row,
+                                                          const uint32_t *__restrict__ row_off, uint32_t *__restrict__ sc_c) {
+    __shared__ Fr sh[64];
+    const uint32_t j = blockIdx.x, t = threadIdx.x;
+    const uint32_t lo = row_off[j], hi = row_off[j + 1];
+    Fr acc = Fr::zero();
+    for (uint32_t s = lo + t; s < hi; s += 64) acc = acc + a_mont[perm_row[s]];
+    sh[t] = acc;
+    __syncthreads();
+    for (int d = 32; d >= 1; d >>= 1) {
+        if ((int)t < d) sh[t] = sh[t] + sh[t + d];
+        __syncthreads();
+    }
+    if (t != 0) return;
+    uint32_t raw[8];
+    fe_to_raw<FrParams>(raw, sh[0]);
+    store_split(sc_c, j, raw);
+}
+
+void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b,
+                          const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t n, size_t m, hipStream_t st) {
+    {
+        ProfScope p("k_cellv_scalars", st);
+        hipLaunchKernelGGL(k_cellv_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pw, idx, tw_fwd, a_mont, sc_a, sc_b, (uint32_t)n);
+    }
+    ProfScope p("k_cellv_row_weights", st);
+    hipLaunchKernelGGL(k_cellv_row_weights, dim3((unsigned)m), dim3(64), 0, st, (const Fr *)a_mont, perm_row, row_off, sc_c);
+}
+
+// ---- behind r: the column sums, their interpolation, and the 64 coefficients of I(X) ------------------------------------------------
+// One workgroup per column k, four waves: wave v sums every fourth item of the column (lane t = element t of the cell; a wave reads
+// a cell's 2 KiB in one pass), the four partial sums meet in LDS, and 32 lanes run the six stages of the 64-point decimation-in-time
+// inverse transform in place. The cell's values are canonical integers and stay so: a Montgomery product of a Montgomery-form
+// factor (a_i, a twiddle, the scale) with a raw value is the raw product. colcoef[64 k + t]: coefficient t of column k's share,
+// canonical limbs (zero for a column nobody sampled).
+__global__ __launch_bounds__(256) void k_cellv_columns(const uint4 *__restrict__ cells, const Fr *__restrict__ a_mont,
+                                                       const uint32_t *__restrict__ perm_col, const uint32_t *__restrict__ col_off,
+                                                       const Fr *__restrict__ tw_inv, Fr *__restrict__ colcoef, int le) {
+    __shared__ Fr part[4][kCellElems];
+    __shared__ Fr buf[kCellElems];
+    const uint32_t k = blockIdx.x, t = threadIdx.x & 63u, v = threadIdx.x >> 6;
+    const uint32_t lo = col_off[k], hi = col_off[k + 1];
+    if (lo == hi) {   // (the same for the whole workgroup: no barrier is left behind)
+        if (v == 0) colcoef[kCellElems * k + t] = Fr::zero();
+        return;
+    }
+    Fr acc = Fr::zero();
+#pragma unroll 1
+    for (uint32_t s = lo + v; s < hi; s += 4) {
+        const uint32_t i = perm_col[s];
+        const uint4 *e = cells + ((size_t)kCellElems * i + t) * 2;
+        Fr x;
+        element_limbs(x.l, e[0], e[1], le);
+        acc = acc + a_mont[i] * x;
+    }
+    part[v][t] = acc;
+    __syncthreads();
+    if (v == 0) buf[t] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+    __syncthreads();
+#pragma unroll 1
+    for (int s = 0; s < 6; s++) {
+        if (threadIdx.x < 32) {
+            const uint32_t half = 1u << s, b = threadIdx.x, q = b & (half - 1);
+            const uint32_t i0 = ((b >> s) << (s + 1)) + q, i1 = i0 + half;
+            // w_(2 half)^-q = w64^-(q 32 / half) = w4096^-(64 q (32 >> s))
+            const Fr u = buf[i0], x = tw_inv[64 * q * (32u >> s)] * buf[i1];
+            buf[i0] = u + x;
+            buf[i1] = u - x;
+        }
+        __syncthreads();
+    }
+    if (v != 0) return;
+    // times h_k^-t / 64, h_k = w8192^bitrev7(k): the exponent e = bitrev7(k) t < 8192; w8192^-e = w4096^-(e >> 1) (w8192^-1 if e is odd)
+    const uint32_t e = (__brev(k) >> 25) * t, half_e = e >> 1;
+    Fr sc = half_e < kBlobElems / 2 ? tw_inv[half_e] : neg(tw_inv[half_e - kBlobElems / 2]);
+    Fr c;
+    if (e & 1u) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) c.l[j] = kInvOmega8192Mont[j];
+        sc = sc * c;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) c.l[j] = kInv64Mont[j];
+    colcoef[kCellElems * k + t] = (sc * c) * buf[t];
+}
+
+// scalar t of the MSM slot: the sum of the 128 columns' coefficient t for t < 64, zero above
+__global__ __launch_bounds__(256) void k_cellv_coeffs(const Fr *__restrict__ colcoef, Fr *__restrict__ slot) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    Fr acc = Fr::zero();
+    if (t < (uint32_t)kCellElems) {
+#pragma unroll 1
+        for (int k = 0; k < kCellsPerBlob; k++) acc = acc + colcoef[kCellElems * k + t];
+    }
+    slot[t] = acc;
+}
+
+void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off, const Fr *tw_inv,
+                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st) {
+    {
+        ProfScope p("k_cellv_columns", st);
+        hipLaunchKernelGGL(k_cellv_columns, dim3(kCellsPerBlob), dim3(256), 0, st, (const uint4 *)cells, a_mont, perm_col, col_off, tw_inv,
+                           colcoef, le);
+    }
+    ProfScope p("k_cellv_coeffs", st);
+    hipLaunchKernelGGL(k_cellv_coeffs, dim3(kBlobElems / 256), dim3(256), 0, st, (const Fr *)colcoef, (Fr *)slot_raw);
+}
+
+}  // namespace lwk

@@ -1,0 +1,406 @@
+// cells_verify_api.hip -- EIP-7594 verify_cell_kzg_proof_batch: lwkzg_verify_cell_kzg_proof_batch (+ _device), lwkzg_cell_verify_partials,
+// lwkzg_cell_batch_challenge_host. DESIGN.md section 4i.
+//
+// One call, one stream, two host visits:
+//   host     indices checked (< 128), commitments de-duplicated by byte equality in order of first occurrence (m rows), the items
+//            counting-sorted by row and by column (the host holds the 48 n + 8 n bytes anyway: the device form copies them down)
+//   device   both point sets validated (the m distinct commitments padded with infinity encodings to the proofs' n, so that the
+//            two-set launches of the blob batch serve), the per-cell digests and the element range check; digests and status come down
+//   device   beside the host's hash: the byte-spaced rows of both point sets (k_vmsm_multiples)
+//   host     r from the distinct commitments and the digests; r^(2^k) goes up
+//   device   scalars, row weights, column sums + interpolation, the 64-term MSM on the engine's own launch set, the three
+//            variable-base sums (vmsm.hip); four points come down
+//   host     the pairing check against g2_values[64] (pairing.hip keeps its line table beside the others)
+#include "engine.h"
+#include "knobs.h"
+
+#include <string.h>
+
+#include <chrono>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace lwk {
+
+void sha256_fast(uint8_t out[32], const uint8_t *msg, size_t len);  // sha256_host.hip
+
+namespace {
+
+constexpr size_t kCellBytes = (size_t)kCellElems * 32;
+constexpr size_t kItemMsg = 16 + kCellBytes + 48;   // le64(row) | le64(k) | cell | proof
+constexpr size_t kPinTail = 33 * sizeof(Fr) + 3 * 96 + 3 * 4 + 48 + 12;   // powers up; three sums, their flags and RLI down
+
+C_KZG_RET bad_input(int mode) { return mode == LWKZG_MODE_CKZG ? C_KZG_BADARGS : C_KZG_ERROR; }
+
+// what the host derives from the commitments and the indices
+struct Grouping {
+    size_t m = 0;
+    std::vector<uint8_t> distinct;    // 48 m: the distinct commitments as given, in order of first occurrence
+    std::vector<uint32_t> rows;       // n
+    std::vector<uint32_t> perm_row, row_off, perm_col, col_off;   // n, m + 1, n, 129
+};
+
+bool group_items(Grouping &g, const uint8_t *comms, const uint64_t *idx, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (idx[i] >= (uint64_t)kCellsPerBlob) return false;
+    g.rows.resize(n);
+    std::unordered_map<std::string, uint32_t> seen;
+    for (size_t i = 0; i < n; i++) {
+        auto it = seen.emplace(std::string((const char *)comms + 48 * i, 48), (uint32_t)g.m);
+        if (it.second) {
+            g.distinct.insert(g.distinct.end(), comms + 48 * i, comms + 48 * i + 48);
+            g.m++;
+        }
+        g.rows[i] = it.first->second;
+    }
+    auto sort_by = [n](std::vector<uint32_t> &perm, std::vector<uint32_t> &off, size_t groups, auto key) {
+        off.assign(groups + 1, 0);
+        for (size_t i = 0; i < n; i++) off[key(i) + 1]++;
+        for (size_t j = 0; j < groups; j++) off[j + 1] += off[j];
+        std::vector<uint32_t> at(off.begin(), off.end() - 1);
+        perm.resize(n);
+        for (size_t i = 0; i < n; i++) perm[at[key(i)]++] = (uint32_t)i;
+    };
+    sort_by(g.perm_row, g.row_off, g.m, [&](size_t i) { return (size_t)g.rows[i]; });
+    sort_by(g.perm_col, g.col_off, kCellsPerBlob, [&](size_t i) { return (size_t)idx[i]; });
+    return true;
+}
+
+// the device side of a batch, carved out of one allocation
+struct Bufs {
+    uint8_t *cells, *proofs, *comm_in, *canon_p, *canon_c, *digests, *out96, *rli48;
+    uint64_t *idx;
+    uint32_t *rows, *perm_row, *row_off, *perm_col, *col_off, *verdict_p, *verdict_c, *sc_a, *sc_b, *sc_c;
+    int32_t *kind_p, *kind_c, *status, *inf;
+    G1Affine29 *pts_p, *pts_c, *tab_p, *tab_c;
+    G1Xyzz29 *vm_tmp, *partial, *bsum;
+    F29<2> *vm_pre;
+    Fr *a_mont, *pw, *colcoef;
+};
+
+size_t carve(Bufs &b, uint8_t *base, size_t cap) {
+    size_t off = 0;
+    auto take = [&](auto *&p, size_t bytes) {
+        p = (std::remove_reference_t<decltype(p)>)(base + off);
+        off += (bytes + 255) & ~(size_t)255;
+    };
+    take(b.cells, cap * kCellBytes);
+    take(b.proofs, cap * 48);
+    take(b.comm_in, cap * 48);
+    take(b.canon_p, cap * 48);
+    take(b.canon_c, cap * 48);
+    take(b.digests, cap * 32);
+    take(b.out96, 3 * 96);
+    take(b.rli48, 48);
+    take(b.idx, cap * 8);
+    take(b.rows, cap * 4);
+    take(b.perm_row, cap * 4);
+    take(b.row_off, (cap + 1) * 4);
+    take(b.perm_col, cap * 4);
+    take(b.col_off, (kCellsPerBlob + 1) * 4);
+    take(b.verdict_p, cap * 4);
+    take(b.verdict_c, cap * 4);
+    take(b.sc_a, cap * 32);
+    take(b.sc_b, cap * 32);
+    take(b.sc_c, cap * 32);
+    take(b.kind_p, cap * 4);
+    take(b.kind_c, cap * 4);
+    take(b.status, cap * 4);
+    take(b.inf, 3 * 4);
+    take(b.pts_p, cap * sizeof(G1Affine29));
+    take(b.pts_c, cap * sizeof(G1Affine29));
+    take(b.tab_p, cap * kVmsmRows * sizeof(G1Affine29));
+    take(b.tab_c, cap * kVmsmRows * sizeof(G1Affine29));
+    take(b.vm_tmp, cap * 2 * kVmsmSteps * sizeof(G1Xyzz29));
+    take(b.partial, 3 * vmsm_max_slices(cap) * 256 * sizeof(G1Xyzz29));
+    take(b.bsum, 3 * 256 * sizeof(G1Xyzz29));
+    take(b.vm_pre, cap * 2 * kVmsmSteps * sizeof(F29<2>));
+    take(b.a_mont, cap * sizeof(Fr));
+    take(b.pw, 33 * sizeof(Fr));
+    take(b.colcoef, (size_t)kCellsPerBlob * kCellElems * sizeof(Fr));
+    return off;
+}
+
+// grow-only, kept with the settings object: no allocation in steady state (caller holds c->mu)
+C_KZG_RET reserve(Ctx *c, size_t n, Bufs &b) {
+    if (!c->cellv_ev) LWK_HIP(hipEventCreateWithFlags(&c->cellv_ev, hipEventDisableTiming));
+    if (c->cellv_cap < n) {
+        LWK_HIP(hipDeviceSynchronize());   // work on any stream may still be using the old buffers
+        if (c->cellv_buf) hipFree(c->cellv_buf);
+        if (c->cellv_pin) hipHostFree(c->cellv_pin);
+        c->cellv_buf = c->cellv_pin = nullptr;
+        c->cellv_cap = 0;
+        size_t cap = 256;
+        while (cap < n) cap <<= 1;
+        Bufs probe;
+        const size_t bytes = carve(probe, nullptr, cap);
+        if (hipMalloc((void **)&c->cellv_buf, bytes) != hipSuccess || hipHostMalloc((void **)&c->cellv_pin, cap * 36 + kPinTail) != hipSuccess) {
+            (void)hipGetLastError();
+            if (c->cellv_buf) hipFree(c->cellv_buf);
+            c->cellv_buf = nullptr;
+            set_error("verify_cell_kzg_proof_batch: no memory for a batch of %zu cells (%zu bytes on the device)", n, bytes);
+            return C_KZG_MALLOC;
+        }
+        c->cellv_cap = cap;
+    }
+    carve(b, c->cellv_buf, c->cellv_cap);
+    return C_KZG_OK;
+}
+
+struct PhaseClock {   // LWKZG_TIMING=1: device time between the phases' boundaries on the call's stream, host time beside it
+    static constexpr int kMarks = 7;
+    hipEvent_t ev[kMarks] = {};
+    bool on = false;
+    hipStream_t st = nullptr;
+    void begin(hipStream_t s) {
+        on = knobs().timing;
+        st = s;
+        if (!on) return;
+        for (auto &e : ev)
+            if (hipEventCreate(&e) != hipSuccess) on = false;
+    }
+    void mark(int k) {
+        if (on) hipEventRecord(ev[k], st);
+    }
+    float ms(int a, int b) {
+        float t = 0;
+        return on && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : -1.f;
+    }
+    ~PhaseClock() {
+        for (auto &e : ev)
+            if (e) hipEventDestroy(e);
+    }
+};
+
+double wall_ms(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+// r (canonical limbs), the three sums of vmsm.hip and the compressed RLI of a batch. Host pointers are uploaded into the context's
+// buffer; device pointers (device_inputs) are read where they are, except the commitments and the indices, which come down first.
+C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], uint8_t rli48[48], const uint8_t *comms, const uint64_t *idx,
+                          const uint8_t *cells, const uint8_t *proofs, size_t n, const KZGSettings *s, int mode, bool device_inputs,
+                          hipStream_t caller) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int le = mode == LWKZG_MODE_CKZG;
+    Grouping g;
+    if (!device_inputs && !group_items(g, comms, idx, n)) {   // before any device work: decidable without a GPU
+        set_error("verify_cell_kzg_proof_batch: a cell index is not below %d", kCellsPerBlob);
+        return C_KZG_BADARGS;
+    }
+    Ctx *c = ctx_of(s);
+    if (!c) return C_KZG_ERROR;
+    if (!s->g2_values) {
+        set_error("KZGSettings.g2_values is NULL");
+        return C_KZG_ERROR;
+    }
+    ensure_lagrange(c, mode);
+    std::lock_guard<std::mutex> lk(c->mu);
+    LWK_HIP(hipSetDevice(c->device));
+    hipStream_t st = caller ? caller : c->stream;
+    std::vector<uint8_t> h_comms;
+    std::vector<uint64_t> h_idx;
+    if (device_inputs) {
+        h_comms.resize(48 * n);
+        h_idx.resize(n);
+        LWK_HIP(hipMemcpyAsync(h_comms.data(), comms, 48 * n, hipMemcpyDeviceToHost, st));
+        LWK_HIP(hipMemcpyAsync(h_idx.data(), idx, 8 * n, hipMemcpyDeviceToHost, st));
+        LWK_HIP(hipStreamSynchronize(st));
+        if (!group_items(g, h_comms.data(), h_idx.data(), n)) {
+            set_error("verify_cell_kzg_proof_batch: a cell index is not below %d", kCellsPerBlob);
+            return C_KZG_BADARGS;
+        }
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    Bufs b;
+    C_KZG_RET rc = reserve(c, n, b);
+    if (rc != C_KZG_OK) return rc;
+    if ((rc = ctx_reserve(c, 1)) != C_KZG_OK) return rc;
+    WsUse wsu(c, st);
+    struct Drain {   // nothing of this call is in flight when it returns, whatever the exit
+        hipStream_t st;
+        ~Drain() { (void)hipStreamSynchronize(st); }
+    } drain{st};
+    PhaseClock clk;
+    clk.begin(st);
+    uint8_t *pin = c->cellv_pin;
+    uint8_t *pin_dig = pin, *pin_tail = pin + 36 * c->cellv_cap;
+    int32_t *pin_status = (int32_t *)(pin + 32 * c->cellv_cap);
+
+    // the distinct commitments, padded with infinity encodings to the proofs' count: both point sets go through the two-set launches
+    std::vector<uint8_t> padded(48 * n, 0);
+    memcpy(padded.data(), g.distinct.data(), 48 * g.m);
+    for (size_t j = g.m; j < n; j++) padded[48 * j] = 0xc0;
+    LWK_HIP(hipMemcpyAsync(b.comm_in, padded.data(), 48 * n, hipMemcpyHostToDevice, st));
+    LWK_HIP(hipMemcpyAsync(b.rows, g.rows.data(), 4 * n, hipMemcpyHostToDevice, st));
+    LWK_HIP(hipMemcpyAsync(b.perm_row, g.perm_row.data(), 4 * n, hipMemcpyHostToDevice, st));
+    LWK_HIP(hipMemcpyAsync(b.row_off, g.row_off.data(), 4 * (g.m + 1), hipMemcpyHostToDevice, st));
+    LWK_HIP(hipMemcpyAsync(b.perm_col, g.perm_col.data(), 4 * n, hipMemcpyHostToDevice, st));
+    LWK_HIP(hipMemcpyAsync(b.col_off, g.col_off.data(), 4 * (kCellsPerBlob + 1), hipMemcpyHostToDevice, st));
+    const uint8_t *d_cells = cells, *d_proofs = proofs;
+    const uint64_t *d_idx = idx;
+    if (!device_inputs) {
+        LWK_HIP(hipMemcpyAsync(b.cells, cells, n * kCellBytes, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(b.proofs, proofs, 48 * n, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(b.idx, idx, 8 * n, hipMemcpyHostToDevice, st));
+        d_cells = b.cells, d_proofs = b.proofs, d_idx = b.idx;
+    }
+    LWK_HIP(hipMemsetAsync(b.status, 0, 4 * n, st));
+    LWK_HIP(hipMemsetAsync(b.sc_c, 0, 32 * n, st));
+    clk.mark(0);
+    const int bad = (int)bad_input(mode);
+    launch_cellv_digests(d_cells, d_proofs, b.rows, d_idx, b.digests, b.status, bad, le, n, st);
+    clk.mark(1);
+    launch_decompress_points2(d_proofs, b.pts_p, b.kind_p, b.comm_in, b.pts_c, b.kind_c, n, st);
+    launch_subgroup_canon2(b.pts_p, b.kind_p, b.canon_p, b.verdict_p, b.pts_c, b.kind_c, b.canon_c, b.verdict_c, b.status, bad, n, st);
+    clk.mark(2);
+    LWK_HIP(hipMemcpyAsync(pin_dig, b.digests, 32 * n, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(pin_status, b.status, 4 * n, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipEventRecord(c->cellv_ev, st));
+    launch_vmsm_multiples2(b.pts_p, b.kind_p, b.tab_p, b.pts_c, b.kind_c, b.tab_c, b.vm_tmp, b.vm_pre, n, st);   // beside the host's hash
+    LWK_HIP(hipEventSynchronize(c->cellv_ev));
+    const auto t2 = std::chrono::steady_clock::now();
+    for (size_t i = 0; i < n; i++)
+        if (pin_status[i] != 0) {
+            set_error("verify_cell_kzg_proof_batch: a commitment or a proof is not a point of G1, or a cell element is not below r (first at %zu)", i);
+            return bad_input(mode);
+        }
+    cell_batch_challenge(r_raw, g.distinct.data(), g.m, pin_dig, n, le);
+    cell_batch_powers((Fr *)pin_tail, r_raw);
+    const auto t3 = std::chrono::steady_clock::now();
+    LWK_HIP(hipMemcpyAsync(b.pw, pin_tail, 33 * sizeof(Fr), hipMemcpyHostToDevice, st));
+    clk.mark(3);
+    launch_cellv_scalars(b.pw, d_idx, c->tw_fwd, b.a_mont, b.sc_a, b.sc_b, b.perm_row, b.row_off, b.sc_c, n, g.m, st);
+    launch_cellv_interpolant(d_cells, b.a_mont, b.perm_col, b.col_off, c->tw_inv, b.colcoef, c->ws.scalars2, le, st);
+    clk.mark(4);
+    const bool lg = coefficients_to_msm_form(c, mode, 1, st);
+    msm_stages(c, c->ws.scalars2, b.rli48, 1, st, 0, false, lg);
+    clk.mark(5);
+    launch_vmsm_accumulate(b.sc_a, b.sc_b, b.tab_p, b.kind_p, b.tab_c, b.kind_c, b.partial, n, st, b.sc_c);
+    launch_vmsm_reduce(b.partial, b.bsum, b.out96, b.inf, n, st);
+    clk.mark(6);
+    uint8_t *res = pin_tail + 33 * sizeof(Fr);
+    LWK_HIP(hipMemcpyAsync(res, b.out96, 3 * 96, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(res + 3 * 96, b.inf, 3 * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(res + 3 * 96 + 12, b.rli48, 48, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipGetLastError());
+    LWK_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < 3; k++) {
+        memcpy(sums[k], res + 96 * k, 96);
+        int32_t f;
+        memcpy(&f, res + 3 * 96 + 4 * k, 4);
+        infs[k] = f;
+    }
+    memcpy(rli48, res + 3 * 96 + 12, 48);
+    if (clk.on)
+        fprintf(stderr, "[lambdaworks_kzg_amd] verify cells n=%zu m=%zu: host grouping %.3f ms | device: digests %.3f, validation %.3f, "
+                        "rows beside the hash + wait %.3f, scalars + column sums %.3f, 64-term MSM %.3f, linear combinations %.3f ms | "
+                        "host: until digests landed %.3f, final hash + powers %.3f, total before the pairing %.3f ms\n",
+                n, g.m, wall_ms(t0, t1), clk.ms(0, 1), clk.ms(1, 2), clk.ms(2, 3), clk.ms(3, 4), clk.ms(4, 5), clk.ms(5, 6), wall_ms(t1, t2),
+                wall_ms(t2, t3), wall_ms(t0, std::chrono::steady_clock::now()));
+    return C_KZG_OK;
+}
+
+// the verdict (ok) and / or r and the four sums (partials): one code path up to the pairing
+C_KZG_RET cell_batch_impl(bool *ok, uint8_t *partials, const void *comms, const void *idx, const void *cells, const void *proofs, size_t n,
+                          const KZGSettings *s, bool device_inputs, hipStream_t caller) {
+    if (!s) return C_KZG_BADARGS;
+    const int mode = mode_of(s);
+    if (n == 0) {
+        if (ok) *ok = true;   // the consensus specs' and c-kzg-4844 2.x's rule for cells, in both modes
+        return C_KZG_OK;
+    }
+    if (!comms || !idx || !cells || !proofs) {
+        set_error("verify_cell_kzg_proof_batch: NULL argument");
+        return C_KZG_BADARGS;
+    }
+    uint32_t r_raw[8];
+    uint8_t sums[3][96], rli48[48];
+    int infs[3];
+    C_KZG_RET rc = cell_batch_sums(r_raw, sums, infs, rli48, (const uint8_t *)comms, (const uint64_t *)idx, (const uint8_t *)cells,
+                                   (const uint8_t *)proofs, n, s, mode, device_inputs, caller);
+    if (rc != C_KZG_OK) return rc;
+    if (partials) {
+        if (mode == LWKZG_MODE_CKZG) raw_to_le<8>(partials, r_raw);
+        else raw_to_be<8>(partials, r_raw);
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = cell_batch_finish(ok, partials ? partials + 32 : nullptr, sums, infs, rli48, s);
+    if (knobs().timing && ok)
+        fprintf(stderr, "[lambdaworks_kzg_amd] verify cells n=%zu: pairing side %.3f ms\n", n, wall_ms(t0, std::chrono::steady_clock::now()));
+    return rc;
+}
+
+// nothing may unwind across the C ABI
+template <class F>
+C_KZG_RET cellv_guarded(const char *what, F &&f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        set_error("%s: out of host memory", what);
+        return C_KZG_MALLOC;
+    } catch (...) {
+        set_error("%s: unexpected exception", what);
+        return C_KZG_ERROR;
+    }
+}
+
+}  // namespace
+
+}  // namespace lwk
+
+using namespace lwk;
+
+extern "C" {
+
+C_KZG_RET lwkzg_verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
+                                            const Bytes48 *proofs, size_t n, const KZGSettings *s) {
+    if (!ok) return C_KZG_BADARGS;
+    *ok = false;
+    return cellv_guarded("lwkzg_verify_cell_kzg_proof_batch",
+                         [&] { return cell_batch_impl(ok, nullptr, commitments, cell_indices, cells, proofs, n, s, false, nullptr); });
+}
+
+C_KZG_RET lwkzg_verify_cell_kzg_proof_batch_device(bool *ok, const void *commitments48_dev, const void *cell_indices_dev, const void *cells_dev,
+                                                   const void *proofs48_dev, size_t n, const KZGSettings *s, void *stream) {
+    if (!ok) return C_KZG_BADARGS;
+    *ok = false;
+    return cellv_guarded("lwkzg_verify_cell_kzg_proof_batch_device", [&] {
+        return cell_batch_impl(ok, nullptr, commitments48_dev, cell_indices_dev, cells_dev, proofs48_dev, n, s, true, (hipStream_t)stream);
+    });
+}
+
+C_KZG_RET lwkzg_cell_verify_partials(uint8_t *out, const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
+                                     const Bytes48 *proofs, size_t n, const KZGSettings *s) {
+    if (!out && n) return C_KZG_BADARGS;
+    return cellv_guarded("lwkzg_cell_verify_partials",
+                         [&] { return cell_batch_impl(nullptr, out, commitments, cell_indices, cells, proofs, n, s, false, nullptr); });
+}
+
+C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
+                                          const Bytes48 *proofs, size_t n, int mode) {
+    if (!r_out || (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG)) return C_KZG_BADARGS;
+    if (n && (!commitments || !cell_indices || !cells || !proofs)) return C_KZG_BADARGS;
+    return cellv_guarded("lwkzg_cell_batch_challenge_host", [&]() -> C_KZG_RET {
+        Grouping g;
+        if (!group_items(g, (const uint8_t *)commitments, cell_indices, n)) return C_KZG_BADARGS;
+        std::vector<uint8_t> digests(32 * n), msg(kItemMsg);
+        for (size_t i = 0; i < n; i++) {
+            for (int k = 0; k < 8; k++) {
+                msg[k] = (uint8_t)((uint64_t)g.rows[i] >> (8 * k));
+                msg[8 + k] = (uint8_t)(cell_indices[i] >> (8 * k));
+            }
+            memcpy(&msg[16], cells[i].bytes, kCellBytes);
+            memcpy(&msg[16 + kCellBytes], proofs[i].bytes, 48);
+            sha256_fast(&digests[32 * i], msg.data(), msg.size());
+        }
+        uint32_t r_raw[8];
+        cell_batch_challenge(r_raw, g.distinct.data(), g.m, digests.data(), n, mode == LWKZG_MODE_CKZG);
+        if (mode == LWKZG_MODE_CKZG) raw_to_le<8>(r_out, r_raw);
+        else raw_to_be<8>(r_out, r_raw);
+        return C_KZG_OK;
+    });
+}
+
+}  // extern "C"

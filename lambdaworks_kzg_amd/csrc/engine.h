@@ -304,6 +304,10 @@ struct Ctx {
     void *each_lines = nullptr;    // verify_each.hip: the line tables of g2_values[0] and [1] on the device (2 x 68 PairingLine), made on first use; under mu
     uint8_t *each_buf = nullptr;   // verify_each.hip: per-item points and verdicts (grow-only, under mu)
     size_t each_cap = 0;           // items each_buf holds
+    uint8_t *cellv_buf = nullptr;  // cells_verify_api.hip: everything a cell proof batch keeps on the device, one allocation carved up (grow-only, under mu)
+    uint8_t *cellv_pin = nullptr;  // hipHostMalloc: its digests and status words on their way down, the powers of r up, the sums down
+    size_t cellv_cap = 0;          // items both hold
+    hipEvent_t cellv_ev = nullptr; // the digests and status words have landed
     VerifyBuffers vs;   // verify-side scratch, sized for vs_cap blobs
     size_t vs_cap;
     std::mutex verify_mu;
@@ -388,6 +392,13 @@ C_KZG_RET vmsm_finish(Ctx *c, VerifyBuffers &vb, uint8_t sums[3][96], int infs[3
 // (canon48 zeroed); for the few-points paths where a 2 ms validation kernel is the wrong tool
 int host_validate_commitment(const uint8_t in48[48], uint8_t canon48[48], G1Affine29 *aff = nullptr);
 void host_validate_commitments(const uint8_t *in48, uint8_t *canon48, int *rc, size_t n, G1Affine29 *aff = nullptr);  // on the host threads
+
+// the host's end of a cell proof batch (verify.hip): the challenge from the distinct commitments and the per-cell
+// digests (canonical limbs), the table of its powers the device takes, and the pairing over the four sums
+void cell_batch_challenge(uint32_t r_raw[8], const uint8_t *distinct48, size_t m, const uint8_t *digests32, size_t n, bool le);
+void cell_batch_powers(Fr pw33[33], const uint32_t r_raw[8]);
+C_KZG_RET cell_batch_finish(bool *ok, uint8_t *out4x97, const uint8_t sums[3][96], const int infs[3], const uint8_t rli48[48],
+                            const KZGSettings *s);
 
 // G2 / pairing side (g2_pairing.hip, host only)
 bool g2_fill_values(g2_t *out65, const uint8_t *g2_bytes, size_t n2);

@@ -491,6 +491,9 @@ static void ctx_destroy(Ctx *c) {
     dev_free(c->vblobs);
     dev_free(c->each_lines);
     dev_free(c->each_buf);
+    dev_free(c->cellv_buf);
+    if (c->cellv_pin) hipHostFree(c->cellv_pin);
+    if (c->cellv_ev) hipEventDestroy(c->cellv_ev);
     if (c->prio_copy) hipStreamDestroy(c->prio_copy);
     if (c->one_pin) hipHostFree(c->one_pin);
     for (int k = 0; k < 2; k++) {

@@ -186,8 +186,10 @@ uint32_t vmsm_terms_per_slice(size_t n);
 size_t vmsm_slices(size_t n);
 size_t vmsm_max_slices(size_t cap);
 // partial: 3 x vmsm_slices(n) x 256 XYZZ; list_cap <= kVmsmListCap (smaller only to force the overflow path in tests)
+// sc_c: the scalars of the third sum (over tab_c) when they are not sc_a (the cell batch's weights of its distinct commitments)
 void launch_vmsm_accumulate(const uint32_t *sc_a, const uint32_t *sc_b, const G1Affine29 *tab_p, const int32_t *kind_p,
-                            const G1Affine29 *tab_c, const int32_t *kind_c, G1Xyzz29 *partial, size_t n, hipStream_t st);
+                            const G1Affine29 *tab_c, const int32_t *kind_c, G1Xyzz29 *partial, size_t n, hipStream_t st,
+                            const uint32_t *sc_c = nullptr);
 // bsum: 3 x 256 XYZZ; out96 / inf: the three sums, affine big-endian x | y and an infinity flag each (what launch_xyzz29_to_affine_be leaves)
 void launch_vmsm_reduce(const G1Xyzz29 *partial, G1Xyzz29 *bsum, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st);
 // records[160 i] = C_i | z_i | y_i | pi_i from the device-resident pieces; *first_bad = lowest index with a status word set (pre-set to 0xffffffff)
@@ -220,5 +222,20 @@ void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr2
 // canonical coefficients of n_cells / 128 blobs -> the monomial quotient q_k = p div (X^64 - c_k) of every cell, canonical limbs in
 // scalar set (blob * 128 + k), zero-padded to 4096
 void launch_cells_quotients(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, size_t n_cells, hipStream_t st);
+
+
+// ---- EIP-7594 cell proof batch verification (cells_verify.hip)
+// digests32[32 i] = SHA-256(le64(rows[i]) | le64(idx[i]) | cell i | proof i); status[i] = bad_code where an element of cell i is not below r.
+// cells and proofs48 are read in 16-byte pieces (16-byte aligned)
+void launch_cellv_digests(const uint8_t *cells, const uint8_t *proofs48, const uint32_t *rows, const uint64_t *idx, uint8_t *digests32,
+                          int32_t *status, int bad_code, int le, size_t n, hipStream_t st);
+// pw: as launch_vmsm_scalars takes it. a_mont[i] = r^i (Montgomery); sc_a / sc_b: the split forms of r^i and r^i c_{idx[i]};
+// sc_c[j], j < m: the split form of the sum of r^i over the items perm_row[row_off[j] .. row_off[j + 1])
+void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b,
+                          const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t n, size_t m, hipStream_t st);
+// slot_raw: 4096 canonical scalars, the first 64 the coefficients of sum_i r^i I_i(X), the rest zero. perm_col / col_off (129 words): the
+// items by column; colcoef: 128 x 64 Fr of scratch
+void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off, const Fr *tw_inv,
+                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st);
 
 }  // namespace lwk

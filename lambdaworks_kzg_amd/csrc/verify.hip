@@ -249,8 +249,8 @@ bool fr_from_bytes(uint32_t raw[8], const uint8_t b[32], int mode) {
     return true;
 }
 
-// e(lhs, G2) * e(-rhs_point, [tau]G2) == 1 with the G2 points of the settings
-C_KZG_RET pairing_verdict(bool *ok, const HXyzz &lhs, const HXyzz &pi, const KZGSettings *s) {
+// e(lhs, G2) * e(-rhs_point, [tau^power]G2) == 1 with the G2 points of the settings (power 1: the openings; 64: the cell proofs)
+C_KZG_RET pairing_verdict(bool *ok, const HXyzz &lhs, const HXyzz &pi, const KZGSettings *s, int power = 1) {
     if (!s->g2_values) {
         set_error("KZGSettings.g2_values is NULL");
         return C_KZG_ERROR;
@@ -267,8 +267,8 @@ C_KZG_RET pairing_verdict(bool *ok, const HXyzz &lhs, const HXyzz &pi, const KZG
     }
     if (!pi.is_inf()) {
         ps[m] = h_to_affine(xyzz_neg(pi));
-        qx[m] = {fp_from_blst(g2[1].x.fp[0]), fp_from_blst(g2[1].x.fp[1])};
-        qy[m] = {fp_from_blst(g2[1].y.fp[0]), fp_from_blst(g2[1].y.fp[1])};
+        qx[m] = {fp_from_blst(g2[power].x.fp[0]), fp_from_blst(g2[power].x.fp[1])};
+        qy[m] = {fp_from_blst(g2[power].y.fp[0]), fp_from_blst(g2[power].y.fp[1])};
         m++;
     }
     *ok = pairing_product_is_one(ps, qx, qy, m);
@@ -697,6 +697,69 @@ bool point_from_bytes(HXyzz &p, const uint8_t *in97) {
 }
 
 }  // namespace
+
+// ---- the host's end of the cell proof batch (cells_verify_api.hip) ------------------------------------------------
+// r = SHA-256("RCKZGCBATCH__V1_" | le64(4096) | le64(64) | le64(m) | le64(n) | the m distinct commitments | the n digests), read in the
+// mode's byte order and reduced: canonical limbs
+void cell_batch_challenge(uint32_t r_raw[8], const uint8_t *distinct48, size_t m, const uint8_t *digests32, size_t n, bool le) {
+    std::vector<uint8_t> msg(48 + 48 * m + 32 * n);
+    memcpy(msg.data(), "RCKZGCBATCH__V1_", 16);
+    const uint64_t head[4] = {4096, 64, (uint64_t)m, (uint64_t)n};
+    for (int q = 0; q < 4; q++)
+        for (int k = 0; k < 8; k++) msg[16 + 8 * q + k] = (uint8_t)(head[q] >> (8 * k));
+    if (m) memcpy(msg.data() + 48, distinct48, 48 * m);
+    if (n) memcpy(msg.data() + 48 + 48 * m, digests32, 32 * n);
+    uint8_t dg[32];
+    sha256_fast(dg, msg.data(), msg.size());
+    uint32_t t[8];
+    if (le) raw_from_le<8>(t, dg); else raw_from_be<8>(t, dg);
+    fe_to_raw<FrParams>(r_raw, fe_from_raw<FrParams>(t));
+}
+
+// pw33 as launch_vmsm_scalars takes it for a batch that starts at r^0: r^(2^k), k < 32, then 1, Montgomery form
+void cell_batch_powers(Fr pw33[33], const uint32_t r_raw[8]) {
+    HFr sq = hfr_raw(r_raw) * hfr_raw(FrParams::R2);
+    for (int k = 0; k < 32; k++) {
+        pw33[k] = sq.to_fe();
+        sq = sq * sq;
+    }
+    pw33[32] = HFr::one().to_fe();
+}
+
+// The four sums of the check -- P, RLP, RLC as launch_vmsm_reduce leaves them (affine big-endian x | y and an infinity flag each),
+// RLI compressed as the MSM leaves it -- written as P | RLC | RLI | RLP (flag 1 | x 48 | y 48 each) when out4x97 is given, and the
+// verdict e(RLC - RLI + RLP, G2) e(-P, [tau^64]G2) == 1 when ok is.
+C_KZG_RET cell_batch_finish(bool *ok, uint8_t *out4x97, const uint8_t sums[3][96], const int infs[3], const uint8_t rli48[48],
+                            const KZGSettings *s) {
+    HXyzz pt[3];
+    for (int k = 0; k < 3; k++) {
+        pt[k] = HXyzz::infinity();
+        if (infs[k]) continue;
+        uint32_t raw[12];
+        G1Affine a;
+        raw_from_be<12>(raw, sums[k]);
+        a.x = fe_from_raw<FpParams>(raw);
+        raw_from_be<12>(raw, sums[k] + 48);
+        a.y = fe_from_raw<FpParams>(raw);
+        pt[k] = HXyzz::from_affine(HFp::from_fe(a.x), HFp::from_fe(a.y));
+    }
+    HXyzz rli = HXyzz::infinity();
+    G1Affine ia;
+    const int rc = host_decompress_nocheck(ia, rli48);
+    if (rc == 2) {
+        set_error("cell batch: the interpolant's commitment is not a point");
+        return C_KZG_ERROR;
+    }
+    if (rc == 0) rli = HXyzz::from_affine(HFp::from_fe(ia.x), HFp::from_fe(ia.y));
+    if (out4x97) {
+        point_to_bytes(out4x97, pt[0]);
+        point_to_bytes(out4x97 + 97, pt[2]);
+        point_to_bytes(out4x97 + 2 * 97, rli);
+        point_to_bytes(out4x97 + 3 * 97, pt[1]);
+    }
+    if (!ok) return C_KZG_OK;
+    return pairing_verdict(ok, xyzz_add(xyzz_add(pt[2], xyzz_neg(rli)), pt[1]), pt[0], s, 64);
+}
 }  // namespace lwk
 
 extern "C" {

@@ -135,12 +135,13 @@ void launch_vmsm_scalars(const uint8_t *z_bytes, int le, const Fr *pw, uint32_t 
 }
 
 // ---- behind r: bucket accumulation -------------------------------------------------------------------------------------------------
-// grid (slices, 3): set 0 = sum a_i pi_i, set 1 = sum b_i pi_i, set 2 = sum a_i C_i. A workgroup sorts the (row, digit) entries of
+// grid (slices, 3): set 0 = sum a_i pi_i, set 1 = sum b_i pi_i, set 2 = sum c_i C_i (c = a for the blob batch; the cell batch passes
+// the weights of its distinct commitments, cells_verify.hip). A workgroup sorts the (row, digit) entries of
 // its slice of terms by digit (one LDS counter and one list per digit value) and lane b sums bucket b. A list that overflows (more
 // than kVmsmListCap rows of one digit in one slice: 2^-40 for hashed scalars, reachable by chosen ones) sends its lane through the
 // slice's entries in order instead. partial[(set * slices + slice) * 256 + b].
 __global__ __launch_bounds__(256) void k_vmsm_accumulate(const uint32_t *__restrict__ sc_a, const uint32_t *__restrict__ sc_b,
-                                                         const G1Affine29 *__restrict__ tab_p, const int32_t *__restrict__ kind_p,
+                                                         const uint32_t *__restrict__ sc_c, const G1Affine29 *__restrict__ tab_p, const int32_t *__restrict__ kind_p,
                                                          const G1Affine29 *__restrict__ tab_c, const int32_t *__restrict__ kind_c,
                                                          G1Xyzz29 *__restrict__ partial, uint32_t n, uint32_t terms, uint32_t list_cap) {
     __shared__ uint32_t dig_w[kVmsmMaxTerms * 8];
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(256) void k_vmsm_accumulate(const uint32_t *__restr
     const int set = blockIdx.y, tid = threadIdx.x;
     const uint32_t base = blockIdx.x * terms;
     const uint32_t m = n - base < terms ? n - base : terms;
-    const uint32_t *sc = set == 1 ? sc_b : sc_a;
+    const uint32_t *sc = set == 1 ? sc_b : set == 2 ? sc_c : sc_a;
     const G1Affine29i *tab = (const G1Affine29i *)(set == 2 ? tab_c : tab_p);
     const int32_t *kind = set == 2 ? kind_c : kind_p;
     count[tid] = 0;
@@ -207,12 +208,14 @@ size_t vmsm_max_slices(size_t cap) {
 }
 
 void launch_vmsm_accumulate(const uint32_t *sc_a, const uint32_t *sc_b, const G1Affine29 *tab_p, const int32_t *kind_p,
-                            const G1Affine29 *tab_c, const int32_t *kind_c, G1Xyzz29 *partial, size_t n, hipStream_t st) {
+                            const G1Affine29 *tab_c, const int32_t *kind_c, G1Xyzz29 *partial, size_t n, hipStream_t st,
+                            const uint32_t *sc_c) {
     ProfScope p("k_vmsm_accumulate", st);
     const uint32_t terms = vmsm_terms_per_slice(n);
     const int lc = knobs().vmsm_list_cap;
     const uint32_t list_cap = lc > 0 && lc < kVmsmListCap ? (uint32_t)lc : (uint32_t)kVmsmListCap;
-    hipLaunchKernelGGL(k_vmsm_accumulate, dim3((unsigned)vmsm_slices(n), 3), dim3(256), 0, st, sc_a, sc_b, tab_p, kind_p, tab_c, kind_c,
+    hipLaunchKernelGGL(k_vmsm_accumulate, dim3((unsigned)vmsm_slices(n), 3), dim3(256), 0, st, sc_a, sc_b, sc_c ? sc_c : sc_a, tab_p, kind_p, tab_c,
+                       kind_c,
                        partial, (uint32_t)n, terms, list_cap);
 }
 
