@@ -699,7 +699,7 @@ static bool launch_direct_t(const DirectPlanRt &plan, const uint64_t *table, siz
         prm.ctr_words = counters;
         uint32_t *ctr = redo + n_blobs;
         if (redo_flag_out) {
-            // a one-blob call (r06, engine.hip: combine_run): the hand-off counters have been cleared by the parse kernel in front of this
+            // a one-blob call (r06, host_api.hip: combine_run): the hand-off counters have been cleared by the parse kernel in front of this
             // launch, the redo flag is a word of pinned host memory the caller cleared and will look at after its one synchronisation -- no
             // fill launch, and no second-pass launch that would exit at its first instruction (the caller repeats a flagged call the long way)
             ProfScope p("k_coop_msm_asm", st);

@@ -151,7 +151,7 @@ int64_t host_last_active_ns();
 int64_t host_now_ns();
 void host_pool_warm();
 
-// Coalescing front of the single-blob symbols (engine.hip: combine_commit). The reference's KZGSettings is read-only
+// Coalescing front of the single-blob symbols (host_api.hip: combine_commit). The reference's KZGSettings is read-only
 // after load, so any number of threads may call blob_to_kzg_commitment on one settings object at once
 // (/root/reference/src/lib.rs:253-283, SURVEY 8b "Threading"); a GPU call per blob would serialise them at one launch
 // set each. Callers that arrive while a launch set is in flight are merged into the next one: each copies its blob into
@@ -180,7 +180,7 @@ struct Combiner {
     bool ready = false, failed = false;
 };
 
-// The same front for compute_blob_kzg_proof and compute_kzg_proof (engine.hip: front_run): one leader at a time runs
+// The same front for compute_blob_kzg_proof and compute_kzg_proof (host_api.hip: front_run): one leader at a time runs
 // everything queued in its mode as one host-pointer batch. `second` is the commitment (48 bytes) or z (32 bytes).
 struct ProofReq {
     enum State { QUEUED, TAKEN, DONE };
@@ -224,7 +224,7 @@ struct SmallProofHost {
 
 // The Lagrange form of the setup (c-kzg mode without the transform): L_i = [l_i(tau)]G in the blob's own
 // (bit-reversed domain) order, so that a c-kzg blob's evaluations are MSM scalars as they stand. Derived on the device from the
-// monomial points (engine.hip: lagrange_prepare), lazily: a settings object that never answers in c-kzg mode never pays for it.
+// monomial points (tables.hip: lagrange_prepare), lazily: a settings object that never answers in c-kzg mode never pays for it.
 struct LagrangeForm {
     bool ready = false;                  // points + 9 MB bucket table exist (written under the context's locks, both of them)
     G1Affine *points = nullptr;          // 4096 affine Montgomery points
@@ -363,7 +363,7 @@ C_KZG_RET point_proof_batch_device(Ctx *c, uint8_t *proof48, uint8_t *y32, const
                                    size_t n, int mode, hipStream_t st, int32_t *status, const G1Xyzz29 **sums_out = nullptr);
 C_KZG_RET msm_scalars_raw_device(Ctx *c, uint8_t *out48, const uint32_t *scalars_raw, size_t n, hipStream_t st);
 
-// verify-side helpers (host pointers in and out; GPU work inside; engine.hip)
+// verify-side helpers (host pointers in and out; GPU work inside; verify_front.hip)
 C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm48, const uint8_t *proofs48, size_t n,
                               int mode, uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p, VerifyBuffers &vb,
                               const uint8_t *trusted_canon_c = nullptr);

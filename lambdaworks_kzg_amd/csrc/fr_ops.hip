@@ -716,7 +716,7 @@ void launch_flag_differs48(const uint8_t *a, const uint8_t *b, uint32_t *flags, 
 //
 // L_i = [l_i(tau)]G, l_i the Lagrange polynomial of the domain point w_i = w^bitrev12(i), is the commitment of l_i's MONOMIAL
 // coefficients c_(i,k) = w_i^(-k) / 4096 -- a column of the inverse DFT matrix -- over the monomial setup, so the 4096 points are 4096
-// commitments of the existing engine (engine.hip: lagrange_prepare). This kernel writes those 4096 "blobs" of coefficients, in the
+// commitments of the existing engine (tables.hip: lagrange_prepare). This kernel writes those 4096 "blobs" of coefficients, in the
 // canonical raw form the MSM's digit extraction reads: row b of the output = l_(first + b). One workgroup per row, 16 consecutive
 // powers per thread (a 12-step square-and-multiply to the thread's first power, then 15 products).
 __global__ __launch_bounds__(256) void k_idft_columns(uint4 *__restrict__ coeffs_raw, const Fr *__restrict__ tw_inv, uint32_t first, Fr ninv) {

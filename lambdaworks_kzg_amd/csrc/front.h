@@ -4,7 +4,7 @@
 // compute_blob_kzg_proof / compute_kzg_proof on one settings object at once (/root/reference/src/lib.rs:253-283,
 // SURVEY 8b "Threading"); a GPU launch set per blob would serialise them. Callers that arrive while a launch set is in
 // flight are merged into the next one. This header holds the THREADING of that -- queues, leaders, lanes, staging slots --
-// as templates over what a leader does with its batch, so that the same code that engine.hip drives the GPU with runs on
+// as templates over what a leader does with its batch, so that the same code that host_api.hip drives the GPU with runs on
 // a CPU under -fsanitize=thread against a stub device (tests/front_tsan.cpp, tests/test_front_tsan_cpu.py).
 //
 // Both fronts give every caller the return code a call of its own would have had, survive a `run` that throws (nothing

@@ -512,7 +512,7 @@ C_KZG_RET shard_begin(Shard &sh, const uint8_t *blobs, const uint8_t *comms, con
     // per blob on the GPU: validate C_i and pi_i (decompress + subgroup check + canonical recompression; the
     // decompressed points stay on the device), z_i = challenge(blob_i, C_i), y_i = p_i(z_i)
     C_KZG_RET rc;
-    if (device_inputs) {   // the transcript is assembled on the device and arrives in one copy (engine.hip)
+    if (device_inputs) {   // the transcript is assembled on the device and arrives in one copy (verify_front.hip)
         rc = verify_prepare_device(sh.ctx, blobs, comms, proofs, n, mode, nullptr, nullptr, nullptr, nullptr, sh.vb, caller, sh.records.data());
     } else {
         std::vector<uint8_t> zs(32 * n), ys(32 * n), canon_c(48 * n), canon_p(48 * n);

@@ -1,5 +1,5 @@
 """CPU: the coalescing fronts of the single-blob symbols (lambdaworks_kzg_amd/csrc/front.h -- the queues, leaders, lanes and
-staging slots that engine.hip drives the GPU with) under -fsanitize=thread against a stub device: tests/front_tsan.cpp.
+staging slots that host_api.hip drives the GPU with) under -fsanitize=thread against a stub device: tests/front_tsan.cpp.
 Many threads on one front, both modes, inputs the "device" rejects, and `run` functions that throw (std::bad_alloc in the
 leader): every request gets the answer of a call of its own, the invariants hold, ThreadSanitizer reports nothing.
 Reference contract: concurrent callers on one KZGSettings, /root/reference/src/lib.rs:253-283 (SURVEY 8b "Threading")."""

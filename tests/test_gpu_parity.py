@@ -852,7 +852,7 @@ def test_verify_long_batch_pipelined_path(K, gpu_setup):
     with pytest.raises(K.KzgError) as e:
         K.verify_blob_kzg_proof_batch(data, bytes(badc), proofs, n, gpu_setup)
     assert e.value.rc == K.C_KZG_ERROR
-    # r06: such a batch lands in one device buffer, the head hashed by the GPU and the tail by the host threads (engine.hip:
+    # r06: such a batch lands in one device buffer, the head hashed by the GPU and the tail by the host threads (verify_front.hip:
     # verify_prepare_staged) -- the same three outcomes with the defect in the HEAD of the batch, and with an invalid proof encoding
     wrong = bytearray(proofs)
     wrong[48 * 7:48 * 8] = proofs[48 * 300:48 * 301]

@@ -32,7 +32,7 @@ def main():
         pj = b"".join(K.compute_blob_kzg_proof_batch(data, cj, ts))
         cut = max(1, (2 * n) // 3)
         if n == 2600:
-            # a first shard of 2100 blobs through host pointers is LONGER THAN ONE CHUNK: the staged form (engine.hip: verify_prepare_staged --
+            # a first shard of 2100 blobs through host pointers is LONGER THAN ONE CHUNK: the staged form (verify_front.hip: verify_prepare_staged --
             # the head of the batch hashed by the GPU as it lands, the tail by the host threads) against the sliced one (LWKZG_HOST_STAGE=0).
             # Two all-zero blobs, one in each part, come with their commitment at infinity in a NON-canonical encoding (stray bits behind the
             # flags, which the reference does not inspect): their challenges must be taken over the canonical bytes on either side
