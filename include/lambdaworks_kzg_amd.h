@@ -400,6 +400,31 @@ C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch(Cell *cells, KZGProof *proofs
 C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch_device(void *cells_dev, void *proofs48_dev, const void *blobs_dev, size_t n,
                                                           const KZGSettings *s, void *stream, int32_t *status_dev);
 
+/* EIP-7594 recover_cells_and_kzg_proofs: all 128 cells and all 128 proofs of a blob from num_cells of its cells, 64 <= num_cells <= 128.
+ * cells[i] is cell cell_indices[i], in the settings' mode's byte order; the indices are below 128 and strictly ascending (c-kzg-4844 2.x's
+ * rule and argument order). With p the polynomial of degree < 4096 that takes the given values on the given cells' cosets -- unique if it
+ * exists -- the outputs are byte for byte what lwkzg_compute_cells_and_kzg_proofs returns for the blob that stands for p in the
+ * settings' mode. Either output may be NULL (proofs NULL: no MSM runs). DESIGN.md section 4j.
+ * C_KZG_BADARGS in both modes, decided before any device work: s NULL; cell_indices or cells NULL; both outputs NULL; num_cells outside
+ * 64 .. 128; an index of 128 or more; indices not strictly ascending. A bad input -- a cell element that is not below r (never reduced, not
+ * in reference mode either), or cells that no polynomial of degree < 4096 goes through (possible from 65 cells on; with exactly 64 every
+ * canonical input is consistent, and with 128 the call is a consistency check plus the proofs) -- gives the mode's code for it
+ * (C_KZG_ERROR in reference mode, C_KZG_BADARGS in c-kzg mode) and nothing is written. Synchronous. */
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs(Cell *recovered_cells, KZGProof *recovered_proofs, const uint64_t *cell_indices,
+                                             const Cell *cells, size_t num_cells, const KZGSettings *s);
+/* n blobs that share ONE index set (the rows of a block seen through the same columns: what a reconstructing node holds).
+ * cells: n x num_cells x 2048 bytes, blob-major; outputs n x 128 each, either may be NULL (proofs NULL: no MSM runs). A bad blob fails
+ * the call with the mode's code (first_bad, if given, gets its index) and nothing is written. n == 0: C_KZG_OK, nothing written. */
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_batch(Cell *recovered_cells, KZGProof *recovered_proofs, const uint64_t *cell_indices,
+                                                   const Cell *cells, size_t num_cells, size_t n, const KZGSettings *s, size_t *first_bad);
+/* cells_dev / outputs are DEVICE pointers (16-byte aligned), cell_indices stays a HOST array (at most 128 words, read before the call
+ * returns); asynchronous on `stream` (NULL = the context's own); status_dev optional, one word per blob: 0 or the mode's code for a bad
+ * input; a good blob's outputs are correct whatever its neighbours' status. No allocation and no device synchronisation once
+ * lwkzg_reserve has covered the batch (8 blobs' worth of proofs = 1024, or 2 slots per blob without proofs). */
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_batch_device(void *recovered_cells_dev, void *recovered_proofs48_dev,
+                                                          const uint64_t *cell_indices, const void *cells_dev, size_t num_cells, size_t n,
+                                                          const KZGSettings *s, void *stream, int32_t *status_dev);
+
 /* EIP-7594 verify_cell_kzg_proof_batch: do the n items (commitments[i], cell_indices[i], cells[i], proofs[i]) belong together?
  * c-kzg-4844 2.x's argument order; the same commitment may appear many times and an item may repeat. cells are in the settings' mode's
  * byte order, as lwkzg_compute_cells_and_kzg_proofs writes them. DESIGN.md section 4i has the definition: commitments de-duplicated by

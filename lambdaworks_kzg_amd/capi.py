@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_compute_cells_and_kzg_proofs", "lwkzg_compute_cells_and_kzg_proofs_batch", "lwkzg_compute_cells_and_kzg_proofs_batch_device",
     "lwkzg_verify_cell_kzg_proof_batch", "lwkzg_verify_cell_kzg_proof_batch_device", "lwkzg_cell_verify_partials",
     "lwkzg_cell_batch_challenge_host",
+    "lwkzg_recover_cells_and_kzg_proofs", "lwkzg_recover_cells_and_kzg_proofs_batch", "lwkzg_recover_cells_and_kzg_proofs_batch_device",
 ]
 
 _lib = None
@@ -122,6 +123,9 @@ def lib():
     l.lwkzg_verify_cell_kzg_proof_batch_device.argtypes = [C.POINTER(C.c_bool), vp, vp, vp, vp, sz, ps, vp]
     l.lwkzg_cell_verify_partials.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ps]
     l.lwkzg_cell_batch_challenge_host.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ci]
+    l.lwkzg_recover_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, ps]
+    l.lwkzg_recover_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, sz, ps, C.POINTER(sz)]
+    l.lwkzg_recover_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, pu64, vp, sz, sz, ps, vp, vp]
     l.lwkzg_shard_range.argtypes = [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]
     pvp, psz = C.POINTER(vp), C.POINTER(sz)
     l.lwkzg_multi_blob_to_kzg_commitment_batch_device.argtypes = [pvp, pvp, psz, vp, psz]
@@ -611,6 +615,46 @@ def compute_cells_and_kzg_proofs_batch_device(cells_ptr, proofs_ptr, blobs_ptr, 
     pointer may be None"""
     _check("lwkzg_compute_cells_and_kzg_proofs_batch_device",
            lib().lwkzg_compute_cells_and_kzg_proofs_batch_device(cells_ptr, proofs_ptr, blobs_ptr, n, ts.ref(), stream, status_ptr))
+
+
+def _recover_args(cell_indices, cells, n):
+    """the indices as a C array and the cells (a list per blob or concatenated bytes, n x num_cells x 2048, blob-major) as bytes"""
+    num = len(cell_indices)
+    ce = cells if isinstance(cells, (bytes, bytearray)) else b"".join(cells)
+    if len(ce) != n * num * BYTES_PER_CELL:
+        raise ValueError("cells must hold one cell per index and blob")
+    return (C.c_uint64 * max(num, 1))(*cell_indices), bytes(ce), num
+
+
+def recover_cells_and_kzg_proofs(cell_indices, cells, ts, cells_out=True, proofs=True):
+    """EIP-7594 recover_cells_and_kzg_proofs (lwkzg_recover_cells_and_kzg_proofs): all 128 cells and 128 proofs of a blob from 64 .. 128
+    of its cells (cells[i] = cell cell_indices[i], indices strictly ascending), in the settings' mode; (cells, proofs) as
+    compute_cells_and_kzg_proofs returns them. cells_out=False / proofs=False leave that output out (None)."""
+    idx, ce, num = _recover_args(cell_indices, cells, 1)
+    cb = C.create_string_buffer(CELLS_PER_EXT_BLOB * BYTES_PER_CELL) if cells_out else None
+    pb = C.create_string_buffer(CELLS_PER_EXT_BLOB * 48) if proofs else None
+    _check("lwkzg_recover_cells_and_kzg_proofs", lib().lwkzg_recover_cells_and_kzg_proofs(cb, pb, idx, ce, num, ts.ref()))
+    return _cells_split(cb.raw if cells_out else None, pb.raw if proofs else None, 1)[0]
+
+
+def recover_cells_and_kzg_proofs_batch(cell_indices, cells, n, ts, cells_out=True, proofs=True):
+    """the same for n blobs that share one index set (cells: n x len(cell_indices) cells, blob-major): a list of (cells, proofs) per blob"""
+    idx, ce, num = _recover_args(cell_indices, cells, n)
+    cb = C.create_string_buffer(max(n, 1) * CELLS_PER_EXT_BLOB * BYTES_PER_CELL) if cells_out else None
+    pb = C.create_string_buffer(max(n, 1) * CELLS_PER_EXT_BLOB * 48) if proofs else None
+    bad = C.c_size_t(0)
+    _check("lwkzg_recover_cells_and_kzg_proofs_batch",
+           lib().lwkzg_recover_cells_and_kzg_proofs_batch(cb, pb, idx, ce, num, n, ts.ref(), C.byref(bad)))
+    return _cells_split(cb.raw if cells_out else None, pb.raw if proofs else None, n)
+
+
+def recover_cells_and_kzg_proofs_batch_device(cells_out_ptr, proofs_ptr, cell_indices, cells_ptr, n, ts, stream=None, status_ptr=None):
+    """cells (n x 128 x 2048 bytes) and proofs (n x 128 x 48 bytes) of n blobs from their device-resident cells (n x len(cell_indices) x
+    2048 bytes, blob-major; cell_indices a host list), asynchronous on `stream`; either output pointer may be None"""
+    num = len(cell_indices)
+    idx = (C.c_uint64 * max(num, 1))(*cell_indices)
+    _check("lwkzg_recover_cells_and_kzg_proofs_batch_device",
+           lib().lwkzg_recover_cells_and_kzg_proofs_batch_device(cells_out_ptr, proofs_ptr, idx, cells_ptr, num, n, ts.ref(), stream, status_ptr))
 
 
 CELL_VERIFY_PARTIAL_BYTES = 32 + 4 * 97

@@ -6,6 +6,7 @@
 //   extension   cells.hip: two forward transforms per blob through ws.fr and ws.scalars2, the cells written in the mode's byte order
 //   quotients   cells.hip: the 128 monomial quotients q_k of each blob straight into the scalar slots of ws.scalars2
 //   MSM         the engine's own launch set over 128 scalar sets per blob: 8 blobs fill its 1024 slots
+// Everything behind the parse is cells_from_coefficients, which the recovery (recover_api.hip) shares.
 // The cells-only call (no proofs) takes chunks of 512 blobs: the two transforms per blob are what bounds it.
 #include "engine.h"
 
@@ -26,13 +27,27 @@ static_assert(kProofChunk * kProofsPerBlob == kMaxChunk, "a chunk of blobs fills
 
 size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
 
+}  // namespace
+
+void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st) {
+    Workspace &w = c->ws;
+    const int le = mode == LWKZG_MODE_CKZG;
+    if (cells) launch_cells_extend(w.scalars, c->tw_fwd, c->tw28_fwd, w.fr, (Fr *)w.scalars2, cells, le, m, st);
+    if (proofs48) {
+        launch_cells_quotients(w.scalars, c->tw_fwd, w.scalars2, m * kProofsPerBlob, st);
+        const bool lg = coefficients_to_msm_form(c, mode, m * kProofsPerBlob, st);
+        msm_stages(c, w.scalars2, proofs48, m * kProofsPerBlob, st, 0, false, lg);
+    }
+}
+
+namespace {
+
 // the device pipeline on st (caller holds the context's lock and the workspace); status: n words, 0 or the mode's rejection code
 C_KZG_RET cells_device(Ctx *c, uint8_t *cells, uint8_t *proofs48, const uint8_t *blobs, size_t n, int mode, hipStream_t st, int32_t *status) {
     const size_t chunk = proofs48 ? kProofChunk : kCellsChunk;
     C_KZG_RET rc = ctx_reserve(c, (proofs48 ? kProofsPerBlob : 2) * min_sz(n, chunk));
     if (rc != C_KZG_OK) return rc;
     Workspace &w = c->ws;
-    const int le = mode == LWKZG_MODE_CKZG;
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = min_sz(chunk, n - off);
         int32_t *stt = status ? status + off : w.status;
@@ -40,12 +55,8 @@ C_KZG_RET cells_device(Ctx *c, uint8_t *cells, uint8_t *proofs48, const uint8_t 
         LWK_HIP(hipMemsetAsync(stt, 0, m * 4, st));
         if (mode == LWKZG_MODE_REFERENCE) launch_parse_be_reduce(b, w.scalars, m * kBlobElems, st);
         else launch_blob_evaluations_to_coefficients(b, w.scalars, c->tw28_inv, stt, m, st);
-        if (cells) launch_cells_extend(w.scalars, c->tw_fwd, c->tw28_fwd, w.fr, (Fr *)w.scalars2, cells + off * kBlobCellBytes, le, m, st);
-        if (proofs48) {
-            launch_cells_quotients(w.scalars, c->tw_fwd, w.scalars2, m * kProofsPerBlob, st);
-            const bool lg = coefficients_to_msm_form(c, mode, m * kProofsPerBlob, st);
-            msm_stages(c, w.scalars2, proofs48 + 48 * kProofsPerBlob * off, m * kProofsPerBlob, st, 0, false, lg);
-        }
+        cells_from_coefficients(c, cells ? cells + off * kBlobCellBytes : nullptr, proofs48 ? proofs48 + 48 * kProofsPerBlob * off : nullptr, m, mode,
+                                st);
     }
     LWK_HIP(hipGetLastError());
     return C_KZG_OK;

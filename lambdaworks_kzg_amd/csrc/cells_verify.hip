@@ -14,6 +14,7 @@
 // Items are grouped by row and by column on the host (a counting sort over the indices it holds anyway): perm_* lists the items
 // of group g at [off[g], off[g + 1]).
 #include "kernels.h"
+#include "cell_interp.cuh"
 #include "glv.cuh"
 #include "sha256_round.cuh"
 
@@ -27,28 +28,11 @@ __device__ __constant__ uint32_t kInv64Mont[8] = {0x00000000u, 0x00000000u, 0x00
 
 namespace {
 
-// the canonical integer of a 32-byte element from its two 16-byte halves as they lie in memory
-__device__ __forceinline__ void element_limbs(uint32_t t[8], const uint4 &first, const uint4 &second, int le) {
-    if (le) {
-        t[0] = first.x, t[1] = first.y, t[2] = first.z, t[3] = first.w;
-        t[4] = second.x, t[5] = second.y, t[6] = second.z, t[7] = second.w;
-    } else {
-        t[7] = __builtin_bswap32(first.x), t[6] = __builtin_bswap32(first.y), t[5] = __builtin_bswap32(first.z), t[4] = __builtin_bswap32(first.w);
-        t[3] = __builtin_bswap32(second.x), t[2] = __builtin_bswap32(second.y), t[1] = __builtin_bswap32(second.z), t[0] = __builtin_bswap32(second.w);
-    }
-}
-
 __device__ __forceinline__ void absorb(uint32_t w[16], int j, const uint4 &c) {
     w[4 * j] = __builtin_bswap32(c.x);
     w[4 * j + 1] = __builtin_bswap32(c.y);
     w[4 * j + 2] = __builtin_bswap32(c.z);
     w[4 * j + 3] = __builtin_bswap32(c.w);
-}
-
-// c_k = w128^bitrev7(k) = w4096^(32 bitrev7(k)), Montgomery form, from the forward twiddles w^e, e < 2048 (w^2048 = -1)
-__device__ __forceinline__ Fr c_of_cell(const Fr *tw_fwd, uint32_t k) {
-    const uint32_t e = 32 * (__brev(k & 127u) >> 25);
-    return e < kBlobElems / 2 ? tw_fwd[e] : neg(tw_fwd[e - kBlobElems / 2]);
 }
 
 __device__ __forceinline__ void store_split(uint32_t *sc, size_t i, const uint32_t raw[8]) {
@@ -222,26 +206,13 @@ __global__ __launch_bounds__(256) void k_cellv_columns(const uint4 *__restrict__
     __syncthreads();
 #pragma unroll 1
     for (int s = 0; s < 6; s++) {
-        if (threadIdx.x < 32) {
-            const uint32_t half = 1u << s, b = threadIdx.x, q = b & (half - 1);
-            const uint32_t i0 = ((b >> s) << (s + 1)) + q, i1 = i0 + half;
-            // w_(2 half)^-q = w64^-(q 32 / half) = w4096^-(64 q (32 >> s))
-            const Fr u = buf[i0], x = tw_inv[64 * q * (32u >> s)] * buf[i1];
-            buf[i0] = u + x;
-            buf[i1] = u - x;
-        }
+        if (threadIdx.x < 32) cell_idft64_stage(buf, tw_inv, s, threadIdx.x);
         __syncthreads();
     }
     if (v != 0) return;
-    // times h_k^-t / 64, h_k = w8192^bitrev7(k): the exponent e = bitrev7(k) t < 8192; w8192^-e = w4096^-(e >> 1) (w8192^-1 if e is odd)
-    const uint32_t e = (__brev(k) >> 25) * t, half_e = e >> 1;
-    Fr sc = half_e < kBlobElems / 2 ? tw_inv[half_e] : neg(tw_inv[half_e - kBlobElems / 2]);
+    // times h_k^-t / 64 (cell_interp.cuh)
+    const Fr sc = cell_coeff_twist(tw_inv, k, t, kInvOmega8192Mont);
     Fr c;
-    if (e & 1u) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) c.l[j] = kInvOmega8192Mont[j];
-        sc = sc * c;
-    }
 #pragma unroll
     for (int j = 0; j < 8; j++) c.l[j] = kInv64Mont[j];
     colcoef[kCellElems * k + t] = (sc * c) * buf[t];

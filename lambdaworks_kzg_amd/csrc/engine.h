@@ -308,6 +308,7 @@ struct Ctx {
     uint8_t *cellv_pin = nullptr;  // hipHostMalloc: its digests and status words on their way down, the powers of r up, the sums down
     size_t cellv_cap = 0;          // items both hold
     hipEvent_t cellv_ev = nullptr; // the digests and status words have landed
+    Fr *recover_tab = nullptr;     // recover_api.hip: the table k_recover_setup leaves for the call's other kernels (kRecoverTabElems, with the context)
     VerifyBuffers vs;   // verify-side scratch, sized for vs_cap blobs
     size_t vs_cap;
     std::mutex verify_mu;
@@ -352,6 +353,11 @@ void msm_stages(Ctx *c, const uint32_t *scalars_raw, uint8_t *out48, size_t n, h
 // n monomial-form scalar sets in ws.scalars2 (slots base ..) -> the form their MSM runs on (evaluations when the settings' only
 // direct table is over the Lagrange form; ws.scalars and ws.fr of the same slots serve as scratch); returns true for that form
 bool coefficients_to_msm_form(Ctx *c, int mode, size_t n, hipStream_t st, size_t base = 0);
+
+// the cells pipeline behind the parse (cells_api.hip): the canonical coefficients of m blobs in ws.scalars (slots 0 ..) -> their 128 cells
+// each (cells: m x 256 KiB, or nullptr) and 128 proofs each (proofs48: m x 128 x 48 bytes, or nullptr: no MSM runs). m is at most one
+// chunk (8 blobs with proofs, 512 without) and the caller has reserved the workspace for it (128 m slots with proofs, 2 m without)
+void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st);
 
 // device-resident pipelines; all pointers device, async on st
 C_KZG_RET commit_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, size_t n, int mode, hipStream_t st,

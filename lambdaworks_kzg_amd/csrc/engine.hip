@@ -486,6 +486,7 @@ void ctx_destroy(Ctx *c) {
     dev_free(c->each_lines);
     dev_free(c->each_buf);
     dev_free(c->cellv_buf);
+    dev_free(c->recover_tab);
     if (c->cellv_pin) hipHostFree(c->cellv_pin);
     if (c->cellv_ev) hipEventDestroy(c->cellv_ev);
     if (c->prio_copy) hipStreamDestroy(c->prio_copy);
@@ -562,6 +563,7 @@ C_KZG_RET ctx_new(Ctx **out, const Ctx *twin_of) {
         e = hipStreamCreateWithFlags(&c->aux[k], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join[k], hipEventDisableTiming);
     }
+    if (e == hipSuccess) e = hipMalloc((void **)&c->recover_tab, kRecoverTabElems * sizeof(Fr));
     if (twin_of) {  // same read-only tables, own streams / events / workspace / locks
         c->points = twin_of->points;
         c->table = twin_of->table;

@@ -223,6 +223,20 @@ void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr2
 // scalar set (blob * 128 + k), zero-padded to 4096
 void launch_cells_quotients(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, size_t n_cells, hipStream_t st);
 
+// ---- EIP-7594 recovery (recover.hip)
+// the index set of a recovery call, passed to its kernels by value: k[i] = the index of the i-th given cell (ascending), and bit q of
+// `given` = the cell at position q = bitrev7(k), whose c_k is w128^q, is among them
+struct RecoverSet {
+    uint8_t k[kCellsPerBlob];
+    uint32_t given[kCellsPerBlob / 32];
+};
+constexpr size_t kRecoverTabElems = 4 * kCellsPerBlob;   // the per-call table of k_recover_setup, Fr elements
+void launch_recover_setup(const RecoverSet &set, const Fr *tw_fwd, Fr *tab, hipStream_t st);
+// cells: n_blobs x num_cells x 2048 bytes, blob-major, 16-byte aligned, in the byte order `le` names -> the 4096 canonical coefficients
+// of every blob at coeffs_raw. scratch: n_blobs x 8192 Fr. status[blob] = bad_code where an element is not below r or no polynomial of
+// degree < 4096 goes through the blob's cells
+void launch_recover_coefficients(const uint8_t *cells, const RecoverSet &set, size_t num_cells, const Fr *tw_fwd, const Fr *tw_inv, const Fr *tab,
+                                 Fr *scratch, uint32_t *coeffs_raw, int32_t *status, int bad_code, int le, size_t n_blobs, hipStream_t st);
 
 // ---- EIP-7594 cell proof batch verification (cells_verify.hip)
 // digests32[32 i] = SHA-256(le64(rows[i]) | le64(idx[i]) | cell i | proof i); status[i] = bad_code where an element of cell i is not below r.

@@ -1,0 +1,170 @@
+// recover.hip -- the kernels of EIP-7594 recover_cells_and_kzg_proofs in front of the cells pipeline (the
+// pipeline is recover_api.hip): 64 .. 128 received cells of a blob -> its 4096 canonical coefficients in the workspace, where
+// cells_from_coefficients (cells_api.hip) takes over.
+//
+// The problem factors through X^64. With p(X) = sum_{t<64} X^t P_t(X^64), deg P_t < 64, the interpolant of cell k on its coset is
+// I_k = p mod (X^64 - c_k) and I_k[t] = P_t(c_k), c_k = w128^bitrev7(k): a blob is 64 independent erasure decodings of a polynomial of
+// degree < 64 over the 128th roots of unity, all with the same erasure pattern. Per call, per (blob, cell) and per (blob, t):
+//
+//  * k_recover_setup: Zs(Y) = prod over the missing cells of (Y - c_k) at the 128 roots and at the coset 7 w128^i (inverted there), and
+//    the powers of 7 the coset transforms scale by -- one 512-element table the context keeps.
+//  * k_recover_interp: one wave per given cell. The range check of its 64 elements rides on the read; the 64-point inverse transform
+//    over the coset (cell_interp.cuh, shared with the batch verification) gives I_k; I_k[t] Zs(c_k) goes to scratch [blob][t][bitrev7(k)].
+//  * k_recover_solve: one wave per (blob, t), 128 values in 4 KiB of LDS. The inverse transform of the 128 values (zero where the
+//    cell is missing) is N_t = Q_t Zs, Q_t the interpolant of degree < num_cells through the given points; N_t / Zs on the coset
+//    and back is Q_t. Its coefficients 64 .. 127 vanish exactly when a polynomial of degree < 4096 through the given cells exists;
+//    otherwise the blob's status word is set. Q_t[m] is coefficient 64 m + t of the blob.
+//
+// Cell values are canonical integers and stay so through every step (a Montgomery-form factor times a raw value is the raw product),
+// which is also the form the coefficients are wanted in.
+#include "kernels.h"
+#include "cell_interp.cuh"
+
+namespace lwk {
+
+#include "recover_consts.inc"
+
+namespace {
+
+__device__ __forceinline__ Fr const_fr(const uint32_t *limbs) {
+    Fr c;
+#pragma unroll
+    for (int j = 0; j < 8; j++) c.l[j] = limbs[j];
+    return c;
+}
+
+__device__ __forceinline__ uint32_t bitrev7(uint32_t q) { return __brev(q) >> 25; }
+
+__device__ __forceinline__ bool position_given(const RecoverSet &set, uint32_t q) { return (set.given[q >> 5] >> (q & 31u)) & 1u; }
+
+// a 128-point decimation-in-time transform of buf in place, butterfly b of 64 per stage: bit-reversed order in, natural order out.
+// tw: w4096^(+-e), e < 2048; w128^(+-j) is entry 32 j. Ends behind a barrier.
+__device__ __forceinline__ void dft128(Fr *buf, const Fr *__restrict__ tw, uint32_t b) {
+#pragma unroll 1
+    for (int s = 0; s < 7; s++) {
+        const uint32_t half = 1u << s, q = b & (half - 1);
+        const uint32_t i0 = ((b >> s) << (s + 1)) + q, i1 = i0 + half;
+        // w_(2 half)^q = w128^(q 64 / half)
+        const Fr u = buf[i0], x = tw[32 * q * (64u >> s)] * buf[i1];
+        buf[i0] = u + x;
+        buf[i1] = u - x;
+        __syncthreads();
+    }
+}
+
+// buf[j] <- scale[j] buf[j] for the lane's two elements j = b, b + 64, stored in bit-reversed order for the next transform
+__device__ __forceinline__ void scale_and_permute(Fr *buf, const Fr *__restrict__ scale, uint32_t b) {
+    const Fr v0 = scale[b] * buf[b], v1 = scale[b + 64] * buf[b + 64];
+    __syncthreads();
+    buf[bitrev7(b)] = v0;
+    buf[bitrev7(b + 64)] = v1;
+    __syncthreads();
+}
+
+}  // namespace
+
+// One workgroup of 128 lanes per call; lane q is position q, the root x_q = w128^q. tab (Montgomery form):
+//   [q]        Zs(x_q) / 64        (the 1/64 of the cells' inverse transform rides here)
+//   [128 + q]  1 / Zs(7 x_q)
+//   [256 + q]  7^q / 128           (into the coset, with the scale of the inverse transform in front)
+//   [384 + q]  7^-q / 128          (out of it, likewise)
+// Zs is never expanded into coefficients: at most 64 factors per value, every lane its own two products.
+__global__ __launch_bounds__(128) void k_recover_setup(RecoverSet set, const Fr *__restrict__ tw_fwd, Fr *__restrict__ tab) {
+    __shared__ Fr root[kCellsPerBlob];
+    const uint32_t q = threadIdx.x;
+    const Fr x = q < 64 ? tw_fwd[32 * q] : neg(tw_fwd[32 * (q - 64)]);   // w128^64 = -1
+    root[q] = x;
+    __syncthreads();
+    const Fr g = const_fr(kRecGenMont), gx = g * x;
+    Fr zr = Fr::one(), zc = Fr::one();
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)kCellsPerBlob; j++) {
+        if (position_given(set, j)) continue;   // (the same for every lane)
+        const Fr c = root[j];
+        zr = zr * (x - c);
+        zc = zc * (gx - c);
+    }
+    tab[q] = zr * const_fr(kRecInv64Mont);
+    tab[128 + q] = inv_divsteps(zc);   // 7 x_q is no 128th root of unity: never zero
+    Fr gp = Fr::one(), gip = Fr::one(), base = g, ibase = const_fr(kRecInvGenMont);
+#pragma unroll 1
+    for (int bit = 0; bit < 7; bit++) {
+        if ((q >> bit) & 1u) {
+            gp = gp * base;
+            gip = gip * ibase;
+        }
+        base = sqr(base);
+        ibase = sqr(ibase);
+    }
+    const Fr inv128 = const_fr(kRecInv128Mont);
+    tab[256 + q] = gp * inv128;
+    tab[384 + q] = gip * inv128;
+}
+
+// One wave (one workgroup) per (blob, given cell i): blockIdx.x = blob * num_cells + i is also the cell's place in `cells`. Lane t reads
+// element t, in the mode's byte order. An element that is not below r sets the blob's status word and counts as zero.
+__global__ __launch_bounds__(64) void k_recover_interp(const uint4 *__restrict__ cells, RecoverSet set, uint32_t num_cells,
+                                                       const Fr *__restrict__ tw_inv, const Fr *__restrict__ tab, Fr *__restrict__ scratch,
+                                                       int32_t *__restrict__ status, int bad_code, int le) {
+    __shared__ Fr buf[kCellElems];
+    const uint32_t t = threadIdx.x, blob = blockIdx.x / num_cells, i = blockIdx.x % num_cells;
+    const uint32_t k = set.k[i], q = bitrev7(k);
+    const uint4 *e = cells + ((size_t)blockIdx.x * kCellElems + t) * 2;
+    Fr x;
+    element_limbs(x.l, e[0], e[1], le);
+    const bool bad = raw_geq<8>(x.l, FrParams::MOD);
+    if (bad) x = Fr::zero();
+    if (__any(bad) && t == 0) status[blob] = bad_code;
+    buf[t] = x;
+    __syncthreads();
+#pragma unroll 1
+    for (int s = 0; s < 6; s++) {
+        if (t < 32) cell_idft64_stage(buf, tw_inv, s, t);
+        __syncthreads();
+    }
+    // I_k[t] Zs(c_k): times h_k^-t, and Zs(c_k) / 64 from the table
+    const Fr sc = cell_coeff_twist(tw_inv, k, t, kRecInvOmega8192Mont) * tab[q];
+    scratch[((size_t)blob * kCellElems + t) * kCellsPerBlob + q] = sc * buf[t];
+}
+
+// One wave (one workgroup) per (blob, t): blockIdx.x = 64 blob + t. Lane b holds elements b and b + 64 wherever a lane owns elements.
+__global__ __launch_bounds__(64) void k_recover_solve(const Fr *__restrict__ scratch, RecoverSet set, const Fr *__restrict__ tw_fwd,
+                                                      const Fr *__restrict__ tw_inv, const Fr *__restrict__ tab, uint4 *__restrict__ coeffs_raw,
+                                                      int32_t *__restrict__ status, int bad_code) {
+    __shared__ Fr buf[kCellsPerBlob];
+    const uint32_t b = threadIdx.x, t = blockIdx.x % kCellElems, blob = blockIdx.x / kCellElems;
+    const Fr *src = scratch + (size_t)blockIdx.x * kCellsPerBlob;
+    // the slots of the missing cells were never written: they count as zero (Zs vanishes there)
+    buf[bitrev7(b)] = position_given(set, b) ? src[b] : Fr::zero();
+    buf[bitrev7(b + 64)] = position_given(set, b + 64) ? src[b + 64] : Fr::zero();
+    __syncthreads();
+    dft128(buf, tw_inv, b);                      // 128 N_t, N_t = Q_t Zs
+    scale_and_permute(buf, tab + 256, b);        // N_t[j] 7^j
+    dft128(buf, tw_fwd, b);                      // N_t(7 w128^i)
+    scale_and_permute(buf, tab + 128, b);        // Q_t(7 w128^i)
+    dft128(buf, tw_inv, b);                      // 128 Q_t[j] 7^j
+    const Fr lo = tab[384 + b] * buf[b], hi = tab[384 + b + 64] * buf[b + 64];
+    if (__any(!hi.is_zero()) && b == 0) status[blob] = bad_code;
+    const size_t slot = (size_t)blob * kBlobElems + (size_t)kCellElems * b + t;
+    coeffs_raw[2 * slot] = make_uint4(lo.l[0], lo.l[1], lo.l[2], lo.l[3]);
+    coeffs_raw[2 * slot + 1] = make_uint4(lo.l[4], lo.l[5], lo.l[6], lo.l[7]);
+}
+
+void launch_recover_setup(const RecoverSet &set, const Fr *tw_fwd, Fr *tab, hipStream_t st) {
+    ProfScope p("k_recover_setup", st);
+    hipLaunchKernelGGL(k_recover_setup, dim3(1), dim3(kCellsPerBlob), 0, st, set, tw_fwd, tab);
+}
+
+void launch_recover_coefficients(const uint8_t *cells, const RecoverSet &set, size_t num_cells, const Fr *tw_fwd, const Fr *tw_inv, const Fr *tab,
+                                 Fr *scratch, uint32_t *coeffs_raw, int32_t *status, int bad_code, int le, size_t n_blobs, hipStream_t st) {
+    {
+        ProfScope p("k_recover_interp", st);
+        hipLaunchKernelGGL(k_recover_interp, dim3((unsigned)(n_blobs * num_cells)), dim3(kCellElems), 0, st, (const uint4 *)cells, set,
+                           (uint32_t)num_cells, tw_inv, tab, scratch, status, bad_code, le);
+    }
+    ProfScope p("k_recover_solve", st);
+    hipLaunchKernelGGL(k_recover_solve, dim3((unsigned)(n_blobs * kCellElems)), dim3(kCellElems), 0, st, (const Fr *)scratch, set, tw_fwd, tw_inv,
+                       tab, (uint4 *)coeffs_raw, status, bad_code);
+}
+
+}  // namespace lwk
