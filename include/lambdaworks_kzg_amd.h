@@ -9,7 +9,7 @@
  *
  * Everything after "extensions" is additive: batched and device-resident entry points (a
  * synchronous one-blob call cannot reach 10k ops/s), the R/C semantics switch, multi-GPU setup
- * hand-off, EIP-7594 cells, cell proofs and their batch verification, and profiling hooks used
+ * hand-off, EIP-7594 cells, cell proofs and their batch and per-item verification, and profiling hooks used
  * by bench.py.
  *
  * Struct layouts follow the reference's #[repr(C)] types (src/lib.rs:45-232). NOTE the
@@ -459,6 +459,35 @@ C_KZG_RET lwkzg_cell_verify_partials(uint8_t *out, const Bytes48 *commitments, c
  * n > 0, an index >= 128 or an unknown mode: C_KZG_BADARGS. */
 C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
                                           const Bytes48 *proofs, size_t n, int mode);
+
+/* Per-item cell verification: n independent lwkzg_verify_cell_kzg_proof_batch calls of ONE item each, in one. For every i, ok_out[i]
+ * (0/1) and rc_out[i] (a C_KZG_RET) are exactly the (*ok, return code) of the batch call on item i alone, in the mode the settings
+ * answer in; with one item the batch's r^0 = 1, so the check is e(C - [I(tau)]G1 + [c_k]pi, G2) e(-pi, g2_values[64]) == 1. A bad item
+ * is an answer, not a failure:
+ *     an index >= 128                                    rc C_KZG_BADARGS in both modes (decided first, whatever else is wrong), ok 0
+ *     a commitment or a proof that is not a compressed
+ *     point of G1 (infinity allowed), or a cell element
+ *     not below r (never reduced)                        rc the mode's code (C_KZG_ERROR reference, C_KZG_BADARGS c-kzg), ok 0
+ *     otherwise                                          rc C_KZG_OK, ok the verdict
+ * and a good item's answer never depends on its neighbours. The call returns C_KZG_OK once every item is decided; C_KZG_BADARGS for
+ * s NULL or any NULL pointer with n > 0; what the batch call refuses as a whole (no context, g2_values NULL) the same way;
+ * C_KZG_MALLOC / C_KZG_ERROR only when the device work itself fails. n == 0: C_KZG_OK, nothing written. Synchronous. Every step runs on
+ * the GPU, the pairing check of each item included. Verify a batch with lwkzg_verify_cell_kzg_proof_batch
+ * first; this call is for a batch that answered false, or where every item needs its own answer. */
+C_KZG_RET lwkzg_verify_cell_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const Bytes48 *commitments, const uint64_t *cell_indices,
+                                           const Cell *cells, const Bytes48 *proofs, size_t n, const KZGSettings *s);
+/* the same for inputs already in HBM (device pointers, 16-byte aligned, produced on `stream`, NULL = already complete); the cells stay
+ * on the device, the verdicts and codes come to the host */
+C_KZG_RET lwkzg_verify_cell_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_out, const void *commitments48_dev,
+                                                  const void *cell_indices_dev, const void *cells_dev, const void *proofs48_dev, size_t n,
+                                                  const KZGSettings *s, void *stream);
+/* test hook: the G1 point each item's pairing is taken of, by the verdict call's own code path up to the pairing. Per item
+ * flag 1 | x 48 | y 48 big-endian: flag 0 = the affine point P_i = C_i - [I_i(tau)]G1 + [c_(k_i)]pi_i, 1 = P_i is the point at infinity
+ * (rest zero), 2 = the item did not reach the combine (a bad item; rest zero). Host arguments and return codes as
+ * lwkzg_verify_cell_kzg_proof_each. */
+#define LWKZG_CELL_EACH_POINT_BYTES 97
+C_KZG_RET lwkzg_cell_verify_each_points(uint8_t *out /* n x 97 */, const Bytes48 *commitments, const uint64_t *cell_indices,
+                                        const Cell *cells, const Bytes48 *proofs, size_t n, const KZGSettings *s);
 
 /* Host-only test hook for the per-item pairing: the 68 lines of the Miller loop of a ZCash-compressed G2 point (not at infinity) as the
  * device takes them, canonical big-endian lambda.c0 | lambda.c1 | c0.c0 | c0.c1 per line (out: 68 x 192 bytes). No GPU, no settings. */

@@ -16,6 +16,7 @@ from .capi import (  # noqa: F401
     BYTES_PER_CELL, CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_CELL, FIELD_ELEMENTS_PER_EXT_BLOB,
     compute_cells_and_kzg_proofs, compute_cells_and_kzg_proofs_batch, compute_cells_and_kzg_proofs_batch_device,
     verify_cell_kzg_proof_batch, verify_cell_kzg_proof_batch_device, cell_verify_partials, cell_batch_challenge_host,
+    verify_cell_kzg_proof_each, verify_cell_kzg_proof_each_device, cell_verify_each_points,
     recover_cells_and_kzg_proofs, recover_cells_and_kzg_proofs_batch, recover_cells_and_kzg_proofs_batch_device,
 )
 

@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_compute_cells_and_kzg_proofs", "lwkzg_compute_cells_and_kzg_proofs_batch", "lwkzg_compute_cells_and_kzg_proofs_batch_device",
     "lwkzg_verify_cell_kzg_proof_batch", "lwkzg_verify_cell_kzg_proof_batch_device", "lwkzg_cell_verify_partials",
     "lwkzg_cell_batch_challenge_host",
+    "lwkzg_verify_cell_kzg_proof_each", "lwkzg_verify_cell_kzg_proof_each_device", "lwkzg_cell_verify_each_points",
     "lwkzg_recover_cells_and_kzg_proofs", "lwkzg_recover_cells_and_kzg_proofs_batch", "lwkzg_recover_cells_and_kzg_proofs_batch_device",
 ]
 
@@ -123,6 +124,9 @@ def lib():
     l.lwkzg_verify_cell_kzg_proof_batch_device.argtypes = [C.POINTER(C.c_bool), vp, vp, vp, vp, sz, ps, vp]
     l.lwkzg_cell_verify_partials.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ps]
     l.lwkzg_cell_batch_challenge_host.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ci]
+    l.lwkzg_verify_cell_kzg_proof_each.argtypes = [pu8, pi32, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_verify_cell_kzg_proof_each_device.argtypes = [pu8, pi32, vp, vp, vp, vp, sz, ps, vp]
+    l.lwkzg_cell_verify_each_points.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, sz, ps, C.POINTER(sz)]
     l.lwkzg_recover_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, pu64, vp, sz, sz, ps, vp, vp]
@@ -696,6 +700,34 @@ def cell_verify_partials(commitments, cell_indices, cells, proofs, ts):
     out = C.create_string_buffer(CELL_VERIFY_PARTIAL_BYTES)
     _check("lwkzg_cell_verify_partials", lib().lwkzg_cell_verify_partials(out, cm, idx, ce, pf, n, ts.ref()))
     return out.raw
+
+
+CELL_EACH_POINT_BYTES = 97
+
+
+def verify_cell_kzg_proof_each(commitments, cell_indices, cells, proofs, ts):
+    """n independent one-item verify_cell_kzg_proof_batch calls in one (lwkzg_verify_cell_kzg_proof_each): a list of (rc, ok), item i
+    exactly what the batch call on item i alone answers. Arguments as verify_cell_kzg_proof_batch."""
+    cm, idx, ce, pf, n = _cell_items(commitments, cell_indices, cells, proofs)
+    return _each("lwkzg_verify_cell_kzg_proof_each", n,
+                 lambda ok, rc: lib().lwkzg_verify_cell_kzg_proof_each(ok, rc, cm, idx, ce, pf, n, ts.ref()))
+
+
+def verify_cell_kzg_proof_each_device(comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, ts, stream=None):
+    """the same on DEVICE pointers (48 n commitment bytes, n uint64 indices, 2048 n cell bytes, 48 n proof bytes, produced on
+    `stream`); the verdicts come to the host, the call is synchronous"""
+    return _each("lwkzg_verify_cell_kzg_proof_each_device", n,
+                 lambda ok, rc: lib().lwkzg_verify_cell_kzg_proof_each_device(ok, rc, comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n,
+                                                                              ts.ref(), stream))
+
+
+def cell_verify_each_points(commitments, cell_indices, cells, proofs, ts):
+    """the G1 point each item's pairing is taken of (97 bytes each: flag | x | y; flag 1 = infinity, 2 = a bad item), by the per-item
+    verdict call's own code path: a list of n bytes objects"""
+    cm, idx, ce, pf, n = _cell_items(commitments, cell_indices, cells, proofs)
+    out = C.create_string_buffer(CELL_EACH_POINT_BYTES * max(n, 1))
+    _check("lwkzg_cell_verify_each_points", lib().lwkzg_cell_verify_each_points(out, cm, idx, ce, pf, n, ts.ref()))
+    return [out.raw[CELL_EACH_POINT_BYTES * i:CELL_EACH_POINT_BYTES * (i + 1)] for i in range(n)]
 
 
 def cell_batch_challenge_host(commitments, cell_indices, cells, proofs, mode):

@@ -308,6 +308,9 @@ struct Ctx {
     uint8_t *cellv_pin = nullptr;  // hipHostMalloc: its digests and status words on their way down, the powers of r up, the sums down
     size_t cellv_cap = 0;          // items both hold
     hipEvent_t cellv_ev = nullptr; // the digests and status words have landed
+    void *celleach_lines = nullptr;   // cells_verify_each.hip: the line tables of g2_values[0] and [64] on the device, made on first use; under mu
+    uint8_t *celleach_buf = nullptr;  // cells_verify_each.hip: everything a per-item cell verification keeps on the device, one allocation carved up (grow-only, under mu)
+    size_t celleach_cap = 0;          // items celleach_buf holds
     Fr *recover_tab = nullptr;     // recover_api.hip: the table k_recover_setup leaves for the call's other kernels (kRecoverTabElems, with the context)
     VerifyBuffers vs;   // verify-side scratch, sized for vs_cap blobs
     size_t vs_cap;

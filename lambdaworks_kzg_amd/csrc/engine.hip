@@ -486,6 +486,8 @@ void ctx_destroy(Ctx *c) {
     dev_free(c->each_lines);
     dev_free(c->each_buf);
     dev_free(c->cellv_buf);
+    dev_free(c->celleach_lines);
+    dev_free(c->celleach_buf);
     dev_free(c->recover_tab);
     if (c->cellv_pin) hipHostFree(c->cellv_pin);
     if (c->cellv_ev) hipEventDestroy(c->cellv_ev);

@@ -9,7 +9,7 @@
 //   pairing  k_each_pairing: e(P_i, G2) e(-pi_i, [tau]G2) == 1 on fp12.cuh's tower, against the line tables of g2_values[0] and [1]
 //            made once per context by the host's fixed_q_lines (pairing.hip)
 // One lane per item. The verdicts and status words come back in one copy each; the host maps a status to the single call's code.
-#include "engine.h"
+#include "each.h"
 #include "knobs.h"
 #include "fp12.cuh"
 #include "glv.cuh"
@@ -24,17 +24,6 @@ void pairing_line_table_host(const Fp2 &qx, const Fp2 &qy, Fp2 *out);  // pairin
 static_assert(sizeof(PairingLine) == 2 * sizeof(Fp2), "pairing_line_table_host writes lambda, c0 per line");
 
 namespace {
-
-constexpr int kEachBlock = 64;
-
-// flags of an item: its status was 0 / its P is not the point at infinity / its proof is not the point at infinity
-constexpr uint32_t kEachValid = 1, kEachHasP = 2, kEachHasPi = 4;
-
-// the two G1 points of an item's pairing check: P = C - [y]G + [z]pi and -pi, affine
-struct alignas(16) EachPoints {
-    Fp px, py, qx, qy;
-    uint32_t flags;
-};
 
 // 32 bytes of a scalar in the mode's byte order -> raw limbs; false if not below r
 __device__ __forceinline__ bool each_scalar(uint32_t raw[8], const uint8_t *b, int le) {
@@ -130,8 +119,6 @@ __global__ void k_each_pairing(const EachPoints *pts, const PairingLine *lines, 
                 : 0;
 }
 
-unsigned each_blocks(size_t n) { return (unsigned)((n + kEachBlock - 1) / kEachBlock); }
-
 // reference blst_fp (canonical, most-significant u64 first) -> Fp
 Fp fp_of_blst(const blst_fp &v) {
     uint32_t raw[12];
@@ -142,12 +129,14 @@ Fp fp_of_blst(const blst_fp &v) {
     return fe_from_raw<FpParams>(raw);
 }
 
-// the line tables of g2_values[0] and [1] on the device, made at the context's first per-item verification. Caller holds c->mu.
-C_KZG_RET each_lines(Ctx *c, const KZGSettings *s, const PairingLine **out) {
-    if (!c->each_lines) {
+}  // namespace
+
+// each.h: the line tables of g2_values[0] and [power] on the device, made at the context's first per-item verification of that kind
+C_KZG_RET each_line_tables(const KZGSettings *s, int power, void **slot, const PairingLine **out) {
+    if (!*slot) {
         std::vector<PairingLine> h(2 * kPairingLines);
         for (int q = 0; q < 2; q++) {
-            const g2_t &p = s->g2_values[q];
+            const g2_t &p = s->g2_values[q ? power : 0];
             const Fp2 qx = {fp_of_blst(p.x.fp[0]), fp_of_blst(p.x.fp[1])}, qy = {fp_of_blst(p.y.fp[0]), fp_of_blst(p.y.fp[1])};
             pairing_line_table_host(qx, qy, (Fp2 *)&h[q * kPairingLines]);
         }
@@ -158,11 +147,18 @@ C_KZG_RET each_lines(Ctx *c, const KZGSettings *s, const PairingLine **out) {
             set_error("per-item verification: line table upload failed");
             return C_KZG_ERROR;
         }
-        c->each_lines = d;
+        *slot = d;
     }
-    *out = (const PairingLine *)c->each_lines;
+    *out = (const PairingLine *)*slot;
     return C_KZG_OK;
 }
+
+void launch_each_pairing(const EachPoints *pts, const PairingLine *lines, uint8_t *ok, size_t n, hipStream_t st) {
+    ProfScope p("k_each_pairing", st);
+    k_each_pairing<<<each_blocks(n), kEachBlock, 0, st>>>(pts, lines, ok, n);
+}
+
+namespace {
 
 // per-item points and verdicts, grow-only. Caller holds c->mu.
 C_KZG_RET each_reserve(Ctx *c, size_t n) {
@@ -207,7 +203,7 @@ C_KZG_RET verify_each_device(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const K
     hipStream_t st = ctx->stream;
     const PairingLine *lines = nullptr;
     if (setup_ok) {
-        if ((rc = each_lines(ctx, s, &lines)) != C_KZG_OK) return rc;
+        if ((rc = each_line_tables(s, 1, &ctx->each_lines, &lines)) != C_KZG_OK) return rc;
         if ((rc = each_reserve(ctx, n)) != C_KZG_OK) return rc;
         EachPoints *pts = (EachPoints *)ctx->each_buf;
         uint8_t *d_ok = ctx->each_buf + ctx->each_cap * sizeof(EachPoints);
@@ -217,7 +213,7 @@ C_KZG_RET verify_each_device(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const K
         k_each_combine<<<each_blocks(n), kEachBlock, 0, st>>>(vb.pts_c, vb.kind_c, vb.pts_p, vb.kind_p, vb.status_all, vb.d_rz, vb.d_r,
                                                              mode == LWKZG_MODE_CKZG, g, beta, pts, n);
         LWK_HIP(hipGetLastError());
-        k_each_pairing<<<each_blocks(n), kEachBlock, 0, st>>>(pts, lines, d_ok, n);
+        launch_each_pairing(pts, lines, d_ok, n, st);
         LWK_HIP(hipGetLastError());
         LWK_HIP(hipMemcpyAsync(ok_out, d_ok, n, hipMemcpyDeviceToHost, st));
     }
