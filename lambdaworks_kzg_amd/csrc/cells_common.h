@@ -1,0 +1,34 @@
+// cells_common.h -- what the EIP-7594 compute paths share (cells_api.hip, recover_api.hip): the sizes, the chunk loop behind the step
+// that makes coefficients, and the driver of the host-pointer forms. The cell verifiers take kCellBytes and bad_input from here.
+#pragma once
+#include "engine.h"
+
+namespace lwk {
+
+constexpr size_t kCellBytes = (size_t)kCellElems * 32;
+constexpr size_t kBlobCellBytes = (size_t)kCellsPerBlob * kCellBytes;   // 256 KiB: the 128 cells of one blob
+constexpr size_t kProofsPerBlob = kCellsPerBlob;
+constexpr size_t kProofChunk = kMaxChunk / kProofsPerBlob;               // 8 blobs = one launch set of 1024 MSMs
+constexpr size_t kCellsChunk = kMaxChunk / 2;                            // two transforms (and 256 KiB of scratch) per blob in 1024 slots
+constexpr size_t kHostSlice = 64;                                        // blobs per upload / download of the host-pointer forms
+static_assert(kProofChunk * kProofsPerBlob == kMaxChunk, "a chunk of blobs fills a launch set");
+
+inline size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
+
+inline C_KZG_RET bad_input(int mode) { return mode == LWKZG_MODE_CKZG ? C_KZG_BADARGS : C_KZG_ERROR; }
+
+// The device pipeline of n blobs on st, a chunk at a time (8 blobs with proofs, 512 without); the caller holds the context's lock and the
+// workspace. coefficients(off, m, stt) enqueues the step that leaves the coefficients of blobs off .. off + m in ws.scalars and a
+// rejection code in stt[0 .. m) (cleared before). status: n words, 0 or the mode's rejection code; nullptr: ws.status takes them
+typedef std::function<void(size_t off, size_t m, int32_t *stt)> CoefficientStep;
+C_KZG_RET cells_chunks(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode, hipStream_t st, int32_t *status,
+                       const CoefficientStep &coefficients);
+
+// Host pointers: slices of up to kHostSlice blobs (in_bytes_per_blob each) go up, through run (the device pipeline of m blobs) and back;
+// the outputs are written only when every blob is good. no_memory takes the staging's byte count, rejected the first bad blob's index
+// and status word
+typedef std::function<C_KZG_RET(uint8_t *d_cells, uint8_t *d_proofs, const uint8_t *d_in, size_t m, hipStream_t st, int32_t *d_status)> SliceRun;
+C_KZG_RET cells_host_slices(Ctx *c, const uint8_t *in, size_t in_bytes_per_blob, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode,
+                            size_t *first_bad, const char *no_memory, const char *rejected, const SliceRun &run);
+
+}  // namespace lwk

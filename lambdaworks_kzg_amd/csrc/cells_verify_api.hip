@@ -11,7 +11,9 @@
 //   device   scalars, row weights, column sums + interpolation, the 64-term MSM on the engine's own launch set, the three
 //            variable-base sums (vmsm.hip); four points come down
 //   host     the pairing check against g2_values[64] (pairing.hip keeps its line table beside the others)
-#include "engine.h"
+#include "abi_guard.h"
+#include "carve.h"
+#include "cells_common.h"
 #include "knobs.h"
 
 #include <string.h>
@@ -27,11 +29,8 @@ void sha256_fast(uint8_t out[32], const uint8_t *msg, size_t len);  // sha256_ho
 
 namespace {
 
-constexpr size_t kCellBytes = (size_t)kCellElems * 32;
 constexpr size_t kItemMsg = 16 + kCellBytes + 48;   // le64(row) | le64(k) | cell | proof
 constexpr size_t kPinTail = 33 * sizeof(Fr) + 3 * 96 + 3 * 4 + 48 + 12;   // powers up; three sums, their flags and RLI down
-
-C_KZG_RET bad_input(int mode) { return mode == LWKZG_MODE_CKZG ? C_KZG_BADARGS : C_KZG_ERROR; }
 
 // what the host derives from the commitments and the indices
 struct Grouping {
@@ -80,71 +79,64 @@ struct Bufs {
 };
 
 size_t carve(Bufs &b, uint8_t *base, size_t cap) {
-    size_t off = 0;
-    auto take = [&](auto *&p, size_t bytes) {
-        p = (std::remove_reference_t<decltype(p)>)(base + off);
-        off += (bytes + 255) & ~(size_t)255;
-    };
-    take(b.cells, cap * kCellBytes);
-    take(b.proofs, cap * 48);
-    take(b.comm_in, cap * 48);
-    take(b.canon_p, cap * 48);
-    take(b.canon_c, cap * 48);
-    take(b.digests, cap * 32);
-    take(b.out96, 3 * 96);
-    take(b.rli48, 48);
-    take(b.idx, cap * 8);
-    take(b.rows, cap * 4);
-    take(b.perm_row, cap * 4);
-    take(b.row_off, (cap + 1) * 4);
-    take(b.perm_col, cap * 4);
-    take(b.col_off, (kCellsPerBlob + 1) * 4);
-    take(b.verdict_p, cap * 4);
-    take(b.verdict_c, cap * 4);
-    take(b.sc_a, cap * 32);
-    take(b.sc_b, cap * 32);
-    take(b.sc_c, cap * 32);
-    take(b.kind_p, cap * 4);
-    take(b.kind_c, cap * 4);
-    take(b.status, cap * 4);
-    take(b.inf, 3 * 4);
-    take(b.pts_p, cap * sizeof(G1Affine29));
-    take(b.pts_c, cap * sizeof(G1Affine29));
-    take(b.tab_p, cap * kVmsmRows * sizeof(G1Affine29));
-    take(b.tab_c, cap * kVmsmRows * sizeof(G1Affine29));
-    take(b.vm_tmp, cap * 2 * kVmsmSteps * sizeof(G1Xyzz29));
-    take(b.partial, 3 * vmsm_max_slices(cap) * 256 * sizeof(G1Xyzz29));
-    take(b.bsum, 3 * 256 * sizeof(G1Xyzz29));
-    take(b.vm_pre, cap * 2 * kVmsmSteps * sizeof(F29<2>));
-    take(b.a_mont, cap * sizeof(Fr));
-    take(b.pw, 33 * sizeof(Fr));
-    take(b.colcoef, (size_t)kCellsPerBlob * kCellElems * sizeof(Fr));
-    return off;
+    Carver cv(base);
+    cv.take(b.cells, cap * kCellBytes);
+    cv.take(b.proofs, cap * 48);
+    cv.take(b.comm_in, cap * 48);
+    cv.take(b.canon_p, cap * 48);
+    cv.take(b.canon_c, cap * 48);
+    cv.take(b.digests, cap * 32);
+    cv.take(b.out96, 3 * 96);
+    cv.take(b.rli48, 48);
+    cv.take(b.idx, cap * 8);
+    cv.take(b.rows, cap * 4);
+    cv.take(b.perm_row, cap * 4);
+    cv.take(b.row_off, (cap + 1) * 4);
+    cv.take(b.perm_col, cap * 4);
+    cv.take(b.col_off, (kCellsPerBlob + 1) * 4);
+    cv.take(b.verdict_p, cap * 4);
+    cv.take(b.verdict_c, cap * 4);
+    cv.take(b.sc_a, cap * 32);
+    cv.take(b.sc_b, cap * 32);
+    cv.take(b.sc_c, cap * 32);
+    cv.take(b.kind_p, cap * 4);
+    cv.take(b.kind_c, cap * 4);
+    cv.take(b.status, cap * 4);
+    cv.take(b.inf, 3 * 4);
+    cv.take(b.pts_p, cap * sizeof(G1Affine29));
+    cv.take(b.pts_c, cap * sizeof(G1Affine29));
+    cv.take(b.tab_p, cap * kVmsmRows * sizeof(G1Affine29));
+    cv.take(b.tab_c, cap * kVmsmRows * sizeof(G1Affine29));
+    cv.take(b.vm_tmp, cap * 2 * kVmsmSteps * sizeof(G1Xyzz29));
+    cv.take(b.partial, 3 * vmsm_max_slices(cap) * 256 * sizeof(G1Xyzz29));
+    cv.take(b.bsum, 3 * 256 * sizeof(G1Xyzz29));
+    cv.take(b.vm_pre, cap * 2 * kVmsmSteps * sizeof(F29<2>));
+    cv.take(b.a_mont, cap * sizeof(Fr));
+    cv.take(b.pw, 33 * sizeof(Fr));
+    cv.take(b.colcoef, (size_t)kCellsPerBlob * kCellElems * sizeof(Fr));
+    return cv.bytes();
 }
 
 // grow-only, kept with the settings object: no allocation in steady state (caller holds c->mu)
 C_KZG_RET reserve(Ctx *c, size_t n, Bufs &b) {
     if (!c->cellv_ev) LWK_HIP(hipEventCreateWithFlags(&c->cellv_ev, hipEventDisableTiming));
-    if (c->cellv_cap < n) {
-        LWK_HIP(hipDeviceSynchronize());   // work on any stream may still be using the old buffers
-        if (c->cellv_buf) hipFree(c->cellv_buf);
+    if (c->cellv.cap < n) {
+        size_t bytes = 0;
+        C_KZG_RET rc = grow_reserve(c->cellv, n, 256, [&](size_t cap) { Bufs probe; return bytes = carve(probe, nullptr, cap); }, nullptr);
+        if (rc == C_KZG_ERROR) return rc;   // the wait failed: both buffers are as they were
         if (c->cellv_pin) hipHostFree(c->cellv_pin);
-        c->cellv_buf = c->cellv_pin = nullptr;
-        c->cellv_cap = 0;
-        size_t cap = 256;
-        while (cap < n) cap <<= 1;
-        Bufs probe;
-        const size_t bytes = carve(probe, nullptr, cap);
-        if (hipMalloc((void **)&c->cellv_buf, bytes) != hipSuccess || hipHostMalloc((void **)&c->cellv_pin, cap * 36 + kPinTail) != hipSuccess) {
+        c->cellv_pin = nullptr;
+        if (rc == C_KZG_OK && hipHostMalloc((void **)&c->cellv_pin, c->cellv.cap * 36 + kPinTail) != hipSuccess) {
             (void)hipGetLastError();
-            if (c->cellv_buf) hipFree(c->cellv_buf);
-            c->cellv_buf = nullptr;
-            set_error("verify_cell_kzg_proof_batch: no memory for a batch of %zu cells (%zu bytes on the device)", n, bytes);
-            return C_KZG_MALLOC;
+            grow_free(c->cellv);
+            rc = C_KZG_MALLOC;
         }
-        c->cellv_cap = cap;
+        if (rc != C_KZG_OK) {
+            set_error("verify_cell_kzg_proof_batch: no memory for a batch of %zu cells (%zu bytes on the device)", n, bytes);
+            return rc;
+        }
     }
-    carve(b, c->cellv_buf, c->cellv_cap);
+    carve(b, c->cellv.dev, c->cellv.cap);
     return C_KZG_OK;
 }
 
@@ -218,15 +210,12 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
     if (rc != C_KZG_OK) return rc;
     if ((rc = ctx_reserve(c, 1)) != C_KZG_OK) return rc;
     WsUse wsu(c, st);
-    struct Drain {   // nothing of this call is in flight when it returns, whatever the exit
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};   // nothing of this call is in flight when it returns, whatever the exit
     PhaseClock clk;
     clk.begin(st);
     uint8_t *pin = c->cellv_pin;
-    uint8_t *pin_dig = pin, *pin_tail = pin + 36 * c->cellv_cap;
-    int32_t *pin_status = (int32_t *)(pin + 32 * c->cellv_cap);
+    uint8_t *pin_dig = pin, *pin_tail = pin + 36 * c->cellv.cap;
+    int32_t *pin_status = (int32_t *)(pin + 32 * c->cellv.cap);
 
     // the distinct commitments, padded with infinity encodings to the proofs' count: both point sets go through the two-set launches
     std::vector<uint8_t> padded(48 * n, 0);
@@ -332,20 +321,6 @@ C_KZG_RET cell_batch_impl(bool *ok, uint8_t *partials, const void *comms, const 
     return rc;
 }
 
-// nothing may unwind across the C ABI
-template <class F>
-C_KZG_RET cellv_guarded(const char *what, F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", what);
-        return C_KZG_MALLOC;
-    } catch (...) {
-        set_error("%s: unexpected exception", what);
-        return C_KZG_ERROR;
-    }
-}
-
 }  // namespace
 
 }  // namespace lwk
@@ -358,15 +333,15 @@ C_KZG_RET lwkzg_verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commitments
                                             const Bytes48 *proofs, size_t n, const KZGSettings *s) {
     if (!ok) return C_KZG_BADARGS;
     *ok = false;
-    return cellv_guarded("lwkzg_verify_cell_kzg_proof_batch",
-                         [&] { return cell_batch_impl(ok, nullptr, commitments, cell_indices, cells, proofs, n, s, false, nullptr); });
+    return guarded("lwkzg_verify_cell_kzg_proof_batch",
+                   [&] { return cell_batch_impl(ok, nullptr, commitments, cell_indices, cells, proofs, n, s, false, nullptr); });
 }
 
 C_KZG_RET lwkzg_verify_cell_kzg_proof_batch_device(bool *ok, const void *commitments48_dev, const void *cell_indices_dev, const void *cells_dev,
                                                    const void *proofs48_dev, size_t n, const KZGSettings *s, void *stream) {
     if (!ok) return C_KZG_BADARGS;
     *ok = false;
-    return cellv_guarded("lwkzg_verify_cell_kzg_proof_batch_device", [&] {
+    return guarded("lwkzg_verify_cell_kzg_proof_batch_device", [&] {
         return cell_batch_impl(ok, nullptr, commitments48_dev, cell_indices_dev, cells_dev, proofs48_dev, n, s, true, (hipStream_t)stream);
     });
 }
@@ -374,15 +349,15 @@ C_KZG_RET lwkzg_verify_cell_kzg_proof_batch_device(bool *ok, const void *commitm
 C_KZG_RET lwkzg_cell_verify_partials(uint8_t *out, const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
                                      const Bytes48 *proofs, size_t n, const KZGSettings *s) {
     if (!out && n) return C_KZG_BADARGS;
-    return cellv_guarded("lwkzg_cell_verify_partials",
-                         [&] { return cell_batch_impl(nullptr, out, commitments, cell_indices, cells, proofs, n, s, false, nullptr); });
+    return guarded("lwkzg_cell_verify_partials",
+                   [&] { return cell_batch_impl(nullptr, out, commitments, cell_indices, cells, proofs, n, s, false, nullptr); });
 }
 
 C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
                                           const Bytes48 *proofs, size_t n, int mode) {
     if (!r_out || (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG)) return C_KZG_BADARGS;
     if (n && (!commitments || !cell_indices || !cells || !proofs)) return C_KZG_BADARGS;
-    return cellv_guarded("lwkzg_cell_batch_challenge_host", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_cell_batch_challenge_host", [&]() -> C_KZG_RET {
         Grouping g;
         if (!group_items(g, (const uint8_t *)commitments, cell_indices, n)) return C_KZG_BADARGS;
         std::vector<uint8_t> digests(32 * n), msg(kItemMsg);

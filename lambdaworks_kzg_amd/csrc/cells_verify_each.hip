@@ -12,6 +12,9 @@
 //   combine     k_celleach_combine, one lane per item: P = C - [I(tau)]G + [c_k]pi, affine, with -pi, as the blob call's records
 //   pairing     k_each_pairing (verify_each.hip) against the line tables of g2_values[0] and [64], made once per context
 // The verdicts and status words come back in one copy each; the host maps a status to the batch of one's code.
+#include "abi_guard.h"
+#include "carve.h"
+#include "cells_common.h"
 #include "each.h"
 #include "cell_interp.cuh"
 #include "cell_each.cuh"
@@ -26,11 +29,8 @@ namespace {
 
 #include "recover_consts.inc"   // w8192^-1 and 1/64 in Montgomery form, as recover.hip takes them
 
-constexpr size_t kCellBytes = (size_t)kCellElems * 32;
 // the status word of an item whose index is not below 128: no C_KZG_RET, so that the host can answer C_KZG_BADARGS for it in both modes
 constexpr int32_t kStatusBadIndex = 0x100;
-
-C_KZG_RET bad_input(int mode) { return mode == LWKZG_MODE_CKZG ? C_KZG_BADARGS : C_KZG_ERROR; }
 
 __device__ __forceinline__ Fr const_fr(const uint32_t *limbs) {
     Fr c;
@@ -143,50 +143,32 @@ struct Bufs {
 };
 
 size_t carve(Bufs &b, uint8_t *base, size_t cap) {
-    size_t off = 0;
-    auto take = [&](auto *&p, size_t bytes) {
-        p = (std::remove_reference_t<decltype(p)>)(base + off);
-        off += (bytes + 255) & ~(size_t)255;
-    };
-    take(b.cells, cap * kCellBytes);
-    take(b.proofs, cap * 48);
-    take(b.comms, cap * 48);
-    take(b.canon_p, cap * 48);
-    take(b.canon_c, cap * 48);
-    take(b.ok, cap);
-    take(b.idx, cap * 8);
-    take(b.verdict_p, cap * 4);
-    take(b.verdict_c, cap * 4);
-    take(b.kind_p, cap * 4);
-    take(b.kind_c, cap * 4);
-    take(b.status, cap * 4);
-    take(b.pts_p, cap * sizeof(G1Affine29));
-    take(b.pts_c, cap * sizeof(G1Affine29));
-    take(b.isum, cap * sizeof(G1Xyzz));
-    take(b.pts, cap * sizeof(EachPoints));
-    return off;
+    Carver cv(base);
+    cv.take(b.cells, cap * kCellBytes);
+    cv.take(b.proofs, cap * 48);
+    cv.take(b.comms, cap * 48);
+    cv.take(b.canon_p, cap * 48);
+    cv.take(b.canon_c, cap * 48);
+    cv.take(b.ok, cap);
+    cv.take(b.idx, cap * 8);
+    cv.take(b.verdict_p, cap * 4);
+    cv.take(b.verdict_c, cap * 4);
+    cv.take(b.kind_p, cap * 4);
+    cv.take(b.kind_c, cap * 4);
+    cv.take(b.status, cap * 4);
+    cv.take(b.pts_p, cap * sizeof(G1Affine29));
+    cv.take(b.pts_c, cap * sizeof(G1Affine29));
+    cv.take(b.isum, cap * sizeof(G1Xyzz));
+    cv.take(b.pts, cap * sizeof(EachPoints));
+    return cv.bytes();
 }
 
 // grow-only, kept with the settings object: first 64 items, then doubling; no allocation in steady state (caller holds c->mu)
 C_KZG_RET reserve(Ctx *c, size_t n, Bufs &b) {
-    if (c->celleach_cap < n) {
-        LWK_HIP(hipDeviceSynchronize());   // work on any stream may still be using the old buffer
-        if (c->celleach_buf) hipFree(c->celleach_buf);
-        c->celleach_buf = nullptr;
-        c->celleach_cap = 0;
-        size_t cap = 64;
-        while (cap < n) cap <<= 1;
-        Bufs probe;
-        const size_t bytes = carve(probe, nullptr, cap);
-        if (hipMalloc((void **)&c->celleach_buf, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("verify_cell_kzg_proof_each: no device memory for %zu cells (%zu bytes)", cap, bytes);
-            return C_KZG_MALLOC;
-        }
-        c->celleach_cap = cap;
-    }
-    carve(b, c->celleach_buf, c->celleach_cap);
-    return C_KZG_OK;
+    C_KZG_RET rc = grow_reserve(c->celleach, n, 64, [](size_t cap) { Bufs probe; return carve(probe, nullptr, cap); },
+                                "verify_cell_kzg_proof_each: no device memory for %zu cells (%zu bytes)");
+    if (rc == C_KZG_OK) carve(b, c->celleach.dev, c->celleach.cap);
+    return rc;
 }
 
 // flag | x 48 | y 48 of an item's P: 0 = affine, 1 = the point at infinity, 2 = the item did not reach the combine
@@ -236,10 +218,7 @@ C_KZG_RET cell_each_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *points_out, 
     if (rc != C_KZG_OK) return rc;
     const PairingLine *lines = nullptr;
     if (!points_out && (rc = each_line_tables(s, 64, &c->celleach_lines, &lines)) != C_KZG_OK) return rc;
-    struct Drain {   // nothing of this call is in flight when it returns, whatever the exit
-        hipStream_t st;
-        ~Drain() { (void)hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};   // nothing of this call is in flight when it returns, whatever the exit
     const uint8_t *d_comms = (const uint8_t *)comms, *d_cells = (const uint8_t *)cells, *d_proofs = (const uint8_t *)proofs;
     const uint64_t *d_idx = (const uint64_t *)idx;
     if (!device_inputs) {
@@ -294,20 +273,6 @@ C_KZG_RET cell_each_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *points_out, 
     return C_KZG_OK;
 }
 
-// nothing may unwind across the C ABI
-template <class F>
-C_KZG_RET celleach_guarded(const char *what, F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", what);
-        return C_KZG_MALLOC;
-    } catch (...) {
-        set_error("%s: unexpected exception", what);
-        return C_KZG_ERROR;
-    }
-}
-
 }  // namespace
 
 }  // namespace lwk
@@ -318,7 +283,7 @@ extern "C" {
 
 C_KZG_RET lwkzg_verify_cell_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const Bytes48 *commitments, const uint64_t *cell_indices,
                                            const Cell *cells, const Bytes48 *proofs, size_t n, const KZGSettings *s) {
-    return celleach_guarded("lwkzg_verify_cell_kzg_proof_each", [&] {
+    return guarded("lwkzg_verify_cell_kzg_proof_each", [&] {
         return cell_each_impl(ok_out, rc_out, nullptr, commitments, cell_indices, cells, proofs, n, s, false, nullptr);
     });
 }
@@ -326,7 +291,7 @@ C_KZG_RET lwkzg_verify_cell_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, con
 C_KZG_RET lwkzg_verify_cell_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_out, const void *commitments48_dev,
                                                   const void *cell_indices_dev, const void *cells_dev, const void *proofs48_dev, size_t n,
                                                   const KZGSettings *s, void *stream) {
-    return celleach_guarded("lwkzg_verify_cell_kzg_proof_each_device", [&] {
+    return guarded("lwkzg_verify_cell_kzg_proof_each_device", [&] {
         return cell_each_impl(ok_out, rc_out, nullptr, commitments48_dev, cell_indices_dev, cells_dev, proofs48_dev, n, s, true,
                               (hipStream_t)stream);
     });
@@ -335,7 +300,7 @@ C_KZG_RET lwkzg_verify_cell_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_o
 C_KZG_RET lwkzg_cell_verify_each_points(uint8_t *out, const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
                                         const Bytes48 *proofs, size_t n, const KZGSettings *s) {
     if (!out && n) return C_KZG_BADARGS;
-    return celleach_guarded("lwkzg_cell_verify_each_points", [&] {
+    return guarded("lwkzg_cell_verify_each_points", [&] {
         return cell_each_impl(nullptr, nullptr, out, commitments, cell_indices, cells, proofs, n, s, false, nullptr);
     });
 }

@@ -235,6 +235,28 @@ struct LagrangeForm {
     size_t direct_row_bytes = 0;
 };
 
+// A device buffer that a settings object keeps and that only grows: no allocation in steady state. cap counts what its user counts
+// (blobs, items). grow_reserve (engine.hip; caller holds the context's lock): big enough -> C_KZG_OK at once; else every stream of the
+// device is waited for (work on any of them may still be using the old block), the block is freed and one of first_cap, doubled until it
+// holds n, is allocated: bytes_for_cap(cap) bytes. No memory: the buffer is left empty, `what` (a format for cap and the byte count;
+// nullptr: no text) becomes the error text and C_KZG_MALLOC comes back.
+struct GrowBuf {
+    uint8_t *dev = nullptr;
+    size_t cap = 0;
+};
+C_KZG_RET grow_reserve(GrowBuf &g, size_t n, size_t first_cap, const std::function<size_t(size_t)> &bytes_for_cap, const char *what);
+void grow_free(GrowBuf &g);
+
+// on scope exit: nothing enqueued on the stream is still in flight / the device block is released
+struct StreamDrain {
+    hipStream_t st;
+    ~StreamDrain() { (void)hipStreamSynchronize(st); }
+};
+struct DevBlock {
+    void *p;
+    ~DevBlock() { hipFree(p); }
+};
+
 // The object KZGSettings.fs points to. Its first member is a genuine FFTSettings.
 // Device-side double buffer of the long host-pointer batches (r06; /root/reference/fuzz/base_fuzz.h:17-34 is that kind of caller: plain
 // host arrays). r05 cut such a batch into slices of 512 blobs on two streams and two workspace halves, so that the upload of one slice ran
@@ -297,20 +319,16 @@ struct Ctx {
     DevStage stage;     // under mu
     uint8_t *one_pin = nullptr;    // 4 KiB of pinned memory for a ONE-blob proof call (r06): XYZZ sum 224 | redo flag 4 | digest 32; under mu
     hipStream_t prio_copy = nullptr;   // a high-priority stream for the uploads of verify_prepare_staged (created by its first call, under mu)
-    uint8_t *vblobs = nullptr;     // ALL blobs of a long host-pointer verification on the device (grow-only, under mu): verify_prepare_staged
-    size_t vblobs_cap = 0;         // blobs
+    GrowBuf vblobs;                // ALL blobs of a long host-pointer verification on the device (cap in blobs; under mu): verify_prepare_staged
     uint8_t *host_res = nullptr;   // results / verdicts / digests of a long host-pointer batch on the device (grow-only, under mu):
     size_t host_res_cap = 0;       // r05 allocated and freed them per call, 6 ms of a 52 ms call of 4096 blobs (profiles/r06_experiments.md section 6)
     void *each_lines = nullptr;    // verify_each.hip: the line tables of g2_values[0] and [1] on the device (2 x 68 PairingLine), made on first use; under mu
-    uint8_t *each_buf = nullptr;   // verify_each.hip: per-item points and verdicts (grow-only, under mu)
-    size_t each_cap = 0;           // items each_buf holds
-    uint8_t *cellv_buf = nullptr;  // cells_verify_api.hip: everything a cell proof batch keeps on the device, one allocation carved up (grow-only, under mu)
-    uint8_t *cellv_pin = nullptr;  // hipHostMalloc: its digests and status words on their way down, the powers of r up, the sums down
-    size_t cellv_cap = 0;          // items both hold
+    GrowBuf each;                  // verify_each.hip: per-item points and verdicts (cap in items; under mu)
+    GrowBuf cellv;                 // cells_verify_api.hip: everything a cell proof batch keeps on the device, one allocation carved up (cap in items; under mu)
+    uint8_t *cellv_pin = nullptr;  // hipHostMalloc, for cellv.cap items: its digests and status words on their way down, the powers of r up, the sums down
     hipEvent_t cellv_ev = nullptr; // the digests and status words have landed
     void *celleach_lines = nullptr;   // cells_verify_each.hip: the line tables of g2_values[0] and [64] on the device, made on first use; under mu
-    uint8_t *celleach_buf = nullptr;  // cells_verify_each.hip: everything a per-item cell verification keeps on the device, one allocation carved up (grow-only, under mu)
-    size_t celleach_cap = 0;          // items celleach_buf holds
+    GrowBuf celleach;                 // cells_verify_each.hip: everything a per-item cell verification keeps on the device, one allocation carved up (cap in items; under mu)
     Fr *recover_tab = nullptr;     // recover_api.hip: the table k_recover_setup leaves for the call's other kernels (kRecoverTabElems, with the context)
     VerifyBuffers vs;   // verify-side scratch, sized for vs_cap blobs
     size_t vs_cap;

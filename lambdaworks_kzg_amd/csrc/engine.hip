@@ -482,12 +482,12 @@ void ctx_destroy(Ctx *c) {
     }
     if (c->comb.pinned_blobs) hipHostFree(c->comb.pinned_blobs);
     dev_free(c->host_res);
-    dev_free(c->vblobs);
+    grow_free(c->vblobs);
     dev_free(c->each_lines);
-    dev_free(c->each_buf);
-    dev_free(c->cellv_buf);
+    grow_free(c->each);
+    grow_free(c->cellv);
     dev_free(c->celleach_lines);
-    dev_free(c->celleach_buf);
+    grow_free(c->celleach);
     dev_free(c->recover_tab);
     if (c->cellv_pin) hipHostFree(c->cellv_pin);
     if (c->cellv_ev) hipEventDestroy(c->cellv_ev);
@@ -1331,6 +1331,29 @@ uint8_t *host_res_block(Ctx *c, size_t bytes) {
     }
     c->host_res_cap = cap;
     return c->host_res;
+}
+
+// engine.h: GrowBuf
+C_KZG_RET grow_reserve(GrowBuf &g, size_t n, size_t first_cap, const std::function<size_t(size_t)> &bytes_for_cap, const char *what) {
+    if (g.cap >= n) return C_KZG_OK;
+    LWK_HIP(hipDeviceSynchronize());
+    grow_free(g);
+    size_t cap = first_cap;
+    while (cap < n) cap <<= 1;
+    const size_t bytes = bytes_for_cap(cap);
+    if (hipMalloc((void **)&g.dev, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        g.dev = nullptr;
+        if (what) set_error(what, cap, bytes);
+        return C_KZG_MALLOC;
+    }
+    g.cap = cap;
+    return C_KZG_OK;
+}
+
+void grow_free(GrowBuf &g) {
+    dev_free(g.dev);
+    g.cap = 0;
 }
 
 // ---- the device-side double buffer of the long host-pointer batches (engine.h: DevStage). Caller holds c->mu. ---------------------------

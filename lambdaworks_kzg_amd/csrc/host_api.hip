@@ -1,5 +1,6 @@
 // host_api.hip -- the host-pointer batch ABI: commitments, blob proofs and point proofs of host-memory batches (one launch set, slices on
 // two streams, or the staged whole-chunk schedule), the coalescing fronts of the single-blob symbols, and the reference's own symbols.
+#include "abi_guard.h"
 #include "engine_internal.h"
 
 #include <stdio.h>
@@ -180,7 +181,7 @@ static bool combine_commit(Ctx *c, uint8_t *out48, const uint8_t *blob, int mode
 
 namespace {
 
-struct DevBlock {  // a piece of the context's result block (host_res_block) carved into 256-byte aligned pieces
+struct ResBlock {  // a piece of the context's result block (host_res_block) carved into 256-byte aligned pieces
     uint8_t *base = nullptr;
     size_t used = 0, cap = 0;
     static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -266,12 +267,12 @@ static C_KZG_RET commitment_batch_impl(KZGCommitment *out, const Blob *blobs, si
     std::vector<int32_t> h_status(n);
     // results and verdicts of all slices stay on the device until the end: a D2H copy into pageable memory would make
     // this thread wait for the slice it belongs to
-    uint8_t *d_out_all = host_res_block(c, DevBlock::pad(n * 48) + n * 4);
+    uint8_t *d_out_all = host_res_block(c, ResBlock::pad(n * 48) + n * 4);
     if (!d_out_all) {
         set_error("lwkzg_blob_to_kzg_commitment_batch: out of device memory for %zu results", n);
         return C_KZG_MALLOC;
     }
-    int32_t *d_status_all = (int32_t *)(d_out_all + DevBlock::pad(n * 48));
+    int32_t *d_status_all = (int32_t *)(d_out_all + ResBlock::pad(n * 48));
     LWK_HIP(hipEventRecord(c->ev_fork, c->stream));
     if (n > kMaxChunk && dev_stage_ready(c)) {   // (up to one chunk r05's 128 + 384 + 512 slices measure better: 81.9k against 79.9k ops/s at 1024 blobs)
         // r06 (engine.h: DevStage): the slices are uploaded into a device-side double buffer on a copy stream and go through the
@@ -338,8 +339,8 @@ C_KZG_RET point_proofs_sliced(Ctx *c, uint8_t *proofs_out, uint8_t *ys_out, cons
     C_KZG_RET rc = ctx_reserve(c, kMaxChunk);
     if (rc != C_KZG_OK) return rc;
     Workspace &w = c->ws;
-    DevBlock blk;
-    if (!blk.alloc(c, DevBlock::pad(n * 48) + 2 * DevBlock::pad(n * 32) + DevBlock::pad(n * 4))) {
+    ResBlock blk;
+    if (!blk.alloc(c, ResBlock::pad(n * 48) + 2 * ResBlock::pad(n * 32) + ResBlock::pad(n * 4))) {
         set_error("lwkzg_compute_kzg_proof_batch: out of device memory for %zu results", n);
         return C_KZG_MALLOC;
     }
@@ -393,8 +394,8 @@ C_KZG_RET blob_proofs_sliced(Ctx *c, uint8_t *out, const uint8_t *blobs, const u
     C_KZG_RET rc = ctx_reserve(c, kMaxChunk);
     if (rc != C_KZG_OK) return rc;
     Workspace &w = c->ws;
-    DevBlock blk;
-    if (!blk.alloc(c, 3 * DevBlock::pad(n * 48) + DevBlock::pad(n * 32) + DevBlock::pad(n * 4))) {
+    ResBlock blk;
+    if (!blk.alloc(c, 3 * ResBlock::pad(n * 48) + ResBlock::pad(n * 32) + ResBlock::pad(n * 4))) {
         set_error("lwkzg_compute_blob_kzg_proof_batch: out of device memory for %zu results", n);
         return C_KZG_MALLOC;
     }
@@ -753,22 +754,6 @@ static C_KZG_RET point_proof_batch_impl(KZGProof *proofs_out, Bytes32 *ys_out, c
 }
 
 }  // namespace lwk
-
-// (a template cannot have C linkage)
-namespace {
-template <class F>
-C_KZG_RET guarded(const char *what, F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        lwk::set_error("%s: out of host memory", what);
-        return C_KZG_MALLOC;
-    } catch (...) {
-        lwk::set_error("%s: unexpected exception", what);
-        return C_KZG_ERROR;
-    }
-}
-}  // namespace
 
 using namespace lwk;
 

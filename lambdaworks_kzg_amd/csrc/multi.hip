@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "abi_guard.h"
 #include "engine.h"
 
 namespace lwk {
@@ -77,20 +78,6 @@ C_KZG_RET on_every_device(size_t parts, F f) {
             return (C_KZG_RET)rc[k];
         }
     return C_KZG_OK;
-}
-
-// nothing may unwind across the C ABI: the entry points size host vectors by the number of devices and of blobs
-template <class F>
-C_KZG_RET guarded_multi(const char *what, F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", what);
-        return C_KZG_MALLOC;
-    } catch (...) {
-        set_error("%s: unexpected exception", what);
-        return C_KZG_ERROR;
-    }
 }
 
 // the shards of a verification are released on every way out of it
@@ -182,7 +169,7 @@ template <class Call>
 C_KZG_RET sharded_batch(const LwkzgMulti *m, size_t n, size_t *first_bad, Call call) {
     if (!m) return C_KZG_BADARGS;
     if (first_bad) *first_bad = (size_t)-1;
-    return guarded_multi("lwkzg_multi batch", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_multi batch", [&]() -> C_KZG_RET {
         const size_t parts = m->s.size();
         std::vector<size_t> bad(parts, (size_t)-1);
         C_KZG_RET rc = on_every_device(parts, [&](size_t k) -> int {
@@ -279,7 +266,7 @@ template <class Call>
 C_KZG_RET sharded_device_batch(const LwkzgMulti *m, const size_t *n_per_device, size_t *first_bad, Call call) {
     if (!m || !n_per_device) return C_KZG_BADARGS;
     if (first_bad) *first_bad = (size_t)-1;
-    return guarded_multi("lwkzg_multi device batch", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_multi device batch", [&]() -> C_KZG_RET {
         const size_t parts = m->s.size();
         std::vector<size_t> bad(parts, (size_t)-1);
         C_KZG_RET rc = on_every_device(parts, [&](size_t k) -> int {
@@ -340,7 +327,7 @@ C_KZG_RET lwkzg_multi_verify_blob_kzg_proof_batch_device(bool *ok, const void *c
     if (!ok) return C_KZG_BADARGS;
     *ok = false;
     if (!m || !blobs_dev || !commitments48_dev || !proofs48_dev || !n_per_device) return C_KZG_BADARGS;
-    return guarded_multi("lwkzg_multi_verify_blob_kzg_proof_batch_device", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_multi_verify_blob_kzg_proof_batch_device", [&]() -> C_KZG_RET {
         const size_t parts = m->s.size();
         std::vector<LwkzgVerifyShard *> shard(parts, nullptr);
         ShardsGuard free_shards{shard};
@@ -368,7 +355,7 @@ C_KZG_RET lwkzg_multi_verify_blob_kzg_proof_batch(bool *ok, const Blob *blobs, c
     if (!ok) return C_KZG_BADARGS;
     *ok = false;
     if (!m || ((!blobs || !commitments || !proofs) && n)) return C_KZG_BADARGS;
-    return guarded_multi("lwkzg_multi_verify_blob_kzg_proof_batch", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_multi_verify_blob_kzg_proof_batch", [&]() -> C_KZG_RET {
         const size_t parts = m->s.size();
         std::vector<LwkzgVerifyShard *> shard(parts, nullptr);
         ShardsGuard free_shards{shard};
@@ -394,7 +381,7 @@ C_KZG_RET lwkzg_multi_verify_blob_kzg_proof_batch(bool *ok, const Blob *blobs, c
 // scalars: whole tiles per device, one 48-byte partial sum back from each, added on the host.
 C_KZG_RET lwkzg_multi_g1_msm_tiled(uint8_t out48[48], const uint8_t *scalars_be, size_t n_terms, const LwkzgMulti *m) {
     if (!m || !out48 || !scalars_be || n_terms == 0 || n_terms % 4096) return C_KZG_BADARGS;
-    return guarded_multi("lwkzg_multi_g1_msm_tiled", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_multi_g1_msm_tiled", [&]() -> C_KZG_RET {
     const size_t parts = m->s.size(), tiles = n_terms / 4096;
     std::vector<uint8_t> partial(parts * 48, 0);
     std::vector<int> have(parts, 0);

@@ -10,6 +10,7 @@
 // that is  e(C - [y]G + [z]pi, G2) * e(-pi, [tau]G2) == 1, which needs no G2 arithmetic: the same
 // accept/reject bit with G2 and [tau]G2 taken straight from the setup.
 #include <chrono>
+#include "abi_guard.h"
 #include "engine.h"
 #include "knobs.h"
 #include <memory>
@@ -762,24 +763,7 @@ C_KZG_RET cell_batch_finish(bool *ok, uint8_t *out4x97, const uint8_t sums[3][96
 }
 }  // namespace lwk
 
-extern "C" {
 
-}  // extern "C"
-namespace {
-// the verification entry points size host vectors by n: nothing may unwind across the C ABI
-template <class F>
-C_KZG_RET guarded(const char *what, F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        lwk::set_error("%s: out of host memory", what);
-        return C_KZG_MALLOC;
-    } catch (...) {
-        lwk::set_error("%s: unexpected exception", what);
-        return C_KZG_ERROR;
-    }
-}
-}  // namespace
 extern "C" {
 
 static C_KZG_RET verify_batch_impl(bool *ok, const Blob *blobs, const Bytes48 *commitments_bytes, const Bytes48 *proofs_bytes, size_t n,

@@ -9,6 +9,7 @@
 //   pairing  k_each_pairing: e(P_i, G2) e(-pi_i, [tau]G2) == 1 on fp12.cuh's tower, against the line tables of g2_values[0] and [1]
 //            made once per context by the host's fixed_q_lines (pairing.hip)
 // One lane per item. The verdicts and status words come back in one copy each; the host maps a status to the single call's code.
+#include "abi_guard.h"
 #include "each.h"
 #include "knobs.h"
 #include "fp12.cuh"
@@ -160,24 +161,6 @@ void launch_each_pairing(const EachPoints *pts, const PairingLine *lines, uint8_
 
 namespace {
 
-// per-item points and verdicts, grow-only. Caller holds c->mu.
-C_KZG_RET each_reserve(Ctx *c, size_t n) {
-    if (c->each_cap >= n) return C_KZG_OK;
-    LWK_HIP(hipStreamSynchronize(c->stream));
-    if (c->each_buf) hipFree(c->each_buf);
-    c->each_buf = nullptr;
-    c->each_cap = 0;
-    size_t cap = 64;
-    while (cap < n) cap <<= 1;
-    if (hipMalloc((void **)&c->each_buf, cap * (sizeof(EachPoints) + 1)) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("per-item verification: no device memory for %zu items", cap);
-        return C_KZG_MALLOC;
-    }
-    c->each_cap = cap;
-    return C_KZG_OK;
-}
-
 // inputs already on the device; blobs == nullptr: the openings form (z / y given)
 C_KZG_RET verify_each_device(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const KZGSettings *s, int mode, const uint8_t *d_blobs,
                              const uint8_t *d_comm, const uint8_t *d_proofs, const uint8_t *d_z, const uint8_t *d_y, size_t n,
@@ -204,9 +187,12 @@ C_KZG_RET verify_each_device(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const K
     const PairingLine *lines = nullptr;
     if (setup_ok) {
         if ((rc = each_line_tables(s, 1, &ctx->each_lines, &lines)) != C_KZG_OK) return rc;
-        if ((rc = each_reserve(ctx, n)) != C_KZG_OK) return rc;
-        EachPoints *pts = (EachPoints *)ctx->each_buf;
-        uint8_t *d_ok = ctx->each_buf + ctx->each_cap * sizeof(EachPoints);
+        // per-item points and verdicts, grow-only: 64 items at first use, then doubling
+        if ((rc = grow_reserve(ctx->each, n, 64, [](size_t cap) { return cap * (sizeof(EachPoints) + 1); },
+                               "per-item verification: no device memory for %zu items")) != C_KZG_OK)
+            return rc;
+        EachPoints *pts = (EachPoints *)ctx->each.dev;
+        uint8_t *d_ok = ctx->each.dev + ctx->each.cap * sizeof(EachPoints);
         uint32_t braw[12];
         g1_beta_raw(braw);
         const Fp beta = fe_from_raw<FpParams>(braw);
@@ -250,10 +236,7 @@ C_KZG_RET verify_each_host(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const KZG
         set_error("per-item verification: no device memory for %zu bytes of inputs", total);
         return C_KZG_MALLOC;
     }
-    struct Free {
-        uint8_t *p;
-        ~Free() { hipFree(p); }
-    } fr{d};
+    DevBlock block{d};
     uint8_t *d_blobs = blobs ? d : nullptr, *d_comm = d + blob_bytes, *d_proofs = d_comm + 48 * n;
     uint8_t *d_z = blobs ? nullptr : d_proofs + 48 * n, *d_y = blobs ? nullptr : d_z + 32 * n;
     LWK_HIP(hipMemcpy(d_comm, comms, 48 * n, hipMemcpyHostToDevice));
@@ -265,20 +248,6 @@ C_KZG_RET verify_each_host(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const KZG
         LWK_HIP(hipMemcpy(d_y, ys, 32 * n, hipMemcpyHostToDevice));
     }
     return verify_each_device(ok_out, rc_out, ctx, s, mode, d_blobs, d_comm, d_proofs, d_z, d_y, n, nullptr);
-}
-
-// nothing may unwind across the C ABI
-template <class F>
-C_KZG_RET each_guarded(const char *what, F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        set_error("%s: out of host memory", what);
-        return C_KZG_MALLOC;
-    } catch (...) {
-        set_error("%s: unexpected exception", what);
-        return C_KZG_ERROR;
-    }
 }
 
 }  // namespace
@@ -296,7 +265,7 @@ extern "C" {
 
 C_KZG_RET lwkzg_verify_blob_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const Blob *blobs, const Bytes48 *commitments,
                                            const Bytes48 *proofs, size_t n, const KZGSettings *s) {
-    return each_guarded("lwkzg_verify_blob_kzg_proof_each", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_verify_blob_kzg_proof_each", [&]() -> C_KZG_RET {
         if (!ok_out || !rc_out || !s) return C_KZG_BADARGS;
         if (n == 0) return C_KZG_OK;
         if (!blobs || !commitments || !proofs) return C_KZG_BADARGS;
@@ -309,7 +278,7 @@ C_KZG_RET lwkzg_verify_blob_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, con
 
 C_KZG_RET lwkzg_verify_blob_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_out, const void *blobs_dev, const void *commitments48_dev,
                                                   const void *proofs48_dev, size_t n, const KZGSettings *s, void *stream) {
-    return each_guarded("lwkzg_verify_blob_kzg_proof_each_device", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_verify_blob_kzg_proof_each_device", [&]() -> C_KZG_RET {
         if (!ok_out || !rc_out || !s) return C_KZG_BADARGS;
         if (n == 0) return C_KZG_OK;
         if (!blobs_dev || !commitments48_dev || !proofs48_dev) return C_KZG_BADARGS;
@@ -322,7 +291,7 @@ C_KZG_RET lwkzg_verify_blob_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_o
 
 C_KZG_RET lwkzg_verify_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const Bytes48 *commitments, const Bytes32 *zs, const Bytes32 *ys,
                                       const Bytes48 *proofs, size_t n, const KZGSettings *s) {
-    return each_guarded("lwkzg_verify_kzg_proof_each", [&]() -> C_KZG_RET {
+    return guarded("lwkzg_verify_kzg_proof_each", [&]() -> C_KZG_RET {
         if (!ok_out || !rc_out || !s) return C_KZG_BADARGS;
         if (n == 0) return C_KZG_OK;
         if (!commitments || !zs || !ys || !proofs) return C_KZG_BADARGS;

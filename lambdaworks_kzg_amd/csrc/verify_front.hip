@@ -1,6 +1,7 @@
 // verify_front.hip -- the front of a batch verification (host side, HIP runtime): the verify scratch, the per-blob pass over host-pointer,
 // staged, long and device-resident inputs, and the three linear combinations behind it. verify.hip and verify_each.hip call it
 // through engine.h.
+#include "carve.h"
 #include "engine_internal.h"
 
 #include <stdio.h>
@@ -58,6 +59,21 @@ void vs_free(Ctx *c) {
     c->vs_cap = 0;
 }
 
+// the pieces of vm_base for `cap` blobs; the byte count of the whole (base == nullptr: the size probe)
+static size_t carve_vmsm(VerifyBuffers &v, uint8_t *base, size_t cap) {
+    Carver cv(base);
+    cv.take(v.tab_p, (size_t)kVmsmRows * cap * sizeof(G1Affine29));
+    cv.take(v.tab_c, (size_t)kVmsmRows * cap * sizeof(G1Affine29));
+    cv.take(v.vm_tmp, (size_t)kVmsmSteps * 2 * cap * sizeof(G1Xyzz29));
+    cv.take(v.vm_pre, (size_t)kVmsmSteps * 2 * cap * sizeof(F29<2>));
+    cv.take(v.sc_a, 32 * cap);
+    cv.take(v.sc_b, 32 * cap);
+    cv.take(v.vm_partial, 3 * vmsm_max_slices(cap) * 256 * sizeof(G1Xyzz29));
+    cv.take(v.vm_bsum, 3 * 256 * sizeof(G1Xyzz29));
+    cv.take(v.vm_pw, 33 * sizeof(Fr));
+    return cv.bytes();
+}
+
 // device scratch of one batch verification of up to `cap` blobs
 static C_KZG_RET verify_buffers_alloc(VerifyBuffers &v, size_t cap) {
     const size_t nblk = lincomb3_blocks(cap);
@@ -75,28 +91,14 @@ static C_KZG_RET verify_buffers_alloc(VerifyBuffers &v, size_t cap) {
               hipMalloc((void **)&v.d_aff, 3 * 96) == hipSuccess && hipMalloc((void **)&v.d_inf, 3 * 4) == hipSuccess;
     // vmsm.hip's scratch: one allocation, 256-byte aligned pieces
     if (ok) {
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t b_tab = up((size_t)kVmsmRows * cap * sizeof(G1Affine29)), b_tmp = up((size_t)kVmsmSteps * 2 * cap * sizeof(G1Xyzz29)),
-                     b_pre = up((size_t)kVmsmSteps * 2 * cap * sizeof(F29<2>)), b_sc = up(32 * cap),
-                     b_part = up(3 * vmsm_max_slices(cap) * 256 * sizeof(G1Xyzz29)), b_bsum = up(3 * 256 * sizeof(G1Xyzz29)),
-                     b_pw = up(33 * sizeof(Fr));
-        ok = hipMalloc((void **)&v.vm_base, 2 * b_tab + b_tmp + b_pre + 2 * b_sc + b_part + b_bsum + b_pw) == hipSuccess &&
+        ok = hipMalloc((void **)&v.vm_base, carve_vmsm(v, nullptr, cap)) == hipSuccess &&
              hipHostMalloc((void **)&v.h_pin, kVmsmPinBytes, hipHostMallocDefault) == hipSuccess &&
              hipMalloc((void **)&v.d_rec, 160 * cap + 16) == hipSuccess &&
              hipHostMalloc((void **)&v.h_rec, 160 * cap + 16, hipHostMallocDefault) == hipSuccess &&
              hipEventCreateWithFlags(&v.vm_done, hipEventDisableTiming) == hipSuccess;
         if (ok) {
             v.rec_cap = cap;
-            uint8_t *p = v.vm_base;
-            v.tab_p = (G1Affine29 *)p; p += b_tab;
-            v.tab_c = (G1Affine29 *)p; p += b_tab;
-            v.vm_tmp = (G1Xyzz29 *)p; p += b_tmp;
-            v.vm_pre = (F29<2> *)p; p += b_pre;
-            v.sc_a = (uint32_t *)p; p += b_sc;
-            v.sc_b = (uint32_t *)p; p += b_sc;
-            v.vm_partial = (G1Xyzz29 *)p; p += b_part;
-            v.vm_bsum = (G1Xyzz29 *)p; p += b_bsum;
-            v.vm_pw = (Fr *)p;
+            carve_vmsm(v, v.vm_base, cap);
         }
     }
     if (!ok) {
@@ -168,31 +170,14 @@ static C_KZG_RET verify_buffers_take(Ctx *c, VerifyBuffers &vb, size_t n) {
 // read straight from the uploaded blobs (k_eval_quotient_from_blobs / its evaluation-form twin: no coefficient slots to recycle).
 // Reference mode and c-kzg mode on the Lagrange form; other forms, no memory for the buffer, or LWKZG_HOST_STAGE=0 (experiment): the
 // sliced form below. `taken` says which. Caller holds c->mu.
-static uint8_t *vblobs_reserve(Ctx *c, size_t n) {
-    if (c->vblobs_cap >= n) return c->vblobs;
-    if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-    dev_free(c->vblobs);
-    c->vblobs = nullptr;
-    c->vblobs_cap = 0;
-    size_t cap = 2 * kMaxChunk;
-    while (cap < n) cap <<= 1;
-    if (hipMalloc((void **)&c->vblobs, cap * (size_t)kBlobBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c->vblobs = nullptr;
-        return nullptr;
-    }
-    c->vblobs_cap = cap;
-    return c->vblobs;
-}
-
 static C_KZG_RET verify_prepare_staged(Ctx *c, const uint8_t *blobs, const uint8_t *comm48, const uint8_t *proofs48, size_t n, int mode,
                                        uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p, VerifyBuffers &vb, bool &taken) {
     taken = false;
     const int le = mode == LWKZG_MODE_CKZG;
     const bool evf = proof_in_evaluation_form(c, mode);
     if (!knobs().host_stage || !(mode == LWKZG_MODE_REFERENCE || evf) || n > ((size_t)1 << 17)) return C_KZG_OK;
-    uint8_t *d_all = vblobs_reserve(c, n);
-    if (!d_all) return C_KZG_OK;
+    if (grow_reserve(c->vblobs, n, 2 * kMaxChunk, [](size_t cap) { return cap * (size_t)kBlobBytes; }, nullptr) != C_KZG_OK) return C_KZG_OK;
+    uint8_t *d_all = c->vblobs.dev;
     C_KZG_RET rc = ws_long_reserve(c, n);
     if (rc != C_KZG_OK) return rc;
     taken = true;
