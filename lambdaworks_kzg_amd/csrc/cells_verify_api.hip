@@ -25,8 +25,6 @@
 
 namespace lwk {
 
-void sha256_fast(uint8_t out[32], const uint8_t *msg, size_t len);  // sha256_host.hip
-
 namespace {
 
 constexpr size_t kItemMsg = 16 + kCellBytes + 48;   // le64(row) | le64(k) | cell | proof
@@ -241,8 +239,9 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
     const int bad = (int)bad_input(mode);
     launch_cellv_digests(d_cells, d_proofs, b.rows, d_idx, b.digests, b.status, bad, le, n, st);
     clk.mark(1);
-    launch_decompress_points2(d_proofs, b.pts_p, b.kind_p, b.comm_in, b.pts_c, b.kind_c, n, st);
-    launch_subgroup_canon2(b.pts_p, b.kind_p, b.canon_p, b.verdict_p, b.pts_c, b.kind_c, b.canon_c, b.verdict_c, b.status, bad, n, st);
+    const PointSet set_p{d_proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
+    launch_decompress_points(set_p, &set_c, n, st);
+    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st);
     clk.mark(2);
     LWK_HIP(hipMemcpyAsync(pin_dig, b.digests, 32 * n, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(pin_status, b.status, 4 * n, hipMemcpyDeviceToHost, st));

@@ -230,8 +230,9 @@ C_KZG_RET cell_each_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *points_out, 
     }
     LWK_HIP(hipMemsetAsync(b.status, 0, 4 * n, st));
     const int bad = (int)bad_input(mode);
-    launch_decompress_points2(d_proofs, b.pts_p, b.kind_p, d_comms, b.pts_c, b.kind_c, n, st);
-    launch_subgroup_canon2(b.pts_p, b.kind_p, b.canon_p, b.verdict_p, b.pts_c, b.kind_c, b.canon_c, b.verdict_c, b.status, bad, n, st);
+    const PointSet set_p{d_proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{d_comms, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
+    launch_decompress_points(set_p, &set_c, n, st);
+    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st);
     uint32_t braw[12];
     g1_beta_raw(braw);
     const Fp beta = fe_from_raw<FpParams>(braw);

@@ -262,7 +262,7 @@ LWK_HD G1Affine29 affine_to_29(const G1Affine &p) {
 // representation: 0 = (x, y) is the point, 1 = point at infinity, 2 = invalid (not flagged compressed, or x^3 + 4 is
 // not a square). want_greater = the ZCash sign bit (select_sqrt_value_from_third_bit).
 // `root`: F29<2> -> its ((p + 1) / 4)-th power given the exponent's words (the default: f29_pow; k_decompress_points passes a chain
-// whose window table lives in LDS, sha256.hip)
+// whose window table lives in LDS, validate.hip)
 template <class Root>
 LWK_HD int g1_decompress29_nocheck_t(const uint8_t *in48, F29<2> &x, F29<2> &y, bool &want_greater, Root root) {
     uint8_t b[48];

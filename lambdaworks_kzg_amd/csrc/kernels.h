@@ -138,35 +138,39 @@ void launch_flag_differs48(const uint8_t *a, const uint8_t *b, uint32_t *flags, 
 // z bytes -> Montgomery. le = 0: big-endian, reduced. le = 1: little-endian, must be canonical else BADARGS.
 void launch_z_from_bytes(const uint8_t *z_bytes, Fr *z_mont, int32_t *status, int le, size_t n, hipStream_t st);
 
-// ---- Fiat-Shamir (sha256.hip)
-// validate + canonicalise commitments (decompress incl. subgroup check, recompress), then
-// z = sha256("FSBLOBVERIFY_V1_" | le64(4096) | le64(0) | blob | commitment) as Fr
-// (compute_challenge, /root/reference/src/utils.rs:120-154).
+// ---- point validation (validate.hip)
+// one set of compressed G1 points on its way through the validation: in48 -> pts / kind (0 = affine, 1 = infinity, 2 = invalid), the
+// canonical bytes, and (optional) one word of scratch per point for the verdicts of the quad-of-lanes subgroup test
+struct PointSet {
+    const uint8_t *in48;
+    G1Affine29 *pts;
+    int32_t *kind;
+    uint8_t *canon48;
+    uint32_t *verdict;
+};
+// validate + canonicalise commitments (decompress incl. subgroup check, recompress: what compute_challenge hashes,
+// /root/reference/src/utils.rs:120-154).
 // verdict_scratch (n words, with aff_out and kind_out): the validation runs as three launches with the subgroup test on a quad of
 // lanes per point (k_subgroup_coop_asm) instead of one lane per point for the whole chain
 // apart (r06): the launches carry an LDS footprint they never touch, sized so that the dispatcher cannot place their workgroups on the
-// compute units of a challenge-hash kernel running beside them (knobs.h: verify_pad_kb; profiles/r06_experiments.md section 1)
+// compute units of a challenge-hash kernel running beside them (knobs.h: verify_pad_kb; profiles/r06_experiments.md section 1; lds_pad.h)
 void launch_validate_commitments(const uint8_t *comm48, uint8_t *canon48, int32_t *status, int bad_code, size_t n,
                                  hipStream_t st, G1Affine29 *aff_out = nullptr, int32_t *kind_out = nullptr, uint32_t *verdict_scratch = nullptr,
                                  bool apart = false);
+// the same in two steps, each ONE launch per kernel over one point set or two (b: a verification's proofs and commitments together): the
+// linear combinations' multiples can start after the first. One set without verdict scratch, or validate_coop off: k_subgroup_canon alone
+void launch_decompress_points(const PointSet &a, const PointSet *b, size_t n, hipStream_t st, bool apart = false);
+void launch_subgroup_canon(const PointSet &a, const PointSet *b, int32_t *status, int bad_code, size_t n, hipStream_t st, bool apart = false);
+
+// ---- the verification's linear combinations, r05's arm (setup.hip)
 // verify side: three variable-base linear combinations in one launch (setup.hip).
 //   set 0 = sum r_i P_i, set 1 = sum rz_i P_i (P = proofs), set 2 = sum r_i C_i (C = commitments);
 // per-block partial sums to partial[set * nblk + block]
 size_t lincomb3_blocks(size_t n);  // workgroups (= partial sums) per set
 // *_mult: [2^32]P, [2^64]P, [2^96]P of every point (3 n entries, launch_point_multiples), so that each scalar is cut
 // into 32-bit pieces on lanes of their own
-void launch_point_multiples(const G1Affine29 *pts, const int32_t *kind, G1Affine29 *mult, size_t n, hipStream_t st);
-void launch_point_multiples2(const G1Affine29 *pts_a, const int32_t *kind_a, G1Affine29 *mult_a, const G1Affine29 *pts_b,
-                             const int32_t *kind_b, G1Affine29 *mult_b, size_t n, hipStream_t st);  // two sets, one launch
-// launch_validate_commitments in two launches (sha256.hip): the multiples above can start after the first
-void launch_decompress_points(const uint8_t *in48, G1Affine29 *pts, int32_t *kind, size_t n, hipStream_t st, bool apart = false);
-void launch_subgroup_canon(G1Affine29 *pts, int32_t *kind, uint8_t *canon48, int32_t *status, int bad_code, size_t n,
-                           hipStream_t st, uint32_t *verdict_scratch = nullptr, bool apart = false);
-// the same two steps for both point sets of a verification at once (one launch per kernel: r06)
-void launch_decompress_points2(const uint8_t *in48_a, G1Affine29 *pts_a, int32_t *kind_a, const uint8_t *in48_b, G1Affine29 *pts_b,
-                               int32_t *kind_b, size_t n, hipStream_t st, bool apart = false);
-void launch_subgroup_canon2(G1Affine29 *pts_a, int32_t *kind_a, uint8_t *canon48_a, uint32_t *verdict_a, G1Affine29 *pts_b, int32_t *kind_b,
-                            uint8_t *canon48_b, uint32_t *verdict_b, int32_t *status, int bad_code, size_t n, hipStream_t st, bool apart = false);
+void launch_point_multiples(const G1Affine29 *pts_a, const int32_t *kind_a, G1Affine29 *mult_a, size_t n, hipStream_t st,
+                            const G1Affine29 *pts_b = nullptr, const int32_t *kind_b = nullptr, G1Affine29 *mult_b = nullptr);  // a second set: one launch
 void launch_lincomb3(const G1Affine29 *proofs, const int32_t *proof_kind, const G1Affine29 *proof_mult, const G1Affine29 *comms,
                      const int32_t *comm_kind, const G1Affine29 *comm_mult, const uint8_t *sc_r_be, const uint8_t *sc_rz_be,
                      G1Xyzz29 *partial, size_t n, hipStream_t st);
@@ -200,17 +204,22 @@ void launch_verify_records(const uint8_t *canon_c, const uint8_t *z32, const uin
 void launch_each_openings(const uint8_t *z_in, const uint8_t *y_in, uint8_t *z_out, uint8_t *y_out, int32_t *status, int bad_code, int le,
                           size_t n, hipStream_t st);
 void launch_xyzz29_to_affine_be(const G1Xyzz29 *in, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st);
+
+// ---- Fiat-Shamir (sha256.hip, sha256_host.hip)
+// z = sha256("FSBLOBVERIFY_V1_" | le64(4096) | le64(0) | blob | commitment) as Fr (compute_challenge, /root/reference/src/utils.rs:120-154)
 void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, int le, size_t n, hipStream_t st,
                       const uint8_t *only_if_differs_from = nullptr);
 void launch_challenge_midstate(const uint8_t *blobs, uint32_t *midstate, size_t n, hipStream_t st);
 void launch_challenge_finish(const uint8_t *blobs, const uint8_t *canon48, const uint32_t *midstate, Fr *z_mont, int le, size_t n,
                              hipStream_t st);
+// sha256_host.hip: host SHA-256 -- portable | with the SHA extensions when present | the same of prefix | msg without the concatenation
 void sha256_host(uint8_t out[32], const uint8_t *msg, size_t len);
+void sha256_fast(uint8_t out[32], const uint8_t *msg, size_t len);
+void sha256_fast_prefixed(uint8_t out[32], const uint8_t *prefix, size_t prefix_len, const uint8_t *msg, size_t len);
 // sha256_host.hip: digests[i] = SHA-256("FSBLOBVERIFY_V1_" | le64(4096) | le64(0) | blobs[i] | comms[i]) on host threads
 void challenge_digests_host(uint8_t *digests32, const uint8_t *blobs, const uint8_t *comms48, size_t n);
 double host_hash_rate();   // bytes per second the host threads hashed in their recent long jobs (sha256_host.hip)
 void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n);   // 8 words per blob: the hash state k_challenge_finish continues from
-void sha256_blocks_portable(uint32_t h[8], const uint8_t *blocks, size_t n_blocks);
 
 // ---- EIP-7594 cells (cells.hip)
 constexpr int kCellElems = 64;        // field elements per cell

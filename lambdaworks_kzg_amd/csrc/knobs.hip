@@ -164,7 +164,7 @@ extern "C" __attribute__((visibility("default"))) size_t lwkzg_knob_report(char 
         (int)k.validate_coop, (int)k.ckzg_eval_proofs, (int)k.mid_proof_pipe, k.verify_msm, k.verify_fused, k.verify_pad_kb[0],
         k.verify_pad_kb[1], k.verify_pad_kb[2], k.verify_order, k.vmsm_list_cap, (int)k.host_stage, lwk::knob_names_operational(),
         lwk::knob_names_experimental());
-    const size_t need = (size_t)(n < 0 ? 0 : n) + 1;
+    const size_t need = (size_t)(n < 0 ? 0 : n >= (int)sizeof tmp ? (int)sizeof tmp - 1 : n) + 1;   // what tmp really holds, plus the terminator
     if (buf && cap) {
         const size_t c = need <= cap ? need - 1 : cap - 1;
         memcpy(buf, tmp, c);

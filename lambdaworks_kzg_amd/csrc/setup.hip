@@ -8,6 +8,7 @@
 // table is built once and cached in the settings' context.
 #include "kernels.h"
 #include "knobs.h"
+#include "lds_pad.h"
 #include "glv.cuh"
 
 namespace lwk {
@@ -154,19 +155,16 @@ __global__ __launch_bounds__(64) void k_point_multiples(const G1Affine29 *__rest
     mult[gid] = xyzz29_to_affine29(*(G1Xyzz29 *)&acc);
 }
 
-unsigned verify_pad_bytes(int which, const void *kernel);  // sha256.hip
-
-void launch_point_multiples(const G1Affine29 *pts, const int32_t *kind, G1Affine29 *mult, size_t n, hipStream_t st) {
+// one point set (pts_b null), or two in one launch. The footprint is unconditional here: r05's arm has no `apart`
+void launch_point_multiples(const G1Affine29 *pts_a, const int32_t *kind_a, G1Affine29 *mult_a, size_t n, hipStream_t st,
+                            const G1Affine29 *pts_b, const int32_t *kind_b, G1Affine29 *mult_b) {
+    const dim3 grid((unsigned)(((kLincombPieces - 1) * n + 63) / 64), pts_b ? 2 : 1);
+    if (!pts_b) pts_b = pts_a, kind_b = kind_a, mult_b = mult_a;
     ProfScope p("k_point_multiples", st);
-    hipLaunchKernelGGL(k_point_multiples, dim3((unsigned)(((kLincombPieces - 1) * n + 63) / 64)), dim3(64), verify_pad_bytes(2, (const void *)k_point_multiples), st, pts, kind, mult,
-                       pts, kind, mult, n);
-}
-
-void launch_point_multiples2(const G1Affine29 *pts_a, const int32_t *kind_a, G1Affine29 *mult_a, const G1Affine29 *pts_b,
-                             const int32_t *kind_b, G1Affine29 *mult_b, size_t n, hipStream_t st) {
-    ProfScope p("k_point_multiples", st);
-    hipLaunchKernelGGL(k_point_multiples, dim3((unsigned)(((kLincombPieces - 1) * n + 63) / 64), 2), dim3(64), verify_pad_bytes(2, (const void *)k_point_multiples), st, pts_a, kind_a,
-                       mult_a, pts_b, kind_b, mult_b, n);
+    static PadCache cache;
+    launch_padded(cache, (const void *)k_point_multiples, knobs().verify_pad_kb[2] * 1024u, [&](unsigned lds) {
+        hipLaunchKernelGGL(k_point_multiples, grid, dim3(64), lds, st, pts_a, kind_a, mult_a, pts_b, kind_b, mult_b, n);
+    });
 }
 
 // The three linear combinations of verify_kzg_proof_batch (/root/reference/src/lib.rs:679-685) in ONE launch, on points

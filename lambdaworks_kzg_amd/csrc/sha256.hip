@@ -7,8 +7,6 @@
 // The reference builds that 131 KB Vec byte by byte on the host for every blob; here the blob is
 // already in HBM, so one lane per blob streams it through the compression function (16 B loads).
 // SHA-256 is sequential per message: the parallelism is across the blobs of the batch.
-#include <stdlib.h>
-#include <atomic>
 #include "kernels.h"
 #include "knobs.h"
 #include "sha256_round.cuh"
@@ -397,339 +395,6 @@ void launch_challenge_finish(const uint8_t *blobs, const uint8_t *canon48, const
     if (n == 0) return;
     ProfScope p("k_challenge_finish", st);
     hipLaunchKernelGGL(k_challenge_finish, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, blobs, canon48, midstate, z_mont, le, n);
-}
-
-// host SHA-256 for the one batch-level hash of verify_blob_kzg_proof_batch (compute_r_powers,
-// /root/reference/src/utils.rs:166-206): a few hundred KB once per call, not worth a launch
-static const uint32_t kShaKHost[64] = {
-    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
-    0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
-    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
-    0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
-    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
-    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
-    0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-
-static void sha256_block_host(uint32_t h[8], const uint8_t *b) {
-    auto ror = [](uint32_t x, int n) { return (x >> n) | (x << (32 - n)); };
-    uint32_t w[64];
-    for (int i = 0; i < 16; i++)
-        w[i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-    for (int i = 16; i < 64; i++) {
-        uint32_t s0 = ror(w[i - 15], 7) ^ ror(w[i - 15], 18) ^ (w[i - 15] >> 3);
-        uint32_t s1 = ror(w[i - 2], 17) ^ ror(w[i - 2], 19) ^ (w[i - 2] >> 10);
-        w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-    }
-    uint32_t a = h[0], bb = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-    for (int i = 0; i < 64; i++) {
-        uint32_t t1 = hh + (ror(e, 6) ^ ror(e, 11) ^ ror(e, 25)) + ((e & f) ^ (~e & g)) + kShaKHost[i] + w[i];
-        uint32_t t2 = (ror(a, 2) ^ ror(a, 13) ^ ror(a, 22)) + ((a & bb) ^ (a & c) ^ (bb & c));
-        hh = g; g = f; f = e; e = d + t1; d = c; c = bb; bb = a; a = t1 + t2;
-    }
-    h[0] += a; h[1] += bb; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
-}
-
-void sha256_blocks_portable(uint32_t h[8], const uint8_t *blocks, size_t n_blocks) {
-    for (size_t k = 0; k < n_blocks; k++) sha256_block_host(h, blocks + 64 * k);
-}
-
-void sha256_host(uint8_t out[32], const uint8_t *msg, size_t len) {
-    uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-    size_t i = 0;
-    for (; i + 64 <= len; i += 64) sha256_block_host(h, msg + i);
-    uint8_t tail[128] = {0};
-    size_t rem = len - i;
-    for (size_t k = 0; k < rem; k++) tail[k] = msg[i + k];
-    tail[rem] = 0x80;
-    size_t tl = rem + 9 <= 64 ? 64 : 128;
-    uint64_t bits = (uint64_t)len * 8;
-    for (int k = 0; k < 8; k++) tail[tl - 1 - k] = (uint8_t)(bits >> (8 * k));
-    sha256_block_host(h, tail);
-    if (tl == 128) sha256_block_host(h, tail + 64);
-    for (int k = 0; k < 8; k++) {
-        out[4 * k] = (uint8_t)(h[k] >> 24);
-        out[4 * k + 1] = (uint8_t)(h[k] >> 16);
-        out[4 * k + 2] = (uint8_t)(h[k] >> 8);
-        out[4 * k + 3] = (uint8_t)h[k];
-    }
-}
-
-// decompress_g1_point (incl. the subgroup check) then compress_g1_point again, as compute_blob_kzg_proof +
-// compute_challenge do (/root/reference/src/lib.rs:372-375, src/utils.rs:138). One lane per point, all in the
-// lazy-limb field (field29.cuh): square root (p = 3 mod 4), root selection by the sign flag, endomorphism subgroup
-// test. Re-compressing an affine point needs no inversion: the canonical bytes are x (reduced) + flags.
-// aff_out / kind_out (optional): the validated point in the hot-loop representation and 0 = affine,
-// 1 = infinity, 2 = invalid, for the verify side's linear combinations.
-__global__ __launch_bounds__(64) void k_validate_commitments(const uint8_t *__restrict__ comm48,
-                                                             uint8_t *__restrict__ canon48, int32_t *__restrict__ status,
-                                                             int bad_code, size_t n, G1Affine29 *__restrict__ aff_out,
-                                                             int32_t *__restrict__ kind_out) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    __builtin_amdgcn_s_setprio(2);  // a latency chain, like the hash kernel it runs beside (see there)
-    G1Affine29 aff;
-    aff.x = F29<2>::zero();
-    aff.y = F29<2>::zero();
-    uint8_t o[48];
-    for (int k = 0; k < 48; k++) o[k] = 0;
-    F29<2> x = F29<2>::zero(), y = F29<2>::zero();
-    bool want_greater = false;
-    int rc = g1_decompress29_nocheck(comm48 + 48 * i, x, y, want_greater);
-    if (rc == 1) {
-        o[0] = 0xc0;
-    } else if (rc == 0) {
-        uint32_t braw[12];
-        g1_beta_raw(braw);
-        if (!g1_in_subgroup_endo<G1Xyzz29>(x, y, f29_from_raw32(braw))) {
-            rc = 2;
-        } else {
-            uint32_t rx[12];
-            f29_to_raw32(rx, x);
-            raw_to_be<12>(o, rx);
-            o[0] |= 0x80;
-            if (want_greater) o[0] |= 0x20;
-            aff.x = x;
-            aff.y = y;
-        }
-    }
-    if (rc == 2) {
-        status[i] = bad_code;
-        for (int k = 0; k < 48; k++) o[k] = 0;
-    }
-    for (int k = 0; k < 48; k++) canon48[48 * i + k] = o[k];
-    if (aff_out) aff_out[i] = aff;
-    if (kind_out) kind_out[i] = rc;
-}
-
-static bool validate_coop_enabled() {
-    return knobs().validate_coop;
-}
-
-
-void launch_validate_commitments(const uint8_t *comm48, uint8_t *canon48, int32_t *status, int bad_code, size_t n,
-                                 hipStream_t st, G1Affine29 *aff_out, int32_t *kind_out, uint32_t *verdict_scratch, bool apart) {
-    // r05: with scratch for the points and the verdicts the validation is three launches -- the square root (one lane per point, windowed),
-    // the subgroup test on a quad of lanes per point (k_subgroup_coop_asm), canonical bytes + verdicts -- 2.0 -> ~1.0 ms whatever the batch
-    if (aff_out && kind_out && verdict_scratch && n && validate_coop_enabled()) {
-        launch_decompress_points(comm48, aff_out, kind_out, n, st, apart);
-        launch_subgroup_canon(aff_out, kind_out, canon48, status, bad_code, n, st, verdict_scratch, apart);
-        return;
-    }
-    ProfScope p("k_validate_commitments", st);
-    // The kernel is a one-wave-per-workgroup latency chain that runs beside other latency chains (the Fiat-Shamir hash of
-    // the device-resident proofs, the other point set's validation). Where a wave of each shares a SIMD, both run at
-    // about half speed, and the dispatcher likes to start every kernel's workgroups on the same compute units. An LDS
-    // footprint the kernel never touches keeps them apart: 112 KB here + the hash kernel's 48 KB (or a second
-    // validation workgroup) exceed the 160 KB of a compute unit, so the dispatcher has to pick another one. The hash
-    // of 1024 blobs takes 3.2 ms instead of 4.3 ms beside it (LWKZG_VALIDATE_LDS_PAD=0 switches the padding off).
-    const unsigned lds_pad = knobs().validate_lds_pad;
-    static std::atomic<bool> pad_ok{true};  // a runtime that refuses the footprint gets the plain launch from then on
-    if (lds_pad && pad_ok.load(std::memory_order_relaxed)) {
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(k_validate_commitments, dim3((unsigned)((n + 63) / 64)), dim3(64), lds_pad, st, comm48, canon48,
-                           status, bad_code, n, aff_out, kind_out);
-        if (hipGetLastError() == hipSuccess) return;
-        pad_ok.store(false);
-    }
-    hipLaunchKernelGGL(k_validate_commitments, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, comm48, canon48, status,
-                       bad_code, n, aff_out, kind_out);
-}
-
-// ---- the same validation in two launches, for the batch verification ------------------------------------------------
-// k_decompress_points: square root only. k_subgroup_canon: subgroup test + canonical bytes + verdicts. What lies
-// between them is the point of the split: the multiples the linear combinations want (setup.hip: k_point_multiples) need
-// the decompressed point but not the subgroup verdict, so they run BESIDE the second kernel instead of behind it.
-// kind carries the sign bit in bit 8 between the two kernels (rc | want_greater << 8) and is final (0 / 1 / 2) after
-// the second; readers in between mask with 0xff.
-
-// The square root's chain for a lane that is alone on its SIMD (256 commitments are four waves): f29_pow's 4-bit windows with the products
-// INLINED (a call costs the lone wave ~40 instruction slots of moves, 475 times) and the 16-entry window table in LDS, [entry][limb][lane]
-// (the exponent is public: every lane reads the same entry, its own column; the table indexed by a run-time digit would otherwise live
-// in scratch, a memory round trip per window).
-__device__ __forceinline__ F29<2> sqrt_chain_lds(const F29<2> &a, const uint32_t *e, uint32_t (*tab)[14][64], int lane) {
-    typedef F29<2, true> Fi;
-    Fi t1;
-#pragma unroll
-    for (int j = 0; j < 14; j++) t1.l[j] = a.l[j];
-    t1 = t1 * F29<1, true>::one();
-    const Fi one = Fi::one();
-#pragma unroll
-    for (int j = 0; j < 14; j++) {
-        tab[0][j][lane] = one.l[j];
-        tab[1][j][lane] = t1.l[j];
-    }
-    Fi cur = t1;
-#pragma unroll 1
-    for (int k = 2; k < 16; k++) {
-        cur = cur * t1;
-#pragma unroll
-        for (int j = 0; j < 14; j++) tab[k][j][lane] = cur.l[j];
-    }
-    Fi acc = one;
-    bool started = false;
-#pragma unroll 1
-    for (int w = 12 * 8 - 1; w >= 0; w--) {
-        const uint32_t d = (e[w >> 3] >> (4 * (w & 7))) & 15u;
-        if (started) {
-            acc = sqr(acc);
-            acc = sqr(acc);
-            acc = sqr(acc);
-            acc = sqr(acc);
-        }
-        if (d) {
-            Fi f;
-#pragma unroll
-            for (int j = 0; j < 14; j++) f.l[j] = tab[d][j][lane];
-            acc = started ? acc * f : f;
-            started = true;
-        }
-    }
-    F29<2> r;
-#pragma unroll
-    for (int j = 0; j < 14; j++) r.l[j] = acc.l[j];
-    return r;
-}
-
-// blockIdx.y selects one of two point sets (a verification's proofs and commitments in one launch; a single set passes itself twice)
-__global__ __launch_bounds__(64) void k_decompress_points(const uint8_t *__restrict__ in48_a, G1Affine29 *__restrict__ pts_a,
-                                                          int32_t *__restrict__ kind_a, const uint8_t *__restrict__ in48_b,
-                                                          G1Affine29 *__restrict__ pts_b, int32_t *__restrict__ kind_b, size_t n) {
-    __shared__ uint32_t tab[16][14][64];   // 56 KiB: two workgroups to a compute unit
-    const uint8_t *in48 = blockIdx.y ? in48_b : in48_a;
-    G1Affine29 *pts = blockIdx.y ? pts_b : pts_a;
-    int32_t *kind = blockIdx.y ? kind_b : kind_a;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    F29<2> x = F29<2>::zero(), y = F29<2>::zero();
-    bool want_greater = false;
-    const int lane = threadIdx.x;
-    const int rc = g1_decompress29_nocheck_t(in48 + 48 * i, x, y, want_greater,
-                                             [&](const F29<2> &a, const uint32_t *e) { return sqrt_chain_lds(a, e, tab, lane); });
-    G1Affine29 aff;
-    aff.x = rc == 0 ? x : F29<2>::zero();
-    aff.y = rc == 0 ? y : F29<2>::zero();
-    pts[i] = aff;
-    kind[i] = rc | (want_greater ? 0x100 : 0);
-}
-
-// verdict (optional): the cooperative subgroup test's word per point (k_subgroup_coop_asm: 0 = not in G1, 1 = in G1, 2 = undetermined --
-// an addition met P = +-Q in its low 56 bits --, which this kernel settles with the complete-branches test)
-__global__ __launch_bounds__(64) void k_subgroup_canon(G1Affine29 *__restrict__ pts_a, int32_t *__restrict__ kind_a,
-                                                       uint8_t *__restrict__ canon48_a, const uint32_t *__restrict__ verdict_a,
-                                                       G1Affine29 *__restrict__ pts_b, int32_t *__restrict__ kind_b,
-                                                       uint8_t *__restrict__ canon48_b, const uint32_t *__restrict__ verdict_b,
-                                                       int32_t *__restrict__ status, int bad_code, size_t n) {
-    G1Affine29 *pts = blockIdx.y ? pts_b : pts_a;
-    int32_t *kind = blockIdx.y ? kind_b : kind_a;
-    uint8_t *canon48 = blockIdx.y ? canon48_b : canon48_a;
-    const uint32_t *verdict = blockIdx.y ? verdict_b : verdict_a;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int k0 = kind[i];
-    int rc = k0 & 0xff;
-    uint8_t o[48];
-    for (int k = 0; k < 48; k++) o[k] = 0;
-    if (rc == 1) {
-        o[0] = 0xc0;
-    } else if (rc == 0) {
-        const G1Affine29 aff = pts[i];
-        const uint32_t vd = verdict ? verdict[i] : 2u;
-        bool in_g1 = vd == 1u;
-        if (vd >= 2u) {
-            uint32_t braw[12];
-            g1_beta_raw(braw);
-            in_g1 = g1_in_subgroup_endo<G1Xyzz29>(aff.x, aff.y, f29_from_raw32(braw));
-        }
-        if (!in_g1) {
-            rc = 2;
-            G1Affine29 z;
-            z.x = F29<2>::zero();
-            z.y = F29<2>::zero();
-            pts[i] = z;
-        } else {
-            uint32_t rx[12];
-            f29_to_raw32(rx, aff.x);
-            raw_to_be<12>(o, rx);
-            o[0] |= 0x80;
-            if (k0 & 0x100) o[0] |= 0x20;
-        }
-    }
-    if (rc == 2) status[i] = bad_code;
-    for (int k = 0; k < 48; k++) canon48[48 * i + k] = o[k];
-    kind[i] = rc;
-}
-
-// LWKZG_VERIFY_PAD_KB (experiment, knobs.h): an LDS footprint the validation kernels never touch, so that the dispatcher cannot put their
-// workgroups on the compute units the hash kernel's workgroups occupy (profiles/r06_experiments.md section 1)
-unsigned verify_pad_bytes(int which, const void *kernel) {
-    static std::atomic<bool> allowed[3];  // a footprint above the default limit needs the attribute once per kernel
-    const unsigned b = (unsigned)knobs().verify_pad_kb[which] * 1024u;
-    if (b > 48u * 1024u && !allowed[which].exchange(true)) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-    return b;
-}
-
-void launch_decompress_points(const uint8_t *in48, G1Affine29 *pts, int32_t *kind, size_t n, hipStream_t st, bool apart) {
-    ProfScope p("k_decompress_points", st);
-    hipLaunchKernelGGL(k_decompress_points, dim3((unsigned)((n + 63) / 64)), dim3(64), apart ? verify_pad_bytes(0, (const void *)k_decompress_points) : 0u, st,
-                       in48, pts, kind, in48, pts, kind, n);
-}
-
-void launch_decompress_points2(const uint8_t *in48_a, G1Affine29 *pts_a, int32_t *kind_a, const uint8_t *in48_b, G1Affine29 *pts_b,
-                               int32_t *kind_b, size_t n, hipStream_t st, bool apart) {
-    ProfScope p("k_decompress_points", st);
-    hipLaunchKernelGGL(k_decompress_points, dim3((unsigned)((n + 63) / 64), 2), dim3(64), apart ? verify_pad_bytes(0, (const void *)k_decompress_points) : 0u, st,
-                       in48_a, pts_a, kind_a, in48_b, pts_b, kind_b, n);
-}
-
-// The subgroup test on a QUAD of lanes per point (tools/gen_subgroup_asm.py writes subgroup_asm.inc and explains it): doublings in three
-// rounds of one product per lane, the cooperative MSM kernel's addition, the public bits of |z| as a scalar loop. Workgroups of four
-// unrelated waves (one per SIMD of a compute unit), 16 points per wave.
-__global__ __launch_bounds__(256) void k_subgroup_coop_asm(const G1Affine29 *__restrict__ pts_a, const int32_t *__restrict__ kind_a,
-                                                           uint32_t *__restrict__ verdict_a, const G1Affine29 *__restrict__ pts_b,
-                                                           const int32_t *__restrict__ kind_b, uint32_t *__restrict__ verdict_b, uint32_t n) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const G1Affine29 *pts = blockIdx.y ? pts_b : pts_a;
-    const int32_t *kind = blockIdx.y ? kind_b : kind_a;
-    uint32_t *verdict = blockIdx.y ? verdict_b : verdict_a;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t first = (blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * 16;
-    __builtin_amdgcn_s_setprio(2);
-    asm volatile(
-#include "subgroup_asm.inc"
-        :
-        : "s"(pts), "s"(kind), "s"(verdict), "s"(n), "s"(first), "v"(lane)
-        :
-#include "subgroup_asm_clobbers.inc"
-    );
-#endif
-}
-
-void launch_subgroup_canon(G1Affine29 *pts, int32_t *kind, uint8_t *canon48, int32_t *status, int bad_code, size_t n,
-                           hipStream_t st, uint32_t *verdict_scratch, bool apart) {
-    const uint32_t *verdict = nullptr;
-    if (verdict_scratch && validate_coop_enabled()) {
-        ProfScope p("k_subgroup_coop_asm", st);
-        hipLaunchKernelGGL(k_subgroup_coop_asm, dim3((unsigned)((n + 63) / 64)), dim3(256), apart ? verify_pad_bytes(1, (const void *)k_subgroup_coop_asm) : 0u, st,
-                           pts, kind, verdict_scratch, pts, kind, verdict_scratch, (uint32_t)n);
-        verdict = verdict_scratch;
-    }
-    ProfScope p("k_subgroup_canon", st);
-    hipLaunchKernelGGL(k_subgroup_canon, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pts, kind, canon48, verdict, pts, kind, canon48, verdict,
-                       status, bad_code, n);
-}
-
-// both point sets of a verification in one launch each (the quad test, then canonical bytes and verdicts)
-void launch_subgroup_canon2(G1Affine29 *pts_a, int32_t *kind_a, uint8_t *canon48_a, uint32_t *verdict_a, G1Affine29 *pts_b, int32_t *kind_b,
-                            uint8_t *canon48_b, uint32_t *verdict_b, int32_t *status, int bad_code, size_t n, hipStream_t st, bool apart) {
-    {
-        ProfScope p("k_subgroup_coop_asm", st);
-        hipLaunchKernelGGL(k_subgroup_coop_asm, dim3((unsigned)((n + 63) / 64), 2), dim3(256), apart ? verify_pad_bytes(1, (const void *)k_subgroup_coop_asm) : 0u, st,
-                           pts_a, kind_a, verdict_a, pts_b, kind_b, verdict_b, (uint32_t)n);
-    }
-    ProfScope p("k_subgroup_canon", st);
-    hipLaunchKernelGGL(k_subgroup_canon, dim3((unsigned)((n + 63) / 64), 2), dim3(64), 0, st, pts_a, kind_a, canon48_a, verdict_a, pts_b, kind_b, canon48_b,
-                       verdict_b, status, bad_code, n);
 }
 
 }  // namespace lwk

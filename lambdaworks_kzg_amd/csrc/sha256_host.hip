@@ -6,7 +6,6 @@
 // the digests are computed here, one std::thread per slice of the batch, while the GPU validates the
 // commitments and parses the blobs; the device-resident entry points keep using k_challenge.
 #include <chrono>
-#include <atomic>
 #include <immintrin.h>
 #include <stdint.h>
 #include <string.h>
@@ -26,12 +25,7 @@
 
 namespace lwk {
 
-void sha256_host(uint8_t out[32], const uint8_t *msg, size_t len);  // portable, sha256.hip
-void sha256_blocks_portable(uint32_t h[8], const uint8_t *blocks, size_t n_blocks);  // portable compression of whole blocks, sha256.hip
-
-namespace {
-
-const uint32_t K256[64] = {
+static const uint32_t K256[64] = {
     0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
     0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
     0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
@@ -40,6 +34,41 @@ const uint32_t K256[64] = {
     0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
     0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
     0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+
+// the portable compression function: what a CPU without the SHA extensions hashes with
+static void sha256_block_host(uint32_t h[8], const uint8_t *b) {
+    auto ror = [](uint32_t x, int n) { return (x >> n) | (x << (32 - n)); };
+    uint32_t w[64];
+    for (int i = 0; i < 16; i++)
+        w[i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
+    for (int i = 16; i < 64; i++) {
+        uint32_t s0 = ror(w[i - 15], 7) ^ ror(w[i - 15], 18) ^ (w[i - 15] >> 3);
+        uint32_t s1 = ror(w[i - 2], 17) ^ ror(w[i - 2], 19) ^ (w[i - 2] >> 10);
+        w[i] = w[i - 16] + s0 + w[i - 7] + s1;
+    }
+    uint32_t a = h[0], bb = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+    for (int i = 0; i < 64; i++) {
+        uint32_t t1 = hh + (ror(e, 6) ^ ror(e, 11) ^ ror(e, 25)) + ((e & f) ^ (~e & g)) + K256[i] + w[i];
+        uint32_t t2 = (ror(a, 2) ^ ror(a, 13) ^ ror(a, 22)) + ((a & bb) ^ (a & c) ^ (bb & c));
+        hh = g; g = f; f = e; e = d + t1; d = c; c = bb; bb = a; a = t1 + t2;
+    }
+    h[0] += a; h[1] += bb; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+}
+
+static void sha256_blocks_portable(uint32_t h[8], const uint8_t *blocks, size_t n_blocks) {
+    for (size_t k = 0; k < n_blocks; k++) sha256_block_host(h, blocks + 64 * k);
+}
+
+static void digest_bytes(uint8_t out[32], const uint32_t h[8]) {   // the digest: big-endian h[0..8)
+    for (int k = 0; k < 8; k++) {
+        out[4 * k] = (uint8_t)(h[k] >> 24);
+        out[4 * k + 1] = (uint8_t)(h[k] >> 16);
+        out[4 * k + 2] = (uint8_t)(h[k] >> 8);
+        out[4 * k + 3] = (uint8_t)h[k];
+    }
+}
+
+namespace {
 
 // SHA extensions: state kept as (ABEF, CDGH), four rounds per _mm_sha256rnds2_epu32 pair
 __attribute__((target("sha,sse4.1,ssse3"))) void compress_shani(uint32_t state[8], const uint8_t *data, size_t nblocks) {
@@ -99,108 +128,75 @@ bool have_shani() {
     return v;
 }
 
+typedef void (*Compress)(uint32_t h[8], const uint8_t *blocks, size_t n_blocks);
+Compress best_compress() { return have_shani() ? compress_shani : sha256_blocks_portable; }   // the SHA extensions when the CPU has them
+
+const uint8_t kChallengeHeader[32] = {'F', 'S', 'B', 'L', 'O', 'B', 'V', 'E', 'R', 'I', 'F', 'Y', '_', 'V', '1', '_',
+                                      0x00, 0x10, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
 // digest of header(32) | blob(131072) | commitment(48), the compute_challenge message
 void challenge_digest(uint8_t out[32], const uint8_t *blob, const uint8_t *comm48) {
-    static const uint8_t header[32] = {'F', 'S', 'B', 'L', 'O', 'B', 'V', 'E', 'R', 'I', 'F', 'Y', '_', 'V', '1', '_',
-                                       0x00, 0x10, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (!have_shani()) {
-        std::vector<uint8_t> m(32 + kBlobBytes + 48);
-        memcpy(m.data(), header, 32);
-        memcpy(m.data() + 32, blob, kBlobBytes);
-        memcpy(m.data() + 32 + kBlobBytes, comm48, 48);
-        sha256_host(out, m.data(), m.size());
-        return;
-    }
+    const Compress compress = best_compress();
     uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
     uint8_t blk[64];
-    memcpy(blk, header, 32);
+    memcpy(blk, kChallengeHeader, 32);
     memcpy(blk + 32, blob, 32);
-    compress_shani(h, blk, 1);
-    compress_shani(h, blob + 32, (kBlobBytes - 64) / 64);       // 2047 whole blocks straight from the blob
+    compress(h, blk, 1);
+    compress(h, blob + 32, (kBlobBytes - 64) / 64);       // 2047 whole blocks straight from the blob
     memcpy(blk, blob + kBlobBytes - 32, 32);
     memcpy(blk + 32, comm48, 32);
-    compress_shani(h, blk, 1);
+    compress(h, blk, 1);
     memset(blk, 0, 64);
     memcpy(blk, comm48 + 32, 16);
     blk[16] = 0x80;
     const uint64_t bits = (uint64_t)(32 + kBlobBytes + 48) * 8;
     for (int k = 0; k < 8; k++) blk[63 - k] = (uint8_t)(bits >> (8 * k));
-    compress_shani(h, blk, 1);
-    for (int k = 0; k < 8; k++) {
-        out[4 * k] = (uint8_t)(h[k] >> 24);
-        out[4 * k + 1] = (uint8_t)(h[k] >> 16);
-        out[4 * k + 2] = (uint8_t)(h[k] >> 8);
-        out[4 * k + 3] = (uint8_t)h[k];
-    }
+    compress(h, blk, 1);
+    digest_bytes(out, h);
 }
 
-}  // namespace
-
-// SHA-256 of an arbitrary message with the SHA extensions when the CPU has them (the batch-level Fiat-Shamir hash of
-// verify_blob_kzg_proof_batch: 160 bytes per blob), the portable routine otherwise
-void sha256_fast(uint8_t out[32], const uint8_t *msg, size_t len) {
-    if (!have_shani()) {
-        sha256_host(out, msg, len);
-        return;
-    }
-    uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-    const size_t whole = len / 64;
-    compress_shani(h, msg, whole);
-    uint8_t tail[128];
-    memset(tail, 0, sizeof tail);
-    const size_t rem = len - 64 * whole;
-    memcpy(tail, msg + 64 * whole, rem);
-    tail[rem] = 0x80;
-    const size_t tl = rem + 9 <= 64 ? 64 : 128;
-    const uint64_t bits = (uint64_t)len * 8;
-    for (int k = 0; k < 8; k++) tail[tl - 1 - k] = (uint8_t)(bits >> (8 * k));
-    compress_shani(h, tail, tl / 64);
-    for (int k = 0; k < 8; k++) {
-        out[4 * k] = (uint8_t)(h[k] >> 24);
-        out[4 * k + 1] = (uint8_t)(h[k] >> 16);
-        out[4 * k + 2] = (uint8_t)(h[k] >> 8);
-        out[4 * k + 3] = (uint8_t)h[k];
-    }
-}
-
-// SHA-256 of prefix | msg without building the concatenation (the batch challenge: a 32-byte header in front of 160 bytes per blob that
-// already lie in one buffer, verify.hip); prefix_len < 64
-void sha256_fast_prefixed(uint8_t out[32], const uint8_t *prefix, size_t prefix_len, const uint8_t *msg, size_t len) {
-    if (!have_shani() || prefix_len >= 64) {
-        std::vector<uint8_t> m(prefix_len + len);
-        memcpy(m.data(), prefix, prefix_len);
-        if (len) memcpy(m.data() + prefix_len, msg, len);
-        sha256_fast(out, m.data(), m.size());
-        return;
-    }
+// SHA-256 of prefix | msg (prefix_len < 64) over a routine that compresses whole blocks, without building the concatenation
+void sha256_over(Compress compress, uint8_t out[32], const uint8_t *prefix, size_t prefix_len, const uint8_t *msg, size_t len) {
     uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
     uint8_t tail[192];
     memset(tail, 0, sizeof tail);
-    memcpy(tail, prefix, prefix_len);
+    if (prefix_len) memcpy(tail, prefix, prefix_len);
     size_t used = 0, fill = prefix_len;   // bytes of msg consumed; bytes in tail
     if (prefix_len + len >= 64) {
         used = 64 - prefix_len;
         memcpy(tail + prefix_len, msg, used);
-        compress_shani(h, tail, 1);
+        compress(h, tail, 1);
         const size_t whole = (len - used) / 64;
-        compress_shani(h, msg + used, whole);
+        compress(h, msg + used, whole);
         used += 64 * whole;
         memset(tail, 0, sizeof tail);
         fill = 0;
     }
-    memcpy(tail + fill, msg + used, len - used);
+    if (len > used) memcpy(tail + fill, msg + used, len - used);
     fill += len - used;
     tail[fill] = 0x80;
     const size_t tl = fill + 9 <= 64 ? 64 : 128;
     const uint64_t bits = (uint64_t)(prefix_len + len) * 8;
     for (int k = 0; k < 8; k++) tail[tl - 1 - k] = (uint8_t)(bits >> (8 * k));
-    compress_shani(h, tail, tl / 64);
-    for (int k = 0; k < 8; k++) {
-        out[4 * k] = (uint8_t)(h[k] >> 24);
-        out[4 * k + 1] = (uint8_t)(h[k] >> 16);
-        out[4 * k + 2] = (uint8_t)(h[k] >> 8);
-        out[4 * k + 3] = (uint8_t)h[k];
-    }
+    compress(h, tail, tl / 64);
+    digest_bytes(out, h);
+}
+
+}  // namespace
+
+// SHA-256 of an arbitrary message: portable, and with the SHA extensions when the CPU has them (the batch-level Fiat-Shamir hash of
+// verify_blob_kzg_proof_batch, compute_r_powers, /root/reference/src/utils.rs:166-206: 160 bytes per blob once per call, not worth a launch)
+void sha256_host(uint8_t out[32], const uint8_t *msg, size_t len) { sha256_over(sha256_blocks_portable, out, nullptr, 0, msg, len); }
+void sha256_fast(uint8_t out[32], const uint8_t *msg, size_t len) { sha256_over(best_compress(), out, nullptr, 0, msg, len); }
+
+// SHA-256 of prefix | msg without building the concatenation (the batch challenge: a 32-byte header in front of 160 bytes per blob that
+// already lie in one buffer, verify.hip)
+void sha256_fast_prefixed(uint8_t out[32], const uint8_t *prefix, size_t prefix_len, const uint8_t *msg, size_t len) {
+    if (prefix_len < 64) return sha256_over(best_compress(), out, prefix, prefix_len, msg, len);
+    std::vector<uint8_t> m(prefix_len + len);
+    memcpy(m.data(), prefix, prefix_len);
+    if (len) memcpy(m.data() + prefix_len, msg, len);
+    sha256_fast(out, m.data(), m.size());
 }
 
 // hardware threads this process may really use (shared with the host-side validation of verify.hip)
@@ -459,21 +455,15 @@ void host_pool_warm() {
 // the commitment (header | blob without its last 32 bytes): what k_challenge_pairs<true> leaves for k_challenge_finish (sha256.hip), computed
 // on the host threads for the one-pass commit-and-prove of mid-size batches (engine.hip)
 void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n) {
-    static const uint8_t header[32] = {'F', 'S', 'B', 'L', 'O', 'B', 'V', 'E', 'R', 'I', 'F', 'Y', '_', 'V', '1', '_',
-                                       0x00, 0x10, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const Compress compress = best_compress();
     host_parallel_for_grain(n, [=](size_t i) {
         const uint8_t *blob = blobs + (size_t)kBlobBytes * i;
         uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
         uint8_t blk[64];
-        memcpy(blk, header, 32);
+        memcpy(blk, kChallengeHeader, 32);
         memcpy(blk + 32, blob, 32);
-        if (have_shani()) {
-            compress_shani(h, blk, 1);
-            compress_shani(h, blob + 32, (kBlobBytes - 64) / 64);   // 2047 whole blocks straight from the blob
-        } else {
-            sha256_blocks_portable(h, blk, 1);
-            sha256_blocks_portable(h, blob + 32, (kBlobBytes - 64) / 64);
-        }
+        compress(h, blk, 1);
+        compress(h, blob + 32, (kBlobBytes - 64) / 64);   // 2047 whole blocks straight from the blob
         for (int k = 0; k < 8; k++) mid[8 * i + k] = h[k];
     }, host_hash_grain());
 }

@@ -29,9 +29,6 @@ namespace lwk {
 
 bool pairing_product_is_one(const G1Affine *ps, const Fp2 *qx, const Fp2 *qy, int n);
 bool pairing_check_compressed(const uint8_t *g1s, const uint8_t *g2s, int n, bool *ok);
-void sha256_host(uint8_t out[32], const uint8_t *msg, size_t len);
-void sha256_fast(uint8_t out[32], const uint8_t *msg, size_t len);  // sha256_host.hip: SHA extensions when present
-void sha256_fast_prefixed(uint8_t out[32], const uint8_t *prefix, size_t prefix_len, const uint8_t *msg, size_t len);
 unsigned host_threads();  // sha256_host.hip: hardware threads capped by the cgroup quota
 void host_parallel_for(size_t n, const std::function<void(size_t)> &fn);  // sha256_host.hip: persistent workers
 

@@ -128,7 +128,7 @@ static void launch_verify_rows(VerifyBuffers &vb, size_t n, hipStream_t st, bool
     if (knobs().verify_msm)
         launch_vmsm_multiples2(vb.pts_p, vb.kind_p, vb.tab_p, vb.pts_c, vb.kind_c, vb.tab_c, vb.vm_tmp, vb.vm_pre, n, st, apart);
     else
-        launch_point_multiples2(vb.pts_p, vb.kind_p, vb.mult_p, vb.pts_c, vb.kind_c, vb.mult_c, n, st);
+        launch_point_multiples(vb.pts_p, vb.kind_p, vb.mult_p, n, st, vb.pts_c, vb.kind_c, vb.mult_c);
 }
 
 // grow-only verify scratch for n blobs; the caller holds verify_mu
@@ -455,14 +455,15 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
             LWK_HIP(hipEventRecord(c->ev_fork, st));
             LWK_HIP(hipStreamWaitEvent(sa, c->ev_fork, 0));
             LWK_HIP(hipMemcpyAsync(vb.proof_in, proofs48, m * 48, hipMemcpyHostToDevice, sa));
-            launch_decompress_points(vb.proof_in, vb.pts_p, vb.kind_p, m, sa);
+            const PointSet set_p{vb.proof_in, vb.pts_p, vb.kind_p, w.out48, vb.verdict_p}, set_c{w.comm48, vb.pts_c, vb.kind_c, w.canon48, vb.verdict_c};
+            launch_decompress_points(set_p, nullptr, m, sa);
             LWK_HIP(hipEventRecord(c->ev_join[4], sa));
-            launch_subgroup_canon(vb.pts_p, vb.kind_p, w.out48, w.status, bad, m, sa, vb.verdict_p);
+            launch_subgroup_canon(set_p, nullptr, w.status, bad, m, sa);
             LWK_HIP(hipEventRecord(c->ev_join[0], sa));
             LWK_HIP(hipStreamWaitEvent(sc, c->ev_fork, 0));
-            launch_decompress_points(w.comm48, vb.pts_c, vb.kind_c, m, sc);
+            launch_decompress_points(set_c, nullptr, m, sc);
             LWK_HIP(hipEventRecord(c->ev_join[5], sc));
-            launch_subgroup_canon(vb.pts_c, vb.kind_c, w.canon48, w.status, bad, m, sc, vb.verdict_c);
+            launch_subgroup_canon(set_c, nullptr, w.status, bad, m, sc);
             LWK_HIP(hipEventRecord(c->ev_join[1], sc));
             LWK_HIP(hipStreamWaitEvent(sm, c->ev_join[4], 0));
             LWK_HIP(hipStreamWaitEvent(sm, c->ev_join[5], 0));
@@ -585,10 +586,10 @@ C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d
     const bool hash_first = fused ? (apart != (knobs().verify_order != 0)) : knobs().verify_order != 0;
     if (hash_first) launch_challenge(d_blobs, d_comm, z, le, n, st);
     if (fused) {   // r06: ONE launch per kernel over both point sets; the rows start as soon as the points are decompressed
-        launch_decompress_points2(d_proofs, vb.pts_p, vb.kind_p, d_comm, vb.pts_c, vb.kind_c, n, sv, apart);
+        const PointSet set_p{d_proofs, vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p}, set_c{d_comm, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c};
+        launch_decompress_points(set_p, &set_c, n, sv, apart);
         LWK_HIP(hipEventRecord(c->ev_join[2], sv));
-        launch_subgroup_canon2(vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c,
-                               vb.status_all, bad, n, sv, apart);
+        launch_subgroup_canon(set_p, &set_c, vb.status_all, bad, n, sv, apart);
         LWK_HIP(hipEventRecord(c->ev_join[0], sv));
         LWK_HIP(hipStreamWaitEvent(sc, c->ev_join[2], 0));
         launch_verify_rows(vb, n, sc, apart);
@@ -670,9 +671,9 @@ C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const ui
     if (rc != C_KZG_OK) return rc;
     verify_buffers_lend(vb, c->vs);
     LWK_HIP(hipMemsetAsync(vb.status_all, 0, n * 4, st));
-    launch_decompress_points2(d_proofs, vb.pts_p, vb.kind_p, d_comm, vb.pts_c, vb.kind_c, n, st);
-    launch_subgroup_canon2(vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c,
-                           vb.status_all, bad, n, st);
+    const PointSet set_p{d_proofs, vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p}, set_c{d_comm, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c};
+    launch_decompress_points(set_p, &set_c, n, st);
+    launch_subgroup_canon(set_p, &set_c, vb.status_all, bad, n, st);
     launch_each_openings(d_z, d_y, vb.d_rz, vb.d_r, vb.status_all, bad, le, n, st);
     LWK_HIP(hipGetLastError());
     return C_KZG_OK;

@@ -24,11 +24,10 @@
 #include <stdint.h>
 #include "kernels.h"
 #include "knobs.h"
+#include "lds_pad.h"
 #include "glv.cuh"
 
 namespace lwk {
-
-unsigned verify_pad_bytes(int which, const void *kernel);  // sha256.hip
 
 // rows of one point: row = half * 16 + j holds [2^(8 j)] of (half ? -phi(P) : P); table[row * n + i]
 static_assert(kVmsmRows == 32 && kVmsmSteps == 15, "two 128-bit halves of sixteen byte digits");
@@ -91,8 +90,11 @@ __global__ __launch_bounds__(256) void k_vmsm_multiples(const G1Affine29 *__rest
 void launch_vmsm_multiples2(const G1Affine29 *pts_a, const int32_t *kind_a, G1Affine29 *tab_a, const G1Affine29 *pts_b,
                             const int32_t *kind_b, G1Affine29 *tab_b, G1Xyzz29 *tmp, F29<2> *pre, size_t n, hipStream_t st, bool apart) {
     ProfScope p("k_vmsm_multiples", st);
-    hipLaunchKernelGGL(k_vmsm_multiples, dim3((unsigned)((n + 255) / 256), 2), dim3(256), apart ? verify_pad_bytes(2, (const void *)k_vmsm_multiples) : 0u, st,
-                       pts_a, kind_a, tab_a, pts_b, kind_b, tab_b, tmp, pre, (uint32_t)n);
+    static PadCache cache;
+    launch_padded(cache, (const void *)k_vmsm_multiples, apart ? knobs().verify_pad_kb[2] * 1024u : 0u, [&](unsigned lds) {
+        hipLaunchKernelGGL(k_vmsm_multiples, dim3((unsigned)((n + 255) / 256), 2), dim3(256), lds, st, pts_a, kind_a, tab_a, pts_b, kind_b, tab_b,
+                           tmp, pre, (uint32_t)n);
+    });
 }
 
 // ---- behind r: the scalars --------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """CPU: the C-ABI library loads, exports every symbol include/lambdaworks_kzg_amd.h declares, has the
 reference's struct layouts, and refuses to compute without a GPU (no CPU fallback)."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -308,6 +309,10 @@ def test_every_environment_knob_is_in_the_integration_table(K):
             assert "getenv(" not in open(os.path.join(src_dir, f)).read(), f
     read = set(re.findall(r'"(LWKZG_[A-Z_0-9]+)"', open(os.path.join(src_dir, "knobs.hip")).read().split("knob_names_operational()")[0]))
     rep = K.knob_report()
+    size = K.lib().lwkzg_knob_report(None, 0)      # the report's length with its terminator: what a caller allocates
+    buf = C.create_string_buffer(size)
+    assert K.lib().lwkzg_knob_report(buf, size) == size
+    assert len(buf.value) == size - 1 and json.loads(buf.value.decode()) == rep
     op, ex = set(rep["operational"].split()), set(rep["experimental_names"].split())
     assert not (op & ex) and op | ex == read, (sorted(read - (op | ex)), sorted((op | ex) - read))
     assert len(op) <= 20, len(op)

@@ -36,6 +36,47 @@ def test_all_arms_of_the_linear_combinations_agree(mode):
     assert sliced == shipped
 
 
+def _run_pads(**env):
+    e = dict(os.environ, LWKZG_EXPERIMENTAL="1", **env)
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "tests", "verify_pad_worker.py")], env=e).decode()
+    return json.loads(out.strip().splitlines()[-1])
+
+
+def test_oversized_lds_pads_are_clamped_and_change_no_answer():
+    """LWKZG_VERIFY_PAD_KB=150,150,150: 56 KiB of the decompression kernel's own LDS + 150 KiB is more than a workgroup can have, so the
+    padded launch (csrc/lds_pad.h) cuts the pad to what fits instead of launching something the runtime refuses -- validation must RUN.
+    65 blobs, device-resident (two workgroups per validation kernel, the second with one live lane / quad): honest triples verify; a
+    last proof outside G1 and a first commitment in a non-canonical encoding answer what the default pads answer, and what the per-item
+    verification of the same inputs implies (the first item's error code if an item has one, else the conjunction of the verdicts)."""
+    default = _run_pads()
+    padded = _run_pads(LWKZG_VERIFY_PAD_KB="150,150,150")
+    assert default["verify_pad_kb"] == [60, 116, 116] and padded["verify_pad_kb"] == [150, 150, 150]
+    assert padded["a"]["batch"] == [0, True]
+    for case in "abc":
+        each = default[case]["each"]
+        assert len(each) == 65 and padded[case]["each"] == each, case
+        codes = [rc for rc, _ in each if rc != 0]
+        want = [codes[0], False] if codes else [0, all(ok for _, ok in each)]
+        assert default[case]["batch"] == want, (case, default[case]["batch"], want)
+        assert padded[case]["batch"] == default[case]["batch"], case
+    assert default["b"]["each"][64][0] != 0 and all(e == [0, True] for e in default["b"]["each"][:64])     # the point outside G1 is what item 64 is rejected for
+    assert default["c"]["batch"] == [0, True]                                                                 # a valid encoding of the same point
+
+
+def test_default_lds_pads_fit_a_workgroup_unclamped(K):
+    """the padded launches (csrc/lds_pad.h) cut a pad to the device's LDS per workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock, which
+    torch reports as shared_memory_per_block) less the kernel's static LDS. At the default knobs nothing may be cut, or r06's placement
+    is gone without any answer changing: 57,344 B of k_decompress_points (its kernel descriptor) + 60 KiB, and 116 KiB beside the 0 B of
+    k_subgroup_coop_asm / k_vmsm_multiples / k_point_multiples, and 112 KiB beside the 0 B of k_validate_commitments, all fit"""
+    import torch
+    limit = torch.cuda.get_device_properties(torch.cuda.current_device()).shared_memory_per_block
+    d, s, m = K.knob_report()["verify_pad_kb"]
+    assert [d, s, m] == [60, 116, 116]
+    assert limit >= 57344 + d * 1024 == 57344 + 61440, limit
+    assert limit >= max(s, m) * 1024 == 118784, limit
+    assert limit >= 112 * 1024, limit
+
+
 def test_experiment_knobs_need_the_switch():
     """without LWKZG_EXPERIMENTAL=1 an experiment knob is ignored (knobs.h): the arm variable alone changes nothing, and the library says so"""
     e = dict(os.environ, LWKZG_VERIFY_MSM="0", LWKZG_VERBOSE="1")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generator (and wave-level simulator driver) of the cooperative G1 subgroup test: lambdaworks_kzg_amd/csrc/subgroup_asm.inc, the body of
-k_subgroup_coop_asm (sha256.hip). Shares the instruction IR, the product chains, the quad ADDITION and the wave simulator with
+k_subgroup_coop_asm (validate.hip). Shares the instruction IR, the product chains, the quad ADDITION and the wave simulator with
 tools/gen_coop_asm.py.
 
     python tools/gen_subgroup_asm.py            # writes csrc/subgroup_asm.inc (+ _clobbers.inc)
