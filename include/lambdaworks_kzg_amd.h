@@ -489,6 +489,36 @@ C_KZG_RET lwkzg_verify_cell_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_o
 C_KZG_RET lwkzg_cell_verify_each_points(uint8_t *out /* n x 97 */, const Bytes48 *commitments, const uint64_t *cell_indices,
                                         const Cell *cells, const Bytes48 *proofs, size_t n, const KZGSettings *s);
 
+/* The engine behind the cell proofs of lwkzg_compute_cells_and_kzg_proofs* and lwkzg_recover_cells_and_kzg_proofs* (DESIGN.md section 4h),
+ * a per-settings choice. FK20 (Feist-Khovratovich): the 128 proofs of a blob as a Toeplitz product over G1 -- 64 coefficient transforms,
+ * 128 MSMs of 64 terms over a per-settings window table of 8192 transformed bases, and two 128-point transforms over G1 -- instead of 128
+ * MSMs of 4096 terms. Same bytes, status words and return codes either way. The table: 8192 x 32 x 128 rows of 112 bytes, 3.5 GiB, at
+ * the default width of 8 bits (widths 4, 6, 7, 8, 9 are supported); with the call's scratch it stays below the 8 GiB that the MSM tables
+ * leave free. The transforms are a chain of thirteen dependent levels, so a call of few blobs is slower on FK20 than on the MSMs: */
+#define LWKZG_CELL_PROOFS_MSM  0   /* 128 MSMs of 4096 terms per blob: DESIGN.md section 4h, the default */
+#define LWKZG_CELL_PROOFS_FK20 1
+#define LWKZG_FK20_DEFAULT_MIN_BLOBS 64   /* the smallest measured n from which FK20's median stays below the MSM path's: 64, from
+                                          * profiles/fk20_timing.txt (tools/fk20_timing.py; 78.4 ms against 92.9 ms per call there, 87.1 against
+                                          * 47.6 at n = 32); DESIGN.md section 4h */
+/* engine FK20 builds the settings' FK20 table, then allocates everything an FK20 call needs. Calls allocate nothing afterwards.
+ * window_bits 0 = the library's default width. min_blobs 0 = the library's default threshold.
+ * A cell call (compute or recover) of fewer than min_blobs blobs keeps the MSM path.
+ * engine MSM frees the table and the scratch.
+ * C_KZG_MALLOC when the memory does not fit (or a transformed base is the point at infinity, which no real setup produces): the engine
+ * stays unchanged and usable.
+ * C_KZG_BADARGS for s NULL, an unknown engine or an unsupported width. Decided before any device work. */
+C_KZG_RET lwkzg_set_cell_proof_engine(const KZGSettings *s, int engine, int window_bits, size_t min_blobs);
+int    lwkzg_cell_proof_engine(const KZGSettings *s);   /* 0 / 1, -1 = bad settings */
+size_t lwkzg_fk20_table_bytes(const KZGSettings *s);    /* 0 = no table */
+size_t lwkzg_fk20_chunk_blobs(void);                    /* blobs per FK20 chunk: the tests cross it by one */
+/* Test hook, run by the proof call's own code path, host pointers.
+ * Per point: flag 1 (1 = infinity) | x 48 | y 48, big-endian, as lwkzg_cell_verify_partials writes them.
+ *   what 0: the 8192 bases, Y^_i[m] at index 128 i + m (blob ignored)
+ *   what 1: E[0..127] of the blob
+ *   what 2: h_0 .. h_63 of the blob
+ * C_KZG_ERROR when the settings' engine is not FK20. */
+C_KZG_RET lwkzg_fk20_points(uint8_t *out, int what, const Blob *blob, const KZGSettings *s);
+
 /* Host-only test hook for the per-item pairing: the 68 lines of the Miller loop of a ZCash-compressed G2 point (not at infinity) as the
  * device takes them, canonical big-endian lambda.c0 | lambda.c1 | c0.c0 | c0.c1 per line (out: 68 x 192 bytes). No GPU, no settings. */
 C_KZG_RET lwkzg_pairing_line_table(uint8_t *out, const uint8_t *g2_compressed);

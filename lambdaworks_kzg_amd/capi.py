@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_cell_batch_challenge_host",
     "lwkzg_verify_cell_kzg_proof_each", "lwkzg_verify_cell_kzg_proof_each_device", "lwkzg_cell_verify_each_points",
     "lwkzg_recover_cells_and_kzg_proofs", "lwkzg_recover_cells_and_kzg_proofs_batch", "lwkzg_recover_cells_and_kzg_proofs_batch_device",
+    "lwkzg_set_cell_proof_engine", "lwkzg_cell_proof_engine", "lwkzg_fk20_table_bytes", "lwkzg_fk20_chunk_blobs", "lwkzg_fk20_points",
 ]
 
 _lib = None
@@ -130,6 +131,13 @@ def lib():
     l.lwkzg_recover_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, sz, ps, C.POINTER(sz)]
     l.lwkzg_recover_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, pu64, vp, sz, sz, ps, vp, vp]
+    l.lwkzg_set_cell_proof_engine.argtypes = [ps, ci, ci, sz]
+    l.lwkzg_cell_proof_engine.argtypes = [ps]
+    l.lwkzg_fk20_table_bytes.argtypes = [ps]
+    l.lwkzg_fk20_table_bytes.restype = sz
+    l.lwkzg_fk20_chunk_blobs.argtypes = []
+    l.lwkzg_fk20_chunk_blobs.restype = sz
+    l.lwkzg_fk20_points.argtypes = [C.c_char_p, ci, C.c_char_p, ps]
     l.lwkzg_shard_range.argtypes = [sz, sz, sz, C.POINTER(sz), C.POINTER(sz)]
     pvp, psz = C.POINTER(vp), C.POINTER(sz)
     l.lwkzg_multi_blob_to_kzg_commitment_batch_device.argtypes = [pvp, pvp, psz, vp, psz]
@@ -345,6 +353,26 @@ class TrustedSetup:
     def direct_table_forms(self):
         """bit 0: a monomial-form direct table is live, bit 1: a Lagrange-form one (c-kzg commitments without the transform)"""
         return lib().lwkzg_direct_table_forms(self.ref())
+
+    def set_cell_proof_engine(self, engine, window_bits=0, min_blobs=0):
+        """The engine behind the cell proofs of the compute and recover calls: CELL_PROOFS_MSM (the default) or CELL_PROOFS_FK20, which
+        builds the settings' FK20 table (window_bits 0 = the default width) and serves calls of at least min_blobs blobs (0 = the
+        library's threshold); raises KzgError(C_KZG_MALLOC) if the table does not fit, the engine staying as it was."""
+        _check("lwkzg_set_cell_proof_engine", lib().lwkzg_set_cell_proof_engine(self.ref(), engine, window_bits, min_blobs))
+
+    def cell_proof_engine(self):
+        return lib().lwkzg_cell_proof_engine(self.ref())
+
+    def fk20_table_bytes(self):
+        return lib().lwkzg_fk20_table_bytes(self.ref())
+
+    def fk20_points(self, what, blob=None):
+        """test hook (lwkzg_fk20_points): what 0 = the 8192 bases, 1 = E[0..127] of the blob, 2 = h_0 .. h_63; a list of 97-byte
+        records flag | x | y"""
+        n = {0: 8192, 1: 128, 2: 64}[what]
+        out = C.create_string_buffer(n * FK20_POINT_BYTES)
+        _check("lwkzg_fk20_points", lib().lwkzg_fk20_points(out, what, blob, self.ref()))
+        return [out.raw[FK20_POINT_BYTES * i:FK20_POINT_BYTES * (i + 1)] for i in range(n)]
 
     def direct_row_bytes(self):
         """128 = table rows aligned to 128-byte lines, 112 = packed, 0 = bucket engine."""
@@ -703,6 +731,14 @@ def cell_verify_partials(commitments, cell_indices, cells, proofs, ts):
 
 
 CELL_EACH_POINT_BYTES = 97
+CELL_PROOFS_MSM, CELL_PROOFS_FK20 = 0, 1     # lwkzg_set_cell_proof_engine
+FK20_POINT_BYTES = 97
+FK20_DEFAULT_MIN_BLOBS = 64                   # LWKZG_FK20_DEFAULT_MIN_BLOBS: the measured crossing of profiles/fk20_timing.txt
+
+
+def fk20_chunk_blobs():
+    """blobs per chunk of the FK20 cell proof engine"""
+    return lib().lwkzg_fk20_chunk_blobs()
 
 
 def verify_cell_kzg_proof_each(commitments, cell_indices, cells, proofs, ts):

@@ -6,6 +6,8 @@
 //   extension   cells.hip: two forward transforms per blob through ws.fr and ws.scalars2, the cells written in the mode's byte order
 //   quotients   cells.hip: the 128 monomial quotients q_k of each blob straight into the scalar slots of ws.scalars2
 //   MSM         the engine's own launch set over 128 scalar sets per blob: 8 blobs fill its 1024 slots
+// With the settings' FK20 engine on (fk20_api.hip) and a call at or above its threshold, fk20_proofs replaces the last two steps and a
+// chunk is 512 blobs.
 // Everything behind the parse is cells_from_coefficients, which the recovery (recover_api.hip) shares.
 // The cells-only call (no proofs) takes chunks of 512 blobs: the two transforms per blob are what bounds it.
 #include "abi_guard.h"
@@ -17,11 +19,13 @@
 
 namespace lwk {
 
-void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st) {
+void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st, bool fk20) {
     Workspace &w = c->ws;
     const int le = mode == LWKZG_MODE_CKZG;
     if (cells) launch_cells_extend(w.scalars, c->tw_fwd, c->tw28_fwd, w.fr, (Fr *)w.scalars2, cells, le, m, st);
-    if (proofs48) {
+    if (proofs48 && fk20) {
+        (void)fk20_proofs(c, proofs48, m, st);   // (launches only without the hook's copy; behind the extension: both write ws.scalars2)
+    } else if (proofs48) {
         launch_cells_quotients(w.scalars, c->tw_fwd, w.scalars2, m * kProofsPerBlob, st);
         const bool lg = coefficients_to_msm_form(c, mode, m * kProofsPerBlob, st);
         msm_stages(c, w.scalars2, proofs48, m * kProofsPerBlob, st, 0, false, lg);
@@ -29,9 +33,11 @@ void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m
 }
 
 C_KZG_RET cells_chunks(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode, hipStream_t st, int32_t *status,
-                       const CoefficientStep &coefficients) {
-    const size_t chunk = proofs48 ? kProofChunk : kCellsChunk;
-    C_KZG_RET rc = ctx_reserve(c, (proofs48 ? kProofsPerBlob : 2) * min_sz(n, chunk));
+                       const CoefficientStep &coefficients, size_t n_call) {
+    const Fk20State &f = c->primary->fk20;   // (the caller holds this context's lock, under which the engine is switched)
+    const bool fk20 = proofs48 && f.engine == LWKZG_CELL_PROOFS_FK20 && n_call >= f.min_blobs;
+    const size_t chunk = fk20 ? kFk20ChunkBlobs : proofs48 ? kProofChunk : kCellsChunk;
+    C_KZG_RET rc = ctx_reserve(c, (proofs48 && !fk20 ? kProofsPerBlob : 2) * min_sz(n, chunk));
     if (rc != C_KZG_OK) return rc;
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = min_sz(chunk, n - off);
@@ -39,7 +45,7 @@ C_KZG_RET cells_chunks(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, size_t n, 
         LWK_HIP(hipMemsetAsync(stt, 0, m * 4, st));
         coefficients(off, m, stt);
         cells_from_coefficients(c, cells_out ? cells_out + off * kBlobCellBytes : nullptr, proofs48 ? proofs48 + 48 * kProofsPerBlob * off : nullptr,
-                                m, mode, st);
+                                m, mode, st, fk20);
     }
     LWK_HIP(hipGetLastError());
     return C_KZG_OK;
@@ -95,12 +101,13 @@ C_KZG_RET cells_host_slices(Ctx *c, const uint8_t *in, size_t in_bytes_per_blob,
 namespace {
 
 // the device pipeline on st (caller holds the context's lock and the workspace); status: n words, 0 or the mode's rejection code
-C_KZG_RET cells_device(Ctx *c, uint8_t *cells, uint8_t *proofs48, const uint8_t *blobs, size_t n, int mode, hipStream_t st, int32_t *status) {
+C_KZG_RET cells_device(Ctx *c, uint8_t *cells, uint8_t *proofs48, const uint8_t *blobs, size_t n, int mode, hipStream_t st, int32_t *status,
+                       size_t n_call) {
     return cells_chunks(c, cells, proofs48, n, mode, st, status, [&](size_t off, size_t m, int32_t *stt) {
         const uint8_t *b = blobs + off * (size_t)kBlobBytes;
         if (mode == LWKZG_MODE_REFERENCE) launch_parse_be_reduce(b, c->ws.scalars, m * kBlobElems, st);
         else launch_blob_evaluations_to_coefficients(b, c->ws.scalars, c->tw28_inv, stt, m, st);
-    });
+    }, n_call);
 }
 
 C_KZG_RET cells_batch_impl(Cell *cells, KZGProof *proofs, const Blob *blobs, size_t n, const KZGSettings *s, size_t *first_bad) {
@@ -117,7 +124,7 @@ C_KZG_RET cells_batch_impl(Cell *cells, KZGProof *proofs, const Blob *blobs, siz
     return cells_host_slices(c, (const uint8_t *)blobs, kBlobBytes, (uint8_t *)cells, (uint8_t *)proofs, n, mode, first_bad,
                              "compute_cells_and_kzg_proofs: no device memory for %zu bytes of staging", "blob %zu rejected (status %d)",
                              [&](uint8_t *d_cells, uint8_t *d_proofs, const uint8_t *d_blobs, size_t m, hipStream_t st, int32_t *d_status) {
-                                 return cells_device(c, d_cells, d_proofs, d_blobs, m, mode, st, d_status);
+                                 return cells_device(c, d_cells, d_proofs, d_blobs, m, mode, st, d_status, n);
                              });
 }
 
@@ -155,7 +162,7 @@ C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch_device(void *cells_dev, void 
         LWK_HIP(hipSetDevice(c->device));
         hipStream_t st = stream ? (hipStream_t)stream : c->stream;
         WsUse wsu(c, st);
-        return cells_device(c, (uint8_t *)cells_dev, (uint8_t *)proofs48_dev, (const uint8_t *)blobs_dev, n, mode, st, status_dev);
+        return cells_device(c, (uint8_t *)cells_dev, (uint8_t *)proofs48_dev, (const uint8_t *)blobs_dev, n, mode, st, status_dev, n);
     });
 }
 

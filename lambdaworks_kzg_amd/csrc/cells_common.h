@@ -19,10 +19,12 @@ inline C_KZG_RET bad_input(int mode) { return mode == LWKZG_MODE_CKZG ? C_KZG_BA
 
 // The device pipeline of n blobs on st, a chunk at a time (8 blobs with proofs, 512 without); the caller holds the context's lock and the
 // workspace. coefficients(off, m, stt) enqueues the step that leaves the coefficients of blobs off .. off + m in ws.scalars and a
-// rejection code in stt[0 .. m) (cleared before). status: n words, 0 or the mode's rejection code; nullptr: ws.status takes them
+// rejection code in stt[0 .. m) (cleared before). status: n words, 0 or the mode's rejection code; nullptr: ws.status takes them.
+// n_call: the blobs of the whole call this is a part of (a host-pointer call comes in slices): with the settings' FK20 engine on and
+// n_call at or above its threshold the proofs take that engine, in chunks of kFk20ChunkBlobs
 typedef std::function<void(size_t off, size_t m, int32_t *stt)> CoefficientStep;
 C_KZG_RET cells_chunks(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode, hipStream_t st, int32_t *status,
-                       const CoefficientStep &coefficients);
+                       const CoefficientStep &coefficients, size_t n_call);
 
 // Host pointers: slices of up to kHostSlice blobs (in_bytes_per_blob each) go up, through run (the device pipeline of m blobs) and back;
 // the outputs are written only when every blob is good. no_memory takes the staging's byte count, rejected the first bad blob's index

@@ -235,6 +235,32 @@ struct LagrangeForm {
     size_t direct_row_bytes = 0;
 };
 
+// The FK20 cell proof engine of a settings object (fk20_api.hip): the window table over the 8192 transformed bases
+// and everything a call needs beside the workspace, allocated when the engine is switched on and freed when it is switched off. Owned
+// by the primary context; a twin holds copies of the pointers (sync_twin_tables). Written under the context's locks, both of them.
+struct Fk20State {
+    int engine = LWKZG_CELL_PROOFS_MSM;
+    int bits = 0;                     // window width of the table
+    size_t min_blobs = 0;             // calls of fewer blobs keep the MSM path
+    G1Affine29 *table = nullptr;      // fk20.cuh: fk20_row
+    size_t table_bytes = 0;
+    G1Affine *bases = nullptr;        // Y^_i[m] at 128 i + m (the test hook reads them)
+    uint8_t *roots = nullptr;         // the recoded roots of the G1 transforms
+    G1Xyzz29 *pts = nullptr;          // kFk20ChunkBlobs x 128: E, then the proof points, of a chunk. One buffer per settings object,
+                                      // ordered by the primary context's WsUse alone: cell calls always run on the primary (ctx_of,
+                                      // never pick_ctx), so the twin's copy of these pointers is not launched against today. A change
+                                      // that routes cell calls to the twin must give it pts (and hook_pts) of its own first: WsUse
+                                      // orders one context's workspace, not a buffer that two contexts share.
+    G1Xyzz29 *hook_pts = nullptr;     // 128 + 64 points, 128 x 96 bytes and 128 words behind them: the test hook's copies
+};
+struct Ctx;
+constexpr size_t kFk20ChunkBlobs = 512;   // blobs per FK20 chunk: their 256 KiB of MSM scalars each fill the 1024 slots of ws.scalars2
+void fk20_free(Ctx *c);
+// the proofs of the m blobs whose coefficients are in ws.scalars (m <= kFk20ChunkBlobs, workspace reserved for 2 m slots), on st;
+// e_copy (128 points) / h_out (64 per blob): the intermediate points of the test hook. Returns the status of the hook's copy of E
+// (hipSuccess without e_copy: launches only)
+hipError_t fk20_proofs(Ctx *c, uint8_t *proofs48, size_t m, hipStream_t st, G1Xyzz29 *e_copy = nullptr, G1Xyzz29 *h_out = nullptr);
+
 // A device buffer that a settings object keeps and that only grows: no allocation in steady state. cap counts what its user counts
 // (blobs, items). grow_reserve (engine.hip; caller holds the context's lock): big enough -> C_KZG_OK at once; else every stream of the
 // device is waited for (work on any of them may still be using the old block), the block is freed and one of first_cap, doubled until it
@@ -329,6 +355,7 @@ struct Ctx {
     hipEvent_t cellv_ev = nullptr; // the digests and status words have landed
     void *celleach_lines = nullptr;   // cells_verify_each.hip: the line tables of g2_values[0] and [64] on the device, made on first use; under mu
     GrowBuf celleach;                 // cells_verify_each.hip: everything a per-item cell verification keeps on the device, one allocation carved up (cap in items; under mu)
+    Fk20State fk20;                // fk20_api.hip: the opt-in FK20 cell proof engine (the primary's; a twin's is a copy of the pointers)
     Fr *recover_tab = nullptr;     // recover_api.hip: the table k_recover_setup leaves for the call's other kernels (kRecoverTabElems, with the context)
     VerifyBuffers vs;   // verify-side scratch, sized for vs_cap blobs
     size_t vs_cap;
@@ -377,8 +404,9 @@ bool coefficients_to_msm_form(Ctx *c, int mode, size_t n, hipStream_t st, size_t
 
 // the cells pipeline behind the parse (cells_api.hip): the canonical coefficients of m blobs in ws.scalars (slots 0 ..) -> their 128 cells
 // each (cells: m x 256 KiB, or nullptr) and 128 proofs each (proofs48: m x 128 x 48 bytes, or nullptr: no MSM runs). m is at most one
-// chunk (8 blobs with proofs, 512 without) and the caller has reserved the workspace for it (128 m slots with proofs, 2 m without)
-void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st);
+// chunk (8 blobs with proofs, 512 without) and the caller has reserved the workspace for it (128 m slots with proofs, 2 m without).
+// fk20: the proofs come from the FK20 engine instead (a chunk of up to kFk20ChunkBlobs blobs, 2 m slots)
+void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st, bool fk20 = false);
 
 // device-resident pipelines; all pointers device, async on st
 C_KZG_RET commit_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, size_t n, int mode, hipStream_t st,

@@ -452,6 +452,7 @@ void ctx_destroy(Ctx *c) {
         c->direct_table = nullptr;
         c->direct_tab = DirectTable();
         c->lag = LagrangeForm();
+        c->fk20 = Fk20State();
         c->tw_fwd = c->tw_inv = nullptr;
         c->tw28_fwd = c->tw28_inv = nullptr;
     }
@@ -489,6 +490,7 @@ void ctx_destroy(Ctx *c) {
     dev_free(c->celleach_lines);
     grow_free(c->celleach);
     dev_free(c->recover_tab);
+    fk20_free(c);
     if (c->cellv_pin) hipHostFree(c->cellv_pin);
     if (c->cellv_ev) hipEventDestroy(c->cellv_ev);
     if (c->prio_copy) hipStreamDestroy(c->prio_copy);
@@ -576,6 +578,7 @@ C_KZG_RET ctx_new(Ctx **out, const Ctx *twin_of) {
         c->lag = twin_of->lag;
         c->lag.direct_tab = DirectTable();
         c->lag.direct_tab.win_dev = twin_of->lag.direct_tab.win_dev;  // (addresses only)
+        c->fk20 = twin_of->fk20;
         c->tw_fwd = twin_of->tw_fwd;
         c->tw_inv = twin_of->tw_inv;
         c->tw28_fwd = twin_of->tw28_fwd;

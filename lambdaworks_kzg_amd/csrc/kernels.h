@@ -232,6 +232,20 @@ void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr2
 // scalar set (blob * 128 + k), zero-padded to 4096
 void launch_cells_quotients(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, size_t n_cells, hipStream_t st);
 
+// ---- the FK20 cell proof engine (fk20.hip, pieces in fk20.cuh)
+// rows first .. first + n_rows of the 8192 scalar rows whose commitments over the monomial setup are the transformed bases (row 128 i + m:
+// Y^_i[m]); roots_raw: w128^e, e < 128, canonical limbs
+void launch_fk20_base_rows(uint32_t *rows_raw, const uint32_t *roots_raw, uint32_t first, size_t n_rows, hipStream_t st);
+// the window table of `bits` (fk20.cuh: fk20_plan, fk20_row) over the 8192 bases, none of them at infinity
+void launch_fk20_table(const G1Affine *bases, G1Affine29 *table, int bits, hipStream_t st);
+// canonical coefficients of n_blobs blobs -> the 64 coefficient transforms A^_i of each as canonical MSM scalars [blob][m][i] (256 KiB per blob)
+void launch_fk20_coeffs(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *scalars_out, size_t n_blobs, hipStream_t st);
+// E[m] = sum_i A^_i[m] Y^_i[m] of every blob, at e_out[128 blob + rev7(m)]
+void launch_fk20_msm(const G1Affine29 *table, int bits, const uint32_t *scalars, G1Xyzz29 *e_out, size_t n_blobs, hipStream_t st);
+// pts[128 blob ..]: E in bit-reversed positions -> the blob's 128 proof points in proof order; roots: the recoded roots (fk20.cuh);
+// h_out (optional): h_0 .. h_63 of every blob
+void launch_fk20_transforms(G1Xyzz29 *pts, const uint8_t *roots, G1Xyzz29 *h_out, size_t n_blobs, hipStream_t st);
+
 // ---- EIP-7594 recovery (recover.hip)
 // the index set of a recovery call, passed to its kernels by value: k[i] = the index of the i-th given cell (ascending), and bit q of
 // `given` = the cell at position q = bitrev7(k), whose c_k is w128^q, is among them

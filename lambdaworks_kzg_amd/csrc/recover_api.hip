@@ -55,13 +55,13 @@ bool check_arguments(RecoverSet &set, const void *out_cells, const void *out_pro
 
 // the device pipeline on st (caller holds the context's lock and the workspace); status: n words, 0 or the mode's rejection code
 C_KZG_RET recover_device(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, const RecoverSet &set, const uint8_t *cells_in, size_t num_cells,
-                         size_t n, int mode, hipStream_t st, int32_t *status) {
+                         size_t n, int mode, hipStream_t st, int32_t *status, size_t n_call) {
     const int le = mode == LWKZG_MODE_CKZG, bad = (int)bad_input(mode);
     launch_recover_setup(set, c->tw_fwd, c->recover_tab, st);
     return cells_chunks(c, cells_out, proofs48, n, mode, st, status, [&](size_t off, size_t m, int32_t *stt) {
         launch_recover_coefficients(cells_in + off * num_cells * kCellBytes, set, num_cells, c->tw_fwd, c->tw_inv, c->recover_tab,
                                     (Fr *)c->ws.scalars2, c->ws.scalars, stt, bad, le, m, st);
-    });
+    }, n_call);
 }
 
 C_KZG_RET recover_batch_impl(Cell *cells_out, KZGProof *proofs, const uint64_t *idx, const Cell *cells, size_t num_cells, size_t n,
@@ -78,7 +78,7 @@ C_KZG_RET recover_batch_impl(Cell *cells_out, KZGProof *proofs, const uint64_t *
                              "recover_cells_and_kzg_proofs: no device memory for %zu bytes of staging",
                              "recover_cells_and_kzg_proofs: blob %zu rejected: a cell element is not below r, or its cells are inconsistent",
                              [&](uint8_t *d_cells, uint8_t *d_proofs, const uint8_t *d_in, size_t m, hipStream_t st, int32_t *d_status) {
-                                 return recover_device(c, d_cells, d_proofs, set, d_in, num_cells, m, mode, st, d_status);
+                                 return recover_device(c, d_cells, d_proofs, set, d_in, num_cells, m, mode, st, d_status, n);
                              });
 }
 
@@ -120,7 +120,7 @@ C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_batch_device(void *recovered_cells_
         hipStream_t st = stream ? (hipStream_t)stream : c->stream;
         WsUse wsu(c, st);
         return recover_device(c, (uint8_t *)recovered_cells_dev, (uint8_t *)recovered_proofs48_dev, set, (const uint8_t *)cells_dev, num_cells, n,
-                              mode, st, status_dev);
+                              mode, st, status_dev, n);
     });
 }
 

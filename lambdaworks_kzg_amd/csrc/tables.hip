@@ -32,6 +32,7 @@ static void sync_twin_tables(Ctx *c) {
     t->lag.direct_tab = DirectTable();
     t->lag.direct_tab.win_dev = c->lag.direct_tab.win_dev;
     t->lag_ready.store(c->lag.ready, std::memory_order_release);
+    t->fk20 = c->fk20;   // (the FK20 engine's table and scratch: fk20_api.hip)
 }
 
 struct FormRef {  // one form's direct-table fields
