@@ -425,6 +425,33 @@ C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_batch_device(void *recovered_cells_
                                                           const uint64_t *cell_indices, const void *cells_dev, size_t num_cells, size_t n,
                                                           const KZGSettings *s, void *stream, int32_t *status_dev);
 
+/* n blobs, each seen through an index set of its OWN (the rows of several blocks, each block through the columns that reached the node: a
+ * node catching up, a backfill, a supernode reconstructing for its peers). num_cells[b] is blob b's count, 64 .. 128; cell_indices
+ * holds the blobs' index lists one after the other and cells their cells in the same order, num_cells[0] + .. + num_cells[n - 1] entries
+ * each; outputs n x 128 each, either may be NULL (proofs NULL: no MSM runs). For every blob b the outputs and its contribution to the
+ * return code are byte for byte those of lwkzg_recover_cells_and_kzg_proofs on (its list, its cells, num_cells[b]) alone, in the mode
+ * the settings answer in and on every cell proof engine; the FK20 threshold counts this call's n. Lists that name the same cells share
+ * one table on the device, so n blobs of a few blocks cost a few tables. DESIGN.md section 4j.
+ * C_KZG_BADARGS in both modes, decided before any device work: s NULL; with n > 0 cell_indices, cells or num_cells NULL; both outputs
+ * NULL; a count outside 64 .. 128; an index of 128 or more; a list not strictly ascending -- where one blob's list is at fault,
+ * first_bad (if given) gets that blob's index. A bad blob (an element not below r, inconsistent cells) fails the call with the mode's
+ * code (first_bad, if given, gets its index) and nothing is written. n == 0: C_KZG_OK, nothing written, whatever the other pointers
+ * are. Synchronous. */
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_mixed(Cell *recovered_cells, KZGProof *recovered_proofs, const uint64_t *cell_indices,
+                                                   const Cell *cells, const size_t *num_cells, size_t n, const KZGSettings *s,
+                                                   size_t *first_bad);
+/* cells_dev / outputs are DEVICE pointers (16-byte aligned), cell_indices and num_cells stay HOST arrays (read before the call returns);
+ * asynchronous on `stream` (NULL = the context's own); status_dev optional, one word per blob: 0 or the mode's code for a bad input; a
+ * good blob's outputs are correct whatever its neighbours' status. Calls that follow each other on one stream need no synchronisation
+ * between them: the sets reach the kernels as launch arguments and through a device block that only kernels of the call write, in
+ * stream order. That block belongs to the settings object and only grows: a call with more DISTINCT sets than any mixed call on these
+ * settings before it (the first 64 come with the first call) waits for the device, frees the block and allocates one of twice the
+ * size, about 16 KiB per set; up to that count no later call allocates or synchronises, once lwkzg_reserve has covered the batch as for
+ * lwkzg_recover_cells_and_kzg_proofs_batch_device. */
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_mixed_device(void *recovered_cells_dev, void *recovered_proofs48_dev,
+                                                          const uint64_t *cell_indices, const void *cells_dev, const size_t *num_cells,
+                                                          size_t n, const KZGSettings *s, void *stream, int32_t *status_dev);
+
 /* EIP-7594 verify_cell_kzg_proof_batch: do the n items (commitments[i], cell_indices[i], cells[i], proofs[i]) belong together?
  * c-kzg-4844 2.x's argument order; the same commitment may appear many times and an item may repeat. cells are in the settings' mode's
  * byte order, as lwkzg_compute_cells_and_kzg_proofs writes them. DESIGN.md section 4i has the definition: commitments de-duplicated by

@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_cell_batch_challenge_host",
     "lwkzg_verify_cell_kzg_proof_each", "lwkzg_verify_cell_kzg_proof_each_device", "lwkzg_cell_verify_each_points",
     "lwkzg_recover_cells_and_kzg_proofs", "lwkzg_recover_cells_and_kzg_proofs_batch", "lwkzg_recover_cells_and_kzg_proofs_batch_device",
+    "lwkzg_recover_cells_and_kzg_proofs_mixed", "lwkzg_recover_cells_and_kzg_proofs_mixed_device",
     "lwkzg_set_cell_proof_engine", "lwkzg_cell_proof_engine", "lwkzg_fk20_table_bytes", "lwkzg_fk20_chunk_blobs", "lwkzg_fk20_points",
 ]
 
@@ -131,6 +132,8 @@ def lib():
     l.lwkzg_recover_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, sz, ps, C.POINTER(sz)]
     l.lwkzg_recover_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, pu64, vp, sz, sz, ps, vp, vp]
+    l.lwkzg_recover_cells_and_kzg_proofs_mixed.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.POINTER(sz), sz, ps, C.POINTER(sz)]
+    l.lwkzg_recover_cells_and_kzg_proofs_mixed_device.argtypes = [vp, vp, pu64, vp, C.POINTER(sz), sz, ps, vp, vp]
     l.lwkzg_set_cell_proof_engine.argtypes = [ps, ci, ci, sz]
     l.lwkzg_cell_proof_engine.argtypes = [ps]
     l.lwkzg_fk20_table_bytes.argtypes = [ps]
@@ -687,6 +690,39 @@ def recover_cells_and_kzg_proofs_batch_device(cells_out_ptr, proofs_ptr, cell_in
     idx = (C.c_uint64 * max(num, 1))(*cell_indices)
     _check("lwkzg_recover_cells_and_kzg_proofs_batch_device",
            lib().lwkzg_recover_cells_and_kzg_proofs_batch_device(cells_out_ptr, proofs_ptr, idx, cells_ptr, num, n, ts.ref(), stream, status_ptr))
+
+
+def _mixed_lists(index_lists):
+    """one index list per blob -> the lists one after the other and the counts, as C arrays"""
+    flat = [k for lst in index_lists for k in lst]
+    return (C.c_uint64 * max(len(flat), 1))(*flat), (C.c_size_t * max(len(index_lists), 1))(*[len(lst) for lst in index_lists]), len(flat)
+
+
+def recover_cells_and_kzg_proofs_mixed(index_lists, cells_per_blob, ts, cells_out=True, proofs=True):
+    """n blobs, each through an index set of its own, in one call (lwkzg_recover_cells_and_kzg_proofs_mixed): index_lists[b] is blob b's
+    list of 64 .. 128 ascending indices and cells_per_blob[b] its cells (a list of cells or their concatenation), one per index. A list
+    of (cells, proofs) per blob, each what recover_cells_and_kzg_proofs gives for that blob alone."""
+    n = len(index_lists)
+    idx, num, total = _mixed_lists(index_lists)
+    ce = b"".join(c if isinstance(c, (bytes, bytearray)) else b"".join(c) for c in cells_per_blob)
+    if len(cells_per_blob) != n or len(ce) != total * BYTES_PER_CELL:
+        raise ValueError("cells_per_blob must hold one cell per index of every blob")
+    cb = C.create_string_buffer(max(n, 1) * CELLS_PER_EXT_BLOB * BYTES_PER_CELL) if cells_out else None
+    pb = C.create_string_buffer(max(n, 1) * CELLS_PER_EXT_BLOB * 48) if proofs else None
+    bad = C.c_size_t(0)
+    _check("lwkzg_recover_cells_and_kzg_proofs_mixed",
+           lib().lwkzg_recover_cells_and_kzg_proofs_mixed(cb, pb, idx, bytes(ce), num, n, ts.ref(), C.byref(bad)))
+    return _cells_split(cb.raw if cells_out else None, pb.raw if proofs else None, n)
+
+
+def recover_cells_and_kzg_proofs_mixed_device(cells_out_ptr, proofs_ptr, index_lists, cells_ptr, ts, stream=None, status_ptr=None):
+    """cells (n x 128 x 2048 bytes) and proofs (n x 128 x 48 bytes) of the n = len(index_lists) blobs from their device-resident cells
+    (the blobs' cells one after the other, blob b's in the order of index_lists[b]; the lists stay on the host), asynchronous on `stream`;
+    either output pointer may be None"""
+    idx, num, _ = _mixed_lists(index_lists)
+    _check("lwkzg_recover_cells_and_kzg_proofs_mixed_device",
+           lib().lwkzg_recover_cells_and_kzg_proofs_mixed_device(cells_out_ptr, proofs_ptr, idx, cells_ptr, num, len(index_lists), ts.ref(),
+                                                                 stream, status_ptr))
 
 
 CELL_VERIFY_PARTIAL_BYTES = 32 + 4 * 97

@@ -53,8 +53,22 @@ C_KZG_RET cells_chunks(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, size_t n, 
 
 C_KZG_RET cells_host_slices(Ctx *c, const uint8_t *in, size_t in_bytes_per_blob, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode,
                             size_t *first_bad, const char *no_memory, const char *rejected, const SliceRun &run) {
+    std::vector<size_t> in_end(n + 1);
+    for (size_t b = 0; b <= n; b++) in_end[b] = b * in_bytes_per_blob;
+    return cells_host_slices_ragged(c, in, in_end.data(), cells_out, proofs48, n, mode, first_bad, no_memory, rejected,
+                                    [&](uint8_t *d_cells, uint8_t *d_proofs, const uint8_t *d_in, size_t, size_t m, hipStream_t st,
+                                        int32_t *d_status) { return run(d_cells, d_proofs, d_in, m, st, d_status); });
+}
+
+C_KZG_RET cells_host_slices_ragged(Ctx *c, const uint8_t *in, const size_t *in_end, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode,
+                                   size_t *first_bad, const char *no_memory, const char *rejected, const SliceRunAt &run) {
     const size_t slice = min_sz(n, kHostSlice);
-    const size_t in_bytes = slice * in_bytes_per_blob;
+    size_t in_bytes = 0;   // of the largest slice
+    for (size_t off = 0; off < n; off += slice) {
+        const size_t b = in_end[min_sz(off + slice, n)] - in_end[off];
+        if (b > in_bytes) in_bytes = b;
+    }
+    in_bytes = (in_bytes + 15) & ~(size_t)15;   // (what follows the input in the block stays 16-byte aligned)
     const size_t cell_bytes = cells_out ? slice * kBlobCellBytes : 0, proof_bytes = proofs48 ? slice * kProofsPerBlob * 48 : 0;
     const size_t total = in_bytes + cell_bytes + proof_bytes + slice * 4;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -77,8 +91,8 @@ C_KZG_RET cells_host_slices(Ctx *c, const uint8_t *in, size_t in_bytes_per_blob,
         WsUse wsu(c, st);
         for (size_t off = 0; off < n; off += slice) {
             const size_t m = min_sz(slice, n - off);
-            LWK_HIP(hipMemcpyAsync(d_in, in + off * in_bytes_per_blob, m * in_bytes_per_blob, hipMemcpyHostToDevice, st));
-            C_KZG_RET rc = run(d_cells, d_proofs, d_in, m, st, d_status);
+            LWK_HIP(hipMemcpyAsync(d_in, in + in_end[off], in_end[off + m] - in_end[off], hipMemcpyHostToDevice, st));
+            C_KZG_RET rc = run(d_cells, d_proofs, d_in, off, m, st, d_status);
             if (rc != C_KZG_OK) return rc;
             LWK_HIP(hipMemcpyAsync(h_status.data() + off, d_status, m * 4, hipMemcpyDeviceToHost, st));
             if (cells_out) LWK_HIP(hipMemcpyAsync(h_cells.data() + off * kBlobCellBytes, d_cells, m * kBlobCellBytes, hipMemcpyDeviceToHost, st));

@@ -26,9 +26,14 @@ typedef std::function<void(size_t off, size_t m, int32_t *stt)> CoefficientStep;
 C_KZG_RET cells_chunks(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode, hipStream_t st, int32_t *status,
                        const CoefficientStep &coefficients, size_t n_call);
 
-// Host pointers: slices of up to kHostSlice blobs (in_bytes_per_blob each) go up, through run (the device pipeline of m blobs) and back;
-// the outputs are written only when every blob is good. no_memory takes the staging's byte count, rejected the first bad blob's index
-// and status word
+// Host pointers: slices of up to kHostSlice blobs go up, through run (the device pipeline of the m blobs from blob off on) and back; the
+// outputs are written only when every blob is good. in_end (n + 1 entries): blob b's input is bytes in_end[b] .. in_end[b + 1] of `in`,
+// so a slice's upload may be ragged. no_memory takes the staging's byte count, rejected the first bad blob's index and status word
+typedef std::function<C_KZG_RET(uint8_t *d_cells, uint8_t *d_proofs, const uint8_t *d_in, size_t off, size_t m, hipStream_t st, int32_t *d_status)>
+    SliceRunAt;
+C_KZG_RET cells_host_slices_ragged(Ctx *c, const uint8_t *in, const size_t *in_end, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode,
+                                   size_t *first_bad, const char *no_memory, const char *rejected, const SliceRunAt &run);
+// the same with in_bytes_per_blob input bytes for every blob
 typedef std::function<C_KZG_RET(uint8_t *d_cells, uint8_t *d_proofs, const uint8_t *d_in, size_t m, hipStream_t st, int32_t *d_status)> SliceRun;
 C_KZG_RET cells_host_slices(Ctx *c, const uint8_t *in, size_t in_bytes_per_blob, uint8_t *cells_out, uint8_t *proofs48, size_t n, int mode,
                             size_t *first_bad, const char *no_memory, const char *rejected, const SliceRun &run);

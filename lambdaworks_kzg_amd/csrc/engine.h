@@ -357,6 +357,7 @@ struct Ctx {
     GrowBuf celleach;                 // cells_verify_each.hip: everything a per-item cell verification keeps on the device, one allocation carved up (cap in items; under mu)
     Fk20State fk20;                // fk20_api.hip: the opt-in FK20 cell proof engine (the primary's; a twin's is a copy of the pointers)
     Fr *recover_tab = nullptr;     // recover_api.hip: the table k_recover_setup leaves for the call's other kernels (kRecoverTabElems, with the context)
+    GrowBuf recover_sets;          // recover_api.hip: the tables, lists and masks of a mixed recovery's distinct sets, one allocation carved up (cap in sets; under mu)
     VerifyBuffers vs;   // verify-side scratch, sized for vs_cap blobs
     size_t vs_cap;
     std::mutex verify_mu;

@@ -490,6 +490,7 @@ void ctx_destroy(Ctx *c) {
     dev_free(c->celleach_lines);
     grow_free(c->celleach);
     dev_free(c->recover_tab);
+    grow_free(c->recover_sets);
     fk20_free(c);
     if (c->cellv_pin) hipHostFree(c->cellv_pin);
     if (c->cellv_ev) hipEventDestroy(c->cellv_ev);

@@ -6,6 +6,7 @@
 #include "g1.cuh"
 #include "fr28.cuh"
 #include "plan.h"
+#include "recover_sets.h"
 
 namespace lwk {
 
@@ -247,12 +248,8 @@ void launch_fk20_msm(const G1Affine29 *table, int bits, const uint32_t *scalars,
 void launch_fk20_transforms(G1Xyzz29 *pts, const uint8_t *roots, G1Xyzz29 *h_out, size_t n_blobs, hipStream_t st);
 
 // ---- EIP-7594 recovery (recover.hip)
-// the index set of a recovery call, passed to its kernels by value: k[i] = the index of the i-th given cell (ascending), and bit q of
-// `given` = the cell at position q = bitrev7(k), whose c_k is w128^q, is among them
-struct RecoverSet {
-    uint8_t k[kCellsPerBlob];
-    uint32_t given[kCellsPerBlob / 32];
-};
+// the index set of a recovery call, passed to its kernels by value: RecoverSet (recover_sets.h)
+static_assert(kRecoverCells == (size_t)kCellsPerBlob, "recover_sets.h counts the cells of a blob as the kernels do");
 constexpr size_t kRecoverTabElems = 4 * kCellsPerBlob;   // the per-call table of k_recover_setup, Fr elements
 void launch_recover_setup(const RecoverSet &set, const Fr *tw_fwd, Fr *tab, hipStream_t st);
 // cells: n_blobs x num_cells x 2048 bytes, blob-major, 16-byte aligned, in the byte order `le` names -> the 4096 canonical coefficients
@@ -260,6 +257,32 @@ void launch_recover_setup(const RecoverSet &set, const Fr *tw_fwd, Fr *tab, hipS
 // degree < 4096 goes through the blob's cells
 void launch_recover_coefficients(const uint8_t *cells, const RecoverSet &set, size_t num_cells, const Fr *tw_fwd, const Fr *tw_inv, const Fr *tab,
                                  Fr *scratch, uint32_t *coeffs_raw, int32_t *status, int bad_code, int le, size_t n_blobs, hipStream_t st);
+
+// The mixed form: every blob its own set. A call's distinct sets live on the device, written there by k_recover_mixed_setup alone:
+// per set a table as k_recover_setup's, the list k[] (128 bytes, 0xff behind the last given cell) and the mask (4 words).
+struct RecoverSetsDev {
+    Fr *tab;          // n_sets x kRecoverTabElems
+    uint8_t *k;       // n_sets x 128
+    uint32_t *given;  // n_sets x 4
+};
+// the masks of up to kRecoverSetupGroup sets, by value to one setup launch
+constexpr size_t kRecoverSetupGroup = 128;
+struct RecoverMasks {
+    uint32_t given[kRecoverSetupGroup][kCellsPerBlob / 32];
+};
+// what the interpolation and the solve know of up to kRecoverGroup blobs that follow each other, by value to one launch of each:
+// set[j] = the set of the group's blob j, cell0[j] = the cells of the group in front of its own
+constexpr size_t kRecoverGroup = 256;
+struct RecoverGroup {
+    uint32_t set[kRecoverGroup];
+    uint32_t cell0[kRecoverGroup];
+};
+// sets first .. first + n_sets of dev from their masks (n_sets <= kRecoverSetupGroup)
+void launch_recover_mixed_setup(const RecoverMasks &masks, size_t first, size_t n_sets, const Fr *tw_fwd, const RecoverSetsDev &dev, hipStream_t st);
+// as launch_recover_coefficients for the n_blobs <= kRecoverGroup blobs of g, whose n_cells cells follow each other at `cells`
+void launch_recover_mixed_coefficients(const uint8_t *cells, const RecoverGroup &g, size_t n_cells, const Fr *tw_fwd, const Fr *tw_inv,
+                                       const RecoverSetsDev &dev, Fr *scratch, uint32_t *coeffs_raw, int32_t *status, int bad_code, int le,
+                                       size_t n_blobs, hipStream_t st);
 
 // ---- EIP-7594 cell proof batch verification (cells_verify.hip)
 // digests32[32 i] = SHA-256(le64(rows[i]) | le64(idx[i]) | cell i | proof i); status[i] = bad_code where an element of cell i is not below r.

@@ -150,6 +150,126 @@ __global__ __launch_bounds__(64) void k_recover_solve(const Fr *__restrict__ scr
     coeffs_raw[2 * slot + 1] = make_uint4(lo.l[4], lo.l[5], lo.l[6], lo.l[7]);
 }
 
+// ---- the mixed form: every blob its own set (recover_api.hip: lwkzg_recover_cells_and_kzg_proofs_mixed). The same three steps; the
+// sets reach the device as 128-bit masks by value to the setup, which leaves everything else a set needs in device memory, and the
+// blobs' set ids and cell offsets by value to the other two. Nothing here reads host memory or a buffer the host writes.
+
+namespace {
+
+__device__ __forceinline__ bool mask_given(const uint32_t *given, uint32_t q) { return (given[q >> 5] >> (q & 31u)) & 1u; }
+
+}  // namespace
+
+// One workgroup of 128 lanes per distinct set: block s makes set first + s from masks.given[s]. Its table as k_recover_setup's; lane k
+// is also cell index k for the list: k[i] = the i-th given index, 0xff from the number of given cells on; the mask goes along.
+__global__ __launch_bounds__(128) void k_recover_mixed_setup(RecoverMasks masks, uint32_t first, const Fr *__restrict__ tw_fwd,
+                                                             Fr *__restrict__ tabs, uint8_t *__restrict__ ks, uint32_t *__restrict__ givens) {
+    __shared__ Fr root[kCellsPerBlob];
+    __shared__ uint8_t has[kCellsPerBlob];   // by cell index
+    const uint32_t q = threadIdx.x;
+    const uint32_t *given = masks.given[blockIdx.x];
+    const size_t set = (size_t)first + blockIdx.x;
+    Fr *tab = tabs + set * kRecoverTabElems;
+    const Fr x = q < 64 ? tw_fwd[32 * q] : neg(tw_fwd[32 * (q - 64)]);   // w128^64 = -1
+    root[q] = x;
+    has[q] = mask_given(given, bitrev7(q));
+    __syncthreads();
+    const Fr g = const_fr(kRecGenMont), gx = g * x;
+    Fr zr = Fr::one(), zc = Fr::one();
+    uint32_t rank = 0, count = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)kCellsPerBlob; j++) {
+        const uint32_t h = has[j];
+        count += h;
+        if (j < q) rank += h;
+        if (mask_given(given, j)) continue;   // (the same for every lane)
+        const Fr c = root[j];
+        zr = zr * (x - c);
+        zc = zc * (gx - c);
+    }
+    if (has[q]) ks[set * kCellsPerBlob + rank] = (uint8_t)q;
+    if (q >= count) ks[set * kCellsPerBlob + q] = 0xff;
+    if (q < (uint32_t)kCellsPerBlob / 32) givens[set * (kCellsPerBlob / 32) + q] = given[q];
+    tab[q] = zr * const_fr(kRecInv64Mont);
+    tab[128 + q] = inv_divsteps(zc);   // 7 x_q is no 128th root of unity: never zero
+    Fr gp = Fr::one(), gip = Fr::one(), base = g, ibase = const_fr(kRecInvGenMont);
+#pragma unroll 1
+    for (int bit = 0; bit < 7; bit++) {
+        if ((q >> bit) & 1u) {
+            gp = gp * base;
+            gip = gip * ibase;
+        }
+        base = sqr(base);
+        ibase = sqr(ibase);
+    }
+    const Fr inv128 = const_fr(kRecInv128Mont);
+    tab[256 + q] = gp * inv128;
+    tab[384 + q] = gip * inv128;
+}
+
+// One wave (one workgroup) per (blob, given cell) of a group: blockIdx.x is the cell's place in `cells`, its blob the last one of the
+// group whose cells start at or before it (every blob has cells, so cell0 ascends strictly). Then as k_recover_interp, with the blob's
+// own list and table.
+__global__ __launch_bounds__(64) void k_recover_mixed_interp(const uint4 *__restrict__ cells, RecoverGroup grp, uint32_t n_blobs,
+                                                             const Fr *__restrict__ tw_inv, const Fr *__restrict__ tabs,
+                                                             const uint8_t *__restrict__ ks, Fr *__restrict__ scratch,
+                                                             int32_t *__restrict__ status, int bad_code, int le) {
+    __shared__ Fr buf[kCellElems];
+    const uint32_t t = threadIdx.x;
+    uint32_t blob = 0, end = n_blobs;   // cell0[blob] <= blockIdx.x < cell0[end] (the group's cell count where end = n_blobs)
+    while (end - blob > 1) {
+        const uint32_t mid = (blob + end) >> 1;
+        if (grp.cell0[mid] <= blockIdx.x) blob = mid;
+        else end = mid;
+    }
+    const uint32_t i = blockIdx.x - grp.cell0[blob];
+    const size_t set = grp.set[blob];
+    const uint32_t k = ks[set * kCellsPerBlob + i], q = bitrev7(k);
+    const uint4 *e = cells + ((size_t)blockIdx.x * kCellElems + t) * 2;
+    Fr x;
+    element_limbs(x.l, e[0], e[1], le);
+    const bool bad = raw_geq<8>(x.l, FrParams::MOD);
+    if (bad) x = Fr::zero();
+    if (__any(bad) && t == 0) status[blob] = bad_code;
+    buf[t] = x;
+    __syncthreads();
+#pragma unroll 1
+    for (int s = 0; s < 6; s++) {
+        if (t < 32) cell_idft64_stage(buf, tw_inv, s, t);
+        __syncthreads();
+    }
+    // I_k[t] Zs(c_k): times h_k^-t, and Zs(c_k) / 64 from the set's table
+    const Fr sc = cell_coeff_twist(tw_inv, k, t, kRecInvOmega8192Mont) * tabs[set * kRecoverTabElems + q];
+    scratch[((size_t)blob * kCellElems + t) * kCellsPerBlob + q] = sc * buf[t];
+}
+
+// One wave (one workgroup) per (blob, t) of a group: blockIdx.x = 64 blob + t. As k_recover_solve, with the blob's own mask and table.
+__global__ __launch_bounds__(64) void k_recover_mixed_solve(const Fr *__restrict__ scratch, RecoverGroup grp, const Fr *__restrict__ tw_fwd,
+                                                            const Fr *__restrict__ tw_inv, const Fr *__restrict__ tabs,
+                                                            const uint32_t *__restrict__ givens, uint4 *__restrict__ coeffs_raw,
+                                                            int32_t *__restrict__ status, int bad_code) {
+    __shared__ Fr buf[kCellsPerBlob];
+    const uint32_t b = threadIdx.x, t = blockIdx.x % kCellElems, blob = blockIdx.x / kCellElems;
+    const size_t set = grp.set[blob];
+    const uint32_t *given = givens + set * (kCellsPerBlob / 32);
+    const Fr *tab = tabs + set * kRecoverTabElems;
+    const Fr *src = scratch + (size_t)blockIdx.x * kCellsPerBlob;
+    // the slots of the missing cells were never written: they count as zero (Zs vanishes there)
+    buf[bitrev7(b)] = mask_given(given, b) ? src[b] : Fr::zero();
+    buf[bitrev7(b + 64)] = mask_given(given, b + 64) ? src[b + 64] : Fr::zero();
+    __syncthreads();
+    dft128(buf, tw_inv, b);                      // 128 N_t, N_t = Q_t Zs
+    scale_and_permute(buf, tab + 256, b);        // N_t[j] 7^j
+    dft128(buf, tw_fwd, b);                      // N_t(7 w128^i)
+    scale_and_permute(buf, tab + 128, b);        // Q_t(7 w128^i)
+    dft128(buf, tw_inv, b);                      // 128 Q_t[j] 7^j
+    const Fr lo = tab[384 + b] * buf[b], hi = tab[384 + b + 64] * buf[b + 64];
+    if (__any(!hi.is_zero()) && b == 0) status[blob] = bad_code;
+    const size_t slot = (size_t)blob * kBlobElems + (size_t)kCellElems * b + t;
+    coeffs_raw[2 * slot] = make_uint4(lo.l[0], lo.l[1], lo.l[2], lo.l[3]);
+    coeffs_raw[2 * slot + 1] = make_uint4(lo.l[4], lo.l[5], lo.l[6], lo.l[7]);
+}
+
 void launch_recover_setup(const RecoverSet &set, const Fr *tw_fwd, Fr *tab, hipStream_t st) {
     ProfScope p("k_recover_setup", st);
     hipLaunchKernelGGL(k_recover_setup, dim3(1), dim3(kCellsPerBlob), 0, st, set, tw_fwd, tab);
@@ -165,6 +285,25 @@ void launch_recover_coefficients(const uint8_t *cells, const RecoverSet &set, si
     ProfScope p("k_recover_solve", st);
     hipLaunchKernelGGL(k_recover_solve, dim3((unsigned)(n_blobs * kCellElems)), dim3(kCellElems), 0, st, (const Fr *)scratch, set, tw_fwd, tw_inv,
                        tab, (uint4 *)coeffs_raw, status, bad_code);
+}
+
+void launch_recover_mixed_setup(const RecoverMasks &masks, size_t first, size_t n_sets, const Fr *tw_fwd, const RecoverSetsDev &dev, hipStream_t st) {
+    ProfScope p("k_recover_mixed_setup", st);
+    hipLaunchKernelGGL(k_recover_mixed_setup, dim3((unsigned)n_sets), dim3(kCellsPerBlob), 0, st, masks, (uint32_t)first, tw_fwd, dev.tab, dev.k,
+                       dev.given);
+}
+
+void launch_recover_mixed_coefficients(const uint8_t *cells, const RecoverGroup &g, size_t n_cells, const Fr *tw_fwd, const Fr *tw_inv,
+                                       const RecoverSetsDev &dev, Fr *scratch, uint32_t *coeffs_raw, int32_t *status, int bad_code, int le,
+                                       size_t n_blobs, hipStream_t st) {
+    {
+        ProfScope p("k_recover_mixed_interp", st);
+        hipLaunchKernelGGL(k_recover_mixed_interp, dim3((unsigned)n_cells), dim3(kCellElems), 0, st, (const uint4 *)cells, g, (uint32_t)n_blobs,
+                           tw_inv, (const Fr *)dev.tab, (const uint8_t *)dev.k, scratch, status, bad_code, le);
+    }
+    ProfScope p("k_recover_mixed_solve", st);
+    hipLaunchKernelGGL(k_recover_mixed_solve, dim3((unsigned)(n_blobs * kCellElems)), dim3(kCellElems), 0, st, (const Fr *)scratch, g, tw_fwd,
+                       tw_inv, (const Fr *)dev.tab, (const uint32_t *)dev.given, (uint4 *)coeffs_raw, status, bad_code);
 }
 
 }  // namespace lwk
