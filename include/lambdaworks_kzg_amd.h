@@ -272,6 +272,41 @@ size_t lwkzg_setup_image_bytes(void);
 C_KZG_RET lwkzg_setup_export_device(const KZGSettings *s, void *image_dev, void *stream);
 C_KZG_RET lwkzg_setup_import_device(KZGSettings *out, const void *image_dev);
 
+/* c-kzg-4844 trusted setups. load_trusted_setup* above read the G1 points as MONOMIAL powers [tau^i]G, which is
+ * the reference's reading (src/srs.rs). c-kzg-4844 itself carries them in LAGRANGE form, natural order: its 1.x load_trusted_setup and
+ * trusted_setup.txt hold only that form, its 2.x file and loader hold Lagrange G1, monomial G2, monomial G1. Handing such a file to
+ * load_trusted_setup_file succeeds (4096 valid subgroup points) and every result afterwards is wrong; these three loaders are the way
+ * in for it, and lwkzg_trusted_setup_check is the one call that tells a mis-loaded setup.
+ * The result is a KZGSettings as load_trusted_setup builds from the matching monomial bytes (g1_values: the 4096 MONOMIAL points,
+ * reference blst_fp convention; every call, free_trusted_setup and the setup image work on it), with two differences: it answers in
+ * c-kzg mode from the start, as after lwkzg_settings_set_mode(s, LWKZG_MODE_CKZG) -- the table the load picks is built in the
+ * Lagrange form first; another mode may be set afterwards --, and its Lagrange form is live at once, taken from the input.
+ * One-section form: the monomial points are derived on the device (4096 MSMs over the Lagrange points). Three-section form: nothing is
+ * derived; both sections are validated and held against each other (a random polynomial committed over each: two MSMs), and the load
+ * fails closed on a mismatch, which c-kzg itself does not check.
+ * C_KZG_BADARGS (c-kzg's code, in both modes): a NULL pointer; counts other than 4096 / 65; a token that is not hex of the right
+ * length or a token count that fits neither layout; a G1 point of either section that is not a compressed point of the subgroup or is
+ * the point at infinity; a bad G2 point; a derived monomial point at infinity; two G1 sections that are not the same setup.
+ * C_KZG_MALLOC: memory; C_KZG_ERROR: a failing device call, no GPU. On failure *out is untouched and nothing stays allocated;
+ * lwkzg_last_error names the section and the index of a bad point. */
+/* c-kzg-4844 1.x's load_trusted_setup: g1 = 4096 compressed LAGRANGE points [l_i(tau)]G1 in NATURAL order (l_i over w^i), g2 = 65 monomial */
+C_KZG_RET lwkzg_load_trusted_setup_lagrange(KZGSettings *out, const uint8_t *g1_lagrange_bytes, size_t n1,
+                                            const uint8_t *g2_bytes, size_t n2);
+/* c-kzg-4844 2.x's load_trusted_setup (its argument order; `precompute` accepted and ignored: this library has its own tables) */
+C_KZG_RET lwkzg_load_trusted_setup_ckzg(KZGSettings *out, const uint8_t *g1_monomial_bytes, size_t n_g1_monomial,
+                                        const uint8_t *g1_lagrange_bytes, size_t n_g1_lagrange,
+                                        const uint8_t *g2_monomial_bytes, size_t n_g2, uint64_t precompute);
+/* either c-kzg text layout, told apart by the token count: "n1 n2", n1 Lagrange G1, n2 G2 [, n1 monomial G1]; tokens separated by ANY whitespace */
+C_KZG_RET lwkzg_load_trusted_setup_file_ckzg(KZGSettings *out, FILE *in);
+/* the Lagrange form of a loaded setup, 4096 x 48 bytes compressed, NATURAL order (what a c-kzg 1.x file holds); derives it if absent
+ * (C_KZG_MALLOC, as lwkzg_settings_set_mode's derivation, when it cannot be had) */
+C_KZG_RET lwkzg_setup_g1_lagrange(uint8_t *out, const KZGSettings *s);
+/* is this a powers-of-tau setup? *ok = g1_values[0] and g2_values[0] are the generators, e(A, G2) e(-B, g2_values[1]) == 1 for
+ * A = sum_(j<4095) rho^j g1_values[j+1], B = sum_(j<4095) rho^j g1_values[j] (rho hashed from the setup's bytes; two MSMs on the settings'
+ * engine), and e(g1_values[1], g2_values[k]) e(-g1_values[0], g2_values[k+1]) == 1 for k < 64 (the host's pairing). For settings of any
+ * loader, hand-built ones included; never changes them. C_KZG_OK with the verdict, C_KZG_BADARGS for NULL or bad settings. About 0.1 s. */
+C_KZG_RET lwkzg_trusted_setup_check(bool *ok, const KZGSettings *s);
+
 /* ONE process, SEVERAL GPUs (csrc/multi.hip): the node-level form of the batch entry points for the reference's own kind of caller
  * -- plain C calls, /root/reference/fuzz/base_fuzz.h:17-34, src/lib.rs:253-283 -- which has no torch.distributed. lwkzg_multi_load*
  * parses, validates and prepares the setup on devices[0] exactly as load_trusted_setup* does (src/lib.rs:709-802), delivers the

@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_recover_cells_and_kzg_proofs", "lwkzg_recover_cells_and_kzg_proofs_batch", "lwkzg_recover_cells_and_kzg_proofs_batch_device",
     "lwkzg_recover_cells_and_kzg_proofs_mixed", "lwkzg_recover_cells_and_kzg_proofs_mixed_device",
     "lwkzg_set_cell_proof_engine", "lwkzg_cell_proof_engine", "lwkzg_fk20_table_bytes", "lwkzg_fk20_chunk_blobs", "lwkzg_fk20_points",
+    "lwkzg_load_trusted_setup_lagrange", "lwkzg_load_trusted_setup_ckzg", "lwkzg_load_trusted_setup_file_ckzg", "lwkzg_setup_g1_lagrange",
+    "lwkzg_trusted_setup_check",
 ]
 
 _lib = None
@@ -167,6 +169,11 @@ def lib():
     l.lwkzg_setup_image_bytes.restype = sz
     l.lwkzg_setup_export_device.argtypes = [ps, vp, vp]
     l.lwkzg_setup_import_device.argtypes = [ps, vp]
+    l.lwkzg_load_trusted_setup_lagrange.argtypes = [ps, C.c_char_p, sz, C.c_char_p, sz]
+    l.lwkzg_load_trusted_setup_ckzg.argtypes = [ps, C.c_char_p, sz, C.c_char_p, sz, C.c_char_p, sz, C.c_uint64]
+    l.lwkzg_load_trusted_setup_file_ckzg.argtypes = [ps, vp]
+    l.lwkzg_setup_g1_lagrange.argtypes = [C.c_char_p, ps]
+    l.lwkzg_trusted_setup_check.argtypes = [C.POINTER(C.c_bool), ps]
     l.lwkzg_set_device.argtypes = [ci]
     l.lwkzg_version.restype = C.c_char_p
     l.lwkzg_last_error.restype = C.c_char_p
@@ -307,6 +314,42 @@ class TrustedSetup:
         return self
 
     @classmethod
+    def from_lagrange_bytes(cls, g1_lagrange_bytes, g2_bytes):
+        """c-kzg-4844 1.x's load_trusted_setup (lwkzg_load_trusted_setup_lagrange): 4096 LAGRANGE G1 points, natural order, and 65 G2
+        points; the monomial points are derived on the device. The settings answer in c-kzg mode."""
+        self = cls()
+        _check("lwkzg_load_trusted_setup_lagrange", lib().lwkzg_load_trusted_setup_lagrange(
+            C.byref(self.s), g1_lagrange_bytes, len(g1_lagrange_bytes) // 48, g2_bytes, len(g2_bytes) // 96))
+        self._loaded = True
+        return self
+
+    @classmethod
+    def from_ckzg_bytes(cls, g1_monomial_bytes, g1_lagrange_bytes, g2_monomial_bytes, precompute=0):
+        """c-kzg-4844 2.x's load_trusted_setup, its argument order (lwkzg_load_trusted_setup_ckzg): both G1 sections are validated and
+        held against each other. The settings answer in c-kzg mode."""
+        self = cls()
+        _check("lwkzg_load_trusted_setup_ckzg", lib().lwkzg_load_trusted_setup_ckzg(
+            C.byref(self.s), g1_monomial_bytes, len(g1_monomial_bytes) // 48, g1_lagrange_bytes, len(g1_lagrange_bytes) // 48,
+            g2_monomial_bytes, len(g2_monomial_bytes) // 96, precompute))
+        self._loaded = True
+        return self
+
+    @classmethod
+    def from_ckzg_file(cls, path):
+        """a c-kzg-4844 trusted_setup.txt of either layout (lwkzg_load_trusted_setup_file_ckzg); from_file is for the reference's
+        monomial text"""
+        self = cls()
+        fp = _libc.fopen(os.fsencode(path), b"r")
+        if not fp:
+            raise FileNotFoundError(path)
+        try:
+            _check("lwkzg_load_trusted_setup_file_ckzg", lib().lwkzg_load_trusted_setup_file_ckzg(C.byref(self.s), fp))
+        finally:
+            _libc.fclose(fp)
+        self._loaded = True
+        return self
+
+    @classmethod
     def from_device_image(cls, image_dev_ptr):
         self = cls()
         _check("lwkzg_setup_import_device", lib().lwkzg_setup_import_device(C.byref(self.s), image_dev_ptr))
@@ -321,6 +364,18 @@ class TrustedSetup:
 
     def g2_values_bytes(self):
         return C.string_at(self.s.g2_values, 65 * 288)
+
+    def g1_lagrange(self):
+        """the Lagrange form of the setup as a c-kzg 1.x file holds it: 4096 x 48 bytes compressed, natural order (derived if absent)"""
+        out = C.create_string_buffer(4096 * 48)
+        _check("lwkzg_setup_g1_lagrange", lib().lwkzg_setup_g1_lagrange(out, self.ref()))
+        return out.raw
+
+    def check(self):
+        """is this a powers-of-tau setup? (lwkzg_trusted_setup_check: False for a Lagrange file loaded as monomial, among others)"""
+        ok = C.c_bool(False)
+        _check("lwkzg_trusted_setup_check", lib().lwkzg_trusted_setup_check(C.byref(ok), self.ref()))
+        return bool(ok.value)
 
     def fft_settings(self):
         return FFTSettings.from_address(self.s.fs)

@@ -205,9 +205,10 @@ extern "C" size_t lwkzg_timing_report(const KZGSettings *s, char *buf, size_t ca
         const BuildTiming &b = c->last_build;
         k = snprintf(tmp, sizeof tmp,
                      "{\"load\": {\"context_ms\": %.3f, \"points_and_tables_ms\": %.3f, \"g2_and_fft_ms\": %.3f, \"default_table_ms\": %.3f, "
+                     "\"lagrange_section_ms\": %.3f, \"derive_monomial_ms\": %.3f, \"cross_check_ms\": %.3f, "
                      "\"total_ms\": %.3f}, \"last_table_build\": {\"bits\": %d, \"row_bytes\": %zu, \"table_bytes\": %zu, \"free_old_ms\": %.3f, "
                      "\"table_malloc_ms\": %.3f, \"scratch_malloc_ms\": %.3f, \"kernels_ms\": %.3f, \"scratch_free_ms\": %.3f, \"total_ms\": %.3f, \"in_place\": %d}}",
-                     l.context_ms, l.points_and_tables_ms, l.g2_and_fft_ms, l.default_table_ms, l.total_ms, b.bits, b.row_bytes, b.table_bytes,
+                     l.context_ms, l.points_and_tables_ms, l.g2_and_fft_ms, l.default_table_ms, l.lagrange_section_ms, l.derive_monomial_ms, l.cross_check_ms, l.total_ms, b.bits, b.row_bytes, b.table_bytes,
                      b.free_old_ms, b.table_malloc_ms, b.scratch_malloc_ms, b.kernels_ms, b.scratch_free_ms, b.total_ms, (int)b.in_place);
     } else {
         k = snprintf(tmp, sizeof tmp, "{}");

@@ -206,6 +206,10 @@ struct LoadTiming {
     double points_and_tables_ms = 0; // upload, decompression + subgroup checks, blst layout, 9 MB fixed-base table, D2H
     double g2_and_fft_ms = 0;        // G2 points on the host, twiddles and FFTSettings
     double default_table_ms = 0;     // the engine the load selects (BuildTiming of it is kept as the last build)
+    // the c-kzg loaders only (load.hip: setup_from_ckzg), part of points_and_tables_ms:
+    double lagrange_section_ms = 0;  // upload, decompression + subgroup checks and the 9 MB table of the Lagrange section
+    double derive_monomial_ms = 0;   // one-section form: the 4096 MSMs that derive the monomial points (0: nothing was derived)
+    double cross_check_ms = 0;       // three-section form: the two MSMs that hold the sections against each other
     double total_ms = 0;
 };
 

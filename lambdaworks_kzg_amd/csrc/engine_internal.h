@@ -92,5 +92,15 @@ void vs_free(Ctx *c);
 // ---- tables.hip -------------------------------------------------------------------------------------------------------------------
 void settings_follow_mode(Ctx *c, int mode);
 C_KZG_RET enable_direct_table(const KZGSettings *s, int window_bits, size_t row_pref, int forms = 0);
+// A setup that arrives in Lagrange form (load.hip: the c-kzg loaders; the context is not published yet, no lock is needed).
+// lagrange_from_bytes: 4096 compressed points ALREADY in the blob's bit-reversed order on the device -> lag.points (decompressed, subgroup
+// check, verdicts in d_status) and lag.table, enqueued on the context's stream. monomial_from_lagrange: the 4096 compressed monomial
+// points at d_comp48, kMaxChunk rows of forward-DFT coefficients at a time over that table (twiddles and workspace must exist).
+// lagrange_publish: the form is live (lagrange_prepare finds nothing to do).
+C_KZG_RET lagrange_from_bytes(Ctx *c, const uint8_t *d_in48, int32_t *d_status);
+C_KZG_RET monomial_from_lagrange(Ctx *c, uint8_t *d_comp48);
+void lagrange_publish(Ctx *c);
+// the Lagrange form of a published settings object, derived now if absent: lagrange_prepare under the locks settings_follow_mode takes
+C_KZG_RET lagrange_ensure(Ctx *c);
 
 }  // namespace lwk

@@ -750,6 +750,30 @@ void launch_idft_columns(uint32_t *coeffs_raw, const Fr *tw_inv, uint32_t first,
     hipLaunchKernelGGL(k_idft_columns, dim3((unsigned)n_rows), dim3(256), 0, st, (uint4 *)coeffs_raw, tw_inv, first, ninv);
 }
 
+// The opposite direction: a c-kzg-4844 setup arrives in LAGRANGE form and the monomial points are derived from it (tables.hip:
+// monomial_from_lagrange). x^j has the evaluations w_k^j on the domain, so [tau^j]G = sum_k w_k^j L_k with w_k = w^bitrev12(k): a row of the
+// forward DFT matrix committed over the Lagrange form. Row b of the output = the 4096 scalars of j = first + b, canonical raw as the
+// MSM's digit extraction reads them. Every entry is a power of w, so it is a lookup: w^e = tw_fwd[e mod 2048], negated when bit 11 of e
+// is set (w^2048 = -1). One lane per entry.
+__global__ __launch_bounds__(256) void k_dft_rows(uint4 *__restrict__ coeffs_raw, const Fr *__restrict__ tw_fwd, uint32_t first, size_t n) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const uint32_t k = (uint32_t)(g & (kBlobElems - 1)), j = first + (uint32_t)(g >> 12);
+    const uint32_t e = (j * (__brev(k) >> 20)) & (kBlobElems - 1);   // (j, bitrev12(k) < 4096: the product is below 2^24)
+    Fr v = tw_fwd[e & (kBlobElems / 2 - 1)];
+    if (e & (kBlobElems / 2)) v = neg(v);
+    uint32_t raw[8];
+    fe_to_raw<FrParams>(raw, v);
+    coeffs_raw[2 * g] = make_uint4(raw[0], raw[1], raw[2], raw[3]);
+    coeffs_raw[2 * g + 1] = make_uint4(raw[4], raw[5], raw[6], raw[7]);
+}
+
+void launch_dft_rows(uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t first, size_t n_rows, hipStream_t st) {
+    ProfScope p("k_dft_rows", st);
+    const size_t n = n_rows * kBlobElems;
+    hipLaunchKernelGGL(k_dft_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (uint4 *)coeffs_raw, tw_fwd, first, n);
+}
+
 // c-kzg blobs on the Lagrange form: the canonical little-endian elements ARE the scalars the MSM reads (32-bit words, least
 // significant first), so "parsing" is a copy with the range check of the c-kzg front end (an element >= r: status[blob] = BADARGS)
 __global__ __launch_bounds__(256) void k_copy_le_check(const uint4 *__restrict__ blobs, uint4 *__restrict__ scalars_raw,

@@ -112,6 +112,9 @@ void launch_bitrev_permute(const Fr *in, Fr *out, size_t n_blobs, hipStream_t st
 // commitments are the Lagrange points; the copy + range check that replaces the transform in front of a commitment; and the forward
 // transform of a proof's quotient when only the Lagrange-form table exists
 void launch_idft_columns(uint32_t *coeffs_raw, const Fr *tw_inv, uint32_t first, size_t n_rows, hipStream_t st);
+// the opposite direction (a c-kzg setup arrives in Lagrange form): row b = the forward-DFT coefficients w^((first + b) bitrev12(k)), k < 4096,
+// whose MSM over the Lagrange form is the monomial point [tau^(first + b)]G
+void launch_dft_rows(uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t first, size_t n_rows, hipStream_t st);
 void launch_copy_le_check(const uint8_t *blobs, uint32_t *scalars_raw, int32_t *status, size_t n_blobs, hipStream_t st);
 void launch_coefficients_to_evaluations(uint32_t *coeffs_raw, Fr *scratch, Fr *scratch2, const Fr28 *tw28_fwd, size_t n_blobs, hipStream_t st);
 void launch_fr_be_to_mont(const uint8_t *in_be, Fr *out, size_t n_elems, hipStream_t st);

@@ -366,6 +366,8 @@ struct FixedQ {
     std::vector<LineCoeff> lines;  // in the order the loop consumes them
 };
 
+thread_local bool tl_keep_lines = true;   // false: this thread's pairings leave the cache alone (pairing_product_is_one_uncached)
+
 std::shared_ptr<const FixedQ> fixed_q_lines(const G2A &q) {
     static std::mutex mu;
     static std::vector<std::shared_ptr<const FixedQ>> cache;  // a handful of entries: linear search
@@ -392,7 +394,7 @@ std::shared_ptr<const FixedQ> fixed_q_lines(const G2A &q) {
         }
     }
     std::lock_guard<std::mutex> lk(mu);
-    if (cache.size() < 8) cache.push_back(fq);  // beyond that (the test hook with arbitrary points) nothing is kept
+    if (tl_keep_lines && cache.size() < 8) cache.push_back(fq);  // beyond that (the test hook with arbitrary points) nothing is kept
     return fq;
 }
 
@@ -511,6 +513,15 @@ bool pairing_product_is_one(const G1Affine *ps, const Fp2 *qx, const Fp2 *qy, in
     }
     f = f12conj(f);  // z < 0
     return final_exponentiation_is_one(f);
+}
+
+// the same for G2 points that no later call will see again (lwkzg_trusted_setup_check walks all 65 of a setup): their line tables are used
+// once and not kept, so the handful of cached ones stay those of the verifications
+bool pairing_product_is_one_uncached(const G1Affine *ps, const Fp2 *qx, const Fp2 *qy, int n) {
+    tl_keep_lines = false;
+    const bool r = pairing_product_is_one(ps, qx, qy, n);
+    tl_keep_lines = true;
+    return r;
 }
 
 // test hook (CPU-only): compressed inputs, host decompression, no subgroup checks on G2

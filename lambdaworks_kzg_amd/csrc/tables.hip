@@ -1,6 +1,8 @@
 // tables.hip -- the two forms of the setup (monomial, Lagrange) and the direct tables over them: derivation of the Lagrange form, table
 // builds, the moves a mode switch asks for, and the lwkzg_enable_direct_table* / lwkzg_direct_* entry points.
 #include "engine_internal.h"
+#include "abi_guard.h"
+#include "setup_text.h"
 
 #include <chrono>
 #include <vector>
@@ -134,6 +136,58 @@ static C_KZG_RET lagrange_prepare(Ctx *c) {
     c->lag.ready = true;
     c->lag_ready.store(true, std::memory_order_release);
     return C_KZG_OK;
+}
+
+// ---- a setup that arrives in Lagrange form (load.hip: the c-kzg loaders) ---------------------------------------------------------
+// The context is the loader's own until the load returns: no lock is taken here. Everything is enqueued on the context's stream; the
+// loader reads the verdicts and decides.
+C_KZG_RET lagrange_from_bytes(Ctx *c, const uint8_t *d_in48, int32_t *d_status) {
+    if (hipMalloc((void **)&c->lag.points, (size_t)kBlobElems * sizeof(G1Affine)) != hipSuccess ||
+        hipMalloc((void **)&c->lag.table, (size_t)kTablePoints * sizeof(G1Affine29)) != hipSuccess) {
+        (void)hipGetLastError();
+        dev_free(c->lag.points);
+        dev_free(c->lag.table);
+        set_error("hipMalloc failed for the Lagrange form of the setup");
+        return C_KZG_MALLOC;
+    }
+    launch_g1_decompress(d_in48, c->lag.points, d_status, kBlobElems, 1, c->stream);
+    launch_build_table(c->lag.points, c->lag.table, c->stream);
+    return C_KZG_OK;
+}
+
+// [tau^j]G = sum_k w_k^j L_k (fr_ops.hip: k_dft_rows): lagrange_prepare the other way round, the same 4096 MSMs over the other form.
+// The Lagrange form has only its bucket table at this point of a load, so that is the engine they run on.
+C_KZG_RET monomial_from_lagrange(Ctx *c, uint8_t *d_comp48) {
+    C_KZG_RET rc = ctx_reserve(c, kMaxChunk);
+    if (rc != C_KZG_OK) return rc;
+    hipStream_t st = c->stream;
+    WsUse wsu(c, st);
+    for (size_t off = 0; off < (size_t)kBlobElems; off += kMaxChunk) {
+        launch_dft_rows(c->ws.scalars, c->tw_fwd, (uint32_t)off, kMaxChunk, st);
+        msm_stages(c, c->ws.scalars, d_comp48 + 48 * off, kMaxChunk, st, 0, false, true);
+    }
+    return C_KZG_OK;
+}
+
+void lagrange_publish(Ctx *c) {
+    c->lag.ready = true;
+    c->lag_ready.store(true, std::memory_order_release);
+}
+
+C_KZG_RET lagrange_ensure(Ctx *c) {
+    c = c->primary;
+    if (c->lag_ready.load(std::memory_order_acquire)) return C_KZG_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    std::unique_lock<std::mutex> lk_twin;
+    Ctx *const twin = c->twin.load(std::memory_order_acquire);
+    if (twin) lk_twin = std::unique_lock<std::mutex>(twin->mu);
+    LWK_HIP(hipSetDevice(c->device));
+    LWK_HIP(hipDeviceSynchronize());
+    c->lag_failed = false;   // (an explicit request retries, as lwkzg_settings_set_mode does)
+    const C_KZG_RET rc = lagrange_prepare(c);
+    hipDeviceSynchronize();
+    sync_twin_tables(c);
+    return rc;
 }
 
 // Bring the tables to what mode `mode` wants (see the block comment above). `may_swap`: when the mode's form has no direct table,
@@ -303,6 +357,30 @@ int lwkzg_direct_table_bits(const KZGSettings *s) {
 int lwkzg_direct_table_forms(const KZGSettings *s) {
     Ctx *c = ctx_of(s);
     return !c ? -1 : (c->direct_table ? 1 : 0) | (c->lag.direct_table ? 2 : 0);
+}
+
+// The Lagrange form of a loaded setup as a c-kzg-4844 1.x file holds it: 4096 x 48 bytes compressed, NATURAL order. Derived first if the
+// settings have not needed it yet (C_KZG_MALLOC, as lwkzg_settings_set_mode's derivation, when it cannot be had).
+C_KZG_RET lwkzg_setup_g1_lagrange(uint8_t *out, const KZGSettings *s) {
+    if (!out || !s) return C_KZG_BADARGS;
+    Ctx *c = ctx_of(s);
+    if (!c) return C_KZG_BADARGS;
+    return guarded("lwkzg_setup_g1_lagrange", [&]() -> C_KZG_RET {
+        C_KZG_RET rc = lagrange_ensure(c);
+        if (rc != C_KZG_OK) return rc;
+        Ctx *p = c->primary;
+        std::vector<G1Affine> pts(kBlobElems);
+        std::vector<uint8_t> comp((size_t)kBlobElems * 48);
+        {
+            std::lock_guard<std::mutex> lk(p->mu);
+            LWK_HIP(hipSetDevice(p->device));
+            LWK_HIP(hipMemcpyAsync(pts.data(), p->lag.points, (size_t)kBlobElems * sizeof(G1Affine), hipMemcpyDeviceToHost, p->stream));
+            LWK_HIP(hipStreamSynchronize(p->stream));
+        }
+        for (size_t i = 0; i < (size_t)kBlobElems; i++) g1_compress_affine(&comp[48 * i], pts[i]);   // (never the point at infinity: lagrange_prepare, the loaders)
+        setup_text_bitrev48(out, comp.data());   // the library's order is the blob's own; a c-kzg file's is the natural one
+        return C_KZG_OK;
+    });
 }
 
 int lwkzg_direct_num_windows(int window_bits) { return direct_num_windows(window_bits); }
