@@ -1,6 +1,7 @@
 // recover_sets.h -- the index sets of the EIP-7594 recovery calls on the host: one list of 64 .. 128 ascending cell
-// indices -> a RecoverSet, and the lists of a mixed call, one per blob -> its distinct sets, a set id and a cell offset per blob, or the
-// first blob whose list is at fault. Plain C++, no HIP header: tests/recover_sets_check.cpp compiles it for the host.
+// indices -> a RecoverSet, and the lists of a call, one per blob (mixed) or one for all (shared set) -> its distinct sets, a set id and a
+// cell offset per blob, or the first blob whose list is at fault. Plain C++, no HIP header: tests/recover_sets_check.cpp compiles it for
+// the host.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -41,7 +42,7 @@ inline RecoverListFault recover_set_of(RecoverSet &set, const uint64_t *idx, siz
     return kRecoverListGood;
 }
 
-// the lists of a mixed call, blob after blob in idx. sets: the distinct ones in order of first occurrence (two lists are the same set
+// the lists of a call, blob after blob in idx. sets: the distinct ones in order of first occurrence (two lists are the same set
 // exactly when their masks are equal); set_of[b]: blob b's set; cell_off[b]: the cells in front of blob b's (n + 1 entries, the last
 // one the call's total)
 struct RecoverSets {
@@ -75,6 +76,19 @@ inline bool recover_sets_of(RecoverSets &out, const uint64_t *idx, const size_t 
         off += num_cells[b];
         out.cell_off.push_back(off);
     }
+    return true;
+}
+
+// a shared-set call of n blobs as the call it is: one list -> one set, every blob's id 0 and num_cells cells per blob. A fault is the
+// list's, as recover_set_of reports it (bad_blob says nothing)
+inline bool recover_sets_shared(RecoverSets &out, const uint64_t *idx, size_t num_cells, size_t n) {
+    out = RecoverSets();
+    RecoverSet set;
+    out.fault = recover_set_of(set, idx, num_cells, &out.bad_at);
+    if (out.fault != kRecoverListGood) return false;
+    out.sets.push_back(set);
+    out.set_of.assign(n, 0);
+    for (size_t b = 0; b <= n; b++) out.cell_off.push_back(b * num_cells);
     return true;
 }
 

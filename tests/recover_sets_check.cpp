@@ -1,4 +1,4 @@
-// The host side of the mixed recovery's index sets (lambdaworks_kzg_amd/csrc/recover_sets.h) as a stand-alone program, built under
+// The host side of the recovery's index sets (lambdaworks_kzg_amd/csrc/recover_sets.h) as a stand-alone program, built under
 // AddressSanitizer and UndefinedBehaviorSanitizer by tests/test_recover_mixed_cpu.py. Every case prints one line, "<name> ok" or
 // "<name> FAILED: ..."; the exit status is the number of failures.
 #include <stdio.h>
@@ -139,6 +139,41 @@ void single_list() {
     report("one list", recover_set_of(set, exact.data(), exact.size()) == kRecoverListGood && set_is(set, l));
 }
 
+// a shared-set call: one list for three blobs is one set, id 0 throughout and m cells per blob; a faulty list is reported as for one list
+void shared_set() {
+    const std::vector<uint64_t> l = range(1, 128, 2);
+    std::vector<uint64_t> exact(l);
+    exact.shrink_to_fit();
+    const size_t m = l.size();
+    RecoverSets s;
+    bool ok = recover_sets_shared(s, exact.data(), m, 3) && s.fault == kRecoverListGood && s.sets.size() == 1 && set_is(s.sets[0], l);
+    ok = ok && s.set_of == std::vector<uint32_t>({0, 0, 0}) && s.cell_off == std::vector<size_t>({0, m, 2 * m, 3 * m});
+    std::string why;
+    const auto faulty = [&](const char *name, const std::vector<uint64_t> &bad, RecoverListFault kind, size_t at) {
+        std::vector<uint64_t> e(bad);
+        e.shrink_to_fit();
+        const bool same = !recover_sets_shared(s, e.data(), e.size(), 3) && s.fault == kind && (kind == kRecoverListCount || s.bad_at == at) &&
+                          s.sets.empty();
+        if (!same) why += std::string(" ") + name;
+        ok = ok && same;
+    };
+    faulty("count 63", range(0, 63), kRecoverListCount, 0);
+    faulty("count 129", range(0, 129), kRecoverListCount, 0);
+    std::vector<uint64_t> b = range(0, 64);
+    b[63] = 128;
+    faulty("index 128", b, kRecoverListIndex, 63);
+    b[63] = ~(uint64_t)0;
+    faulty("index 2^64 - 1", b, kRecoverListIndex, 63);
+    b = range(0, 64);
+    b[10] = 9;
+    faulty("a repeated index", b, kRecoverListOrder, 10);
+    b = range(0, 64);
+    b[10] = 11;
+    b[11] = 10;
+    faulty("a descending pair", b, kRecoverListOrder, 11);
+    report("shared set, n = 3", ok, why);
+}
+
 }  // namespace
 
 int main() {
@@ -147,5 +182,6 @@ int main() {
     faults();
     empty_call();
     single_list();
+    shared_set();
     return failures;
 }

@@ -62,7 +62,7 @@ def cell_interpolant(k, vals):
 
 
 def recover_tables(cell_indices):
-    """what k_recover_setup leaves: Zs(w128^q) and 1 / Zs(7 w128^q) for q < 128, Zs(Y) = prod over the missing cells of (Y - c_k)"""
+    """what k_recover_setup leaves for one index set: Zs(w128^q) and 1 / Zs(7 w128^q) for q < 128, Zs(Y) = prod over the missing cells of (Y - c_k)"""
     given = set(cell_indices)
     miss_roots = [S.c_of_cell(k) for k in range(S.N_CELLS) if k not in given]
 

@@ -1,7 +1,7 @@
 """GPU: EIP-7594 recovery (lwkzg_recover_cells_and_kzg_proofs, _batch, _batch_device) in both modes. The expected outputs are
 lwkzg_compute_cells_and_kzg_proofs' for the original blob, which tests/test_gpu_cells.py pins to the Python restatement: byte for byte
 over ten index patterns (one also against tests/recover_spec.py's coefficients), edge polynomials, batches across the 8-blob launch
-set in the three forms, outputs left out, the caller's stream, elements not below r and inconsistent cells in the middle of a batch,
+set in the three forms, one call across the kernels' group of 256 blobs, outputs left out, the caller's stream, elements not below r and inconsistent cells in the middle of a batch,
 exactly 64 cells with an altered element (another polynomial, not an error), the round trip through the cell proof verifier, both
 engines, a Lagrange-only table and the other two setups."""
 import contextlib
@@ -152,6 +152,31 @@ def test_batches_across_the_launch_set(K, gpu_setup, mode, n):
         assert got == want
         singles = [K.recover_cells_and_kzg_proofs(idx, cells[64 * CELL * b:64 * CELL * (b + 1)], gpu_setup) for b in range(n)]
         assert singles == want
+
+
+def test_a_shared_set_call_across_the_kernels_group_of_256_blobs(K, gpu_setup):
+    """a chunk without proofs holds up to 512 blobs and reaches the kernels 256 at a time, every blob with set id 0 and its cells
+    65 b cells into the input: blob 256, the first of the second group, has an altered element, so its cells are inconsistent. It
+    alone is flagged and every other blob's cells are the compute call's. One device call, compared on the device."""
+    import torch
+    mode = S.MODE_REFERENCE
+    n, idx = 257, _pick(65, 150)
+    with _mode(K, gpu_setup, mode):
+        db = _dev(torch, b"".join(_blob(2000 + i, mode) for i in range(n)))
+        want = torch.zeros(n * 128 * CELL, dtype=torch.uint8, device="cuda")
+        got = torch.zeros(n * 128 * CELL, dtype=torch.uint8, device="cuda")
+        ds = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        K.compute_cells_and_kzg_proofs_batch_device(want.data_ptr(), None, db.data_ptr(), n, gpu_setup)
+        torch.cuda.synchronize()
+        given = want.view(n, 128, CELL)[:, idx, :].contiguous()
+        spoilt = _alter(bytes(given[256, 32].cpu().numpy()), 0, 7, mode)
+        given[256, 32] = _dev(torch, spoilt)
+        torch.cuda.synchronize()
+        K.recover_cells_and_kzg_proofs_batch_device(got.data_ptr(), None, idx, given.data_ptr(), n, gpu_setup, None, ds.data_ptr())
+        torch.cuda.synchronize()
+        assert ds.cpu().tolist() == [0] * 256 + [_bad_code(K, mode)]
+        assert torch.equal(got.view(n, -1)[:256], want.view(n, -1)[:256])
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -2,8 +2,7 @@
 own) in both modes. Every expected output is lwkzg_compute_cells_and_kzg_proofs_batch's for the original blobs, computed once per mode
 for a pool of 17 blobs (tests/test_gpu_cells.py pins that call to the Python restatement); the shared-set recovery is the second
 yardstick. Byte for byte, no tolerance: ragged inputs, repeated sets, sets and offsets that change across the 8-blob proof chunk and
-the 64-blob host slice, outputs left out, bad inputs in the middle, two calls back to back on one stream, both MSM engines, FK20 and
-the round trip through the cell proof verifier."""
+the 64-blob host slice, outputs left out, bad inputs in the middle, two calls back to back on one stream, shared-set calls around a mixed one on one stream, both MSM engines, FK20 and the round trip through the cell proof verifier."""
 import contextlib
 import ctypes as C
 import random
@@ -93,6 +92,15 @@ class _DeviceCall:
         cr = bytes(self.dc.cpu().numpy()) if self.dc is not None else None
         pr = bytes(self.dp.cpu().numpy()) if self.dp is not None else None
         return K.capi._cells_split(cr, pr, self.n), self.ds.cpu().tolist()[:self.n]
+
+
+class _SharedSetCall(_DeviceCall):
+    """the same for the shared-set device call: every blob through lists[0]"""
+
+    def enqueue(self, K, ts, stream=None):
+        K.recover_cells_and_kzg_proofs_batch_device(self.dc.data_ptr() if self.dc is not None else None,
+                                                    self.dp.data_ptr() if self.dp is not None else None, self.lists[0], self.din.data_ptr(),
+                                                    self.n, ts, stream, self.ds.data_ptr())
 
 
 def _device(K, torch, lists, per, ts, cells_out=True, proofs=True):
@@ -285,6 +293,29 @@ def test_two_device_calls_back_to_back_on_one_stream(K, gpu_setup, mode):
         s.synchronize()
         assert call1.result(K) == (want1, [0, 0])
         assert call2.result(K) == (want2, [0, 0, 0])
+
+
+def test_shared_set_calls_around_a_mixed_call_on_one_stream(K, gpu_setup):
+    """the two kinds of call share one host pipeline, the workspace and the context's tables: a shared-set call with A, a mixed call
+    with B and A and a shared-set call with B, on one stream without synchronisation between them. Each call's setup runs behind the
+    kernels of the call before it, so all three are right."""
+    import torch
+    mode = S.MODE_REFERENCE
+    pool = _pool(K, gpu_setup, mode)
+    a, b = _pick(64, 710), _pick(90, 711)
+    wants = [[(c, None) for c, _ in _want(pool, 2, first=f)] for f in (4, 8, 13)]
+    with _mode(K, gpu_setup, mode):
+        s = torch.cuda.Stream()
+        with torch.cuda.stream(s):
+            calls = [_SharedSetCall(torch, [a, a], _given(wants[0], [a, a]), proofs=False),
+                     _DeviceCall(torch, [b, a], _given(wants[1], [b, a]), proofs=False),
+                     _SharedSetCall(torch, [b, b], _given(wants[2], [b, b]), proofs=False)]
+        torch.cuda.synchronize()
+        for call in calls:   # no synchronisation between them
+            call.enqueue(K, gpu_setup, s.cuda_stream)
+        s.synchronize()
+        for call, want in zip(calls, wants):
+            assert call.result(K) == (want, [0, 0])
 
 
 # 8

@@ -1,7 +1,7 @@
 """CPU: the mixed recovery (lwkzg_recover_cells_and_kzg_proofs_mixed, _mixed_device: every blob its own index set). The host side of
 the sets, lambdaworks_kzg_amd/csrc/recover_sets.h, as a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer
 (tests/recover_sets_check.cpp: de-duplication in order of first occurrence, cell offsets, every argument error naming its blob,
-n = 0), and the argument checks of both entry points on a hand-built settings object, which need no GPU."""
+n = 0, the one set of a shared-set call), and the argument checks of both entry points on a hand-built settings object, which need no GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -13,7 +13,7 @@ CASES = [
     "deduplication [A, B, A]", "deduplication [B, A, B, A]", "offsets 64, 128, 65",
     "count 63", "count 63 in front", "count 129", "count 129 in front", "index 128", "index 128 in front",
     "index 2^64 - 1", "index 2^64 - 1 in front", "a repeated index", "a repeated index in front",
-    "a descending pair", "a descending pair in front", "n = 0", "one list",
+    "a descending pair", "a descending pair in front", "n = 0", "one list", "shared set, n = 3",
 ]
 
 
