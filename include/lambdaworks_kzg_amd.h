@@ -386,6 +386,61 @@ void lwkzg_verify_shard_free(LwkzgVerifyShard *shard);
 C_KZG_RET lwkzg_verify_shards_finish(bool *ok, const uint8_t *partials /* n_shards * 328 */, size_t n_shards, size_t n_total,
                                      const KZGSettings *s);
 
+/* lwkzg_verify_blob_kzg_proof_batch_device without a parked host thread: a VERIFIER takes device-resident batches on the caller's
+ * stream and answers each into a LwkzgVerifyResult, in stream order.
+ *   lwkzg_verifier_new      allocates everything a call of up to max_blobs blobs needs (device scratch, pinned blocks, events, job slots;
+ *                           the settings' workspace grows as a call of that size would grow it). The only call of the five that may
+ *                           allocate or synchronise the device. C_KZG_BADARGS: NULL arguments, max_blobs == 0; C_KZG_MALLOC: no memory
+ *                           (the settings stay usable).
+ *   lwkzg_verifier_enqueue  the synchronous device call split where that call first waits: same inputs (device pointers produced on
+ *                           `stream`, NULL = already complete), same mode resolution at entry, same verdict, return code and empty-batch
+ *                           rule -- written to *result instead. It returns as soon as everything is enqueued: no wait for a stream or
+ *                           an event, no allocation. *result is any host memory that stays valid until state == 1 (pinned mapped
+ *                           memory lets a later kernel on the same stream read the verdict); state is 0 when the call returns and is
+ *                           stored LAST, with release order. Work enqueued on `stream` AFTER the call is ordered behind the verdict.
+ *                           The inputs must stay untouched until the call completes. The call's own return value covers only what is
+ *                           known at once -- C_KZG_BADARGS: NULL v or result, n above the verifier's capacity, NULL inputs with n > 0, a
+ *                           verifier whose settings were freed; C_KZG_ERROR: a failing enqueue -- and *result is then completed on the
+ *                           spot with that code. n == 0 completes on the spot with the mode's empty-batch verdict. A rejected input
+ *                           is an answer: the call returns C_KZG_OK, result->rc is the mode's code and first_bad the lowest such index.
+ *                           Calls on ONE verifier run one after the other on the GPU (they share its scratch, ordered by events); up
+ *                           to LWKZG_VERIFIER_DEPTH may be in flight, and ONE MORE WAITS FOR THE OLDEST TO COMPLETE: the only place this
+ *                           call waits for the GPU. Like every device-resident call it takes the settings' context lock while it
+ *                           enqueues, and a SYNCHRONOUS call on the same settings holds that lock until its own GPU work is done: an
+ *                           enqueue issued meanwhile by another thread waits for that call. Calls on TWO verifiers on two caller
+ *                           streams run on the settings' two contexts. Call lwkzg_reserve_streams(s, n, 2) BEFORE lwkzg_verifier_new:
+ *                           otherwise the first enqueue that finds the first context busy creates the second one (an allocation
+ *                           inside enqueue), and a second context created after lwkzg_verifier_new grows its workspace inside the
+ *                           first enqueue that lands on it. Synchronous verifications on the same settings stay correct meanwhile.
+ *   lwkzg_verifier_pending  calls enqueued and not yet complete; -1 for a NULL handle.
+ *   lwkzg_verifier_wait     until pending == 0.
+ *   lwkzg_verifier_free     waits first; NULL is fine. free_trusted_setup on settings that still have verifiers waits for their calls in
+ *                           flight; such a verifier answers C_KZG_BADARGS to further enqueues and is still freed with this call.
+ * Not covered: host-pointer batches (they are upload-bound), lwkzg_multi_*, the cell verifications (they de-duplicate commitments on the
+ * host mid-call), and stream capture -- enqueue on a capturing stream is not supported. With the experiment arm LWKZG_VERIFY_MSM=0 the
+ * enqueue runs the synchronous call and completes *result before it returns (first_bad is then not reported). */
+#define LWKZG_VERIFIER_DEPTH 4
+typedef struct {
+    int32_t  state;      /* 0 = pending, 1 = complete; written LAST, with release order */
+    int32_t  rc;         /* the C_KZG_RET the synchronous device call would have returned */
+    int32_t  ok;         /* 0 / 1: its *ok */
+    uint32_t first_bad;  /* lowest rejected index, 0xffffffff = none */
+    uint8_t  r[32];      /* the batch challenge, canonical big-endian, as lwkzg_batch_challenge_host writes it */
+    uint8_t  partial[LWKZG_VERIFY_PARTIAL_BYTES]; /* as lwkzg_verify_shard_partial(first_index = 0) writes it */
+} LwkzgVerifyResult;
+typedef struct LwkzgVerifier LwkzgVerifier;
+C_KZG_RET lwkzg_verifier_new(LwkzgVerifier **out, const KZGSettings *s, size_t max_blobs);
+C_KZG_RET lwkzg_verifier_enqueue(LwkzgVerifier *v, LwkzgVerifyResult *result, const void *blobs_dev,
+                                 const void *commitments48_dev, const void *proofs48_dev, size_t n, void *stream);
+int       lwkzg_verifier_pending(const LwkzgVerifier *v);   /* calls enqueued and not yet complete, -1 = bad handle */
+C_KZG_RET lwkzg_verifier_wait(LwkzgVerifier *v);            /* until pending == 0 */
+void      lwkzg_verifier_free(LwkzgVerifier *v);            /* waits first; NULL is fine */
+/* Host-only test hook: the two host steps of an enqueue back to back on caller-supplied blocks -- the n records, the lowest rejected
+ * index (0xffffffff: none), the three sums (flag 1 | x 48 | y 48 each, as in a partial) and sum r^i y_i (canonical big-endian) -- with
+ * the generator and the G2 points of *s. No GPU, no context; *out is complete when it returns. */
+C_KZG_RET lwkzg_verifier_host_steps(LwkzgVerifyResult *out, const uint8_t *records, size_t n, uint32_t first_bad, const uint8_t *sums3x97,
+                                    const uint8_t *ysum32, const KZGSettings *s, int mode);
+
 /* Per-item verification: n independent verify_blob_kzg_proof calls (src/lib.rs:456-505) in one. For every i, ok_out[i] (0/1) and
  * rc_out[i] (a C_KZG_RET) are exactly what verify_blob_kzg_proof(&ok, &blobs[i], &commitments[i], &proofs[i], s) gives, in the mode the
  * settings answer in. A bad item is an answer, not a failure: the call returns C_KZG_OK once every item is decided, C_KZG_BADARGS for

@@ -10,7 +10,7 @@ from .capi import (  # noqa: F401
     blob_to_kzg_commitment, blob_to_kzg_commitment_batch, blob_to_kzg_commitment_batch_device, commit_and_prove_batch_device,
     compute_blob_kzg_proof, compute_blob_kzg_proof_batch, compute_blob_kzg_proof_batch_device,
     compute_kzg_proof, compute_kzg_proof_batch, get_mode, knob_report, lib, set_device, set_mode,
-    VerifyShard, verify_shards_finish,
+    VerifyShard, verify_shards_finish, Verifier, VerifyResult, VERIFIER_DEPTH, verifier_host_steps, batch_challenge_host,
     verify_blob_kzg_proof, verify_blob_kzg_proof_batch, verify_blob_kzg_proof_batch_device, verify_kzg_proof,
     verify_blob_kzg_proof_each, verify_blob_kzg_proof_each_device, verify_kzg_proof_each,
     BYTES_PER_CELL, CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_CELL, FIELD_ELEMENTS_PER_EXT_BLOB,

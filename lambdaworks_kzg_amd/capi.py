@@ -38,6 +38,15 @@ class FFTSettings(C.Structure):
                 ("reverse_roots_of_unity", C.c_void_p), ("roots_of_unity", C.c_void_p)]
 
 
+VERIFIER_DEPTH = 4   # LWKZG_VERIFIER_DEPTH
+
+
+class VerifyResult(C.Structure):
+    """LwkzgVerifyResult: where an asynchronous verification answers. state is written last (0 = pending, 1 = complete)."""
+    _fields_ = [("state", C.c_int32), ("rc", C.c_int32), ("ok", C.c_int32), ("first_bad", C.c_uint32),
+                ("r", C.c_uint8 * 32), ("partial", C.c_uint8 * 328)]
+
+
 # every symbol include/lambdaworks_kzg_amd.h declares
 EXPORTED_SYMBOLS = [
     "load_trusted_setup", "load_trusted_setup_file", "free_trusted_setup", "blob_to_kzg_commitment",
@@ -75,6 +84,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_set_cell_proof_engine", "lwkzg_cell_proof_engine", "lwkzg_fk20_table_bytes", "lwkzg_fk20_chunk_blobs", "lwkzg_fk20_points",
     "lwkzg_load_trusted_setup_lagrange", "lwkzg_load_trusted_setup_ckzg", "lwkzg_load_trusted_setup_file_ckzg", "lwkzg_setup_g1_lagrange",
     "lwkzg_trusted_setup_check",
+    "lwkzg_verifier_new", "lwkzg_verifier_enqueue", "lwkzg_verifier_pending", "lwkzg_verifier_wait", "lwkzg_verifier_free",
+    "lwkzg_verifier_host_steps",
 ]
 
 _lib = None
@@ -155,6 +166,13 @@ def lib():
     l.lwkzg_verify_shard_free.argtypes = [vp]
     l.lwkzg_verify_shard_free.restype = None
     l.lwkzg_verify_shards_finish.argtypes = [C.POINTER(C.c_bool), C.c_char_p, sz, sz, ps]
+    l.lwkzg_verifier_new.argtypes = [C.POINTER(vp), ps, sz]
+    l.lwkzg_verifier_enqueue.argtypes = [vp, C.POINTER(VerifyResult), vp, vp, vp, sz, vp]
+    l.lwkzg_verifier_pending.argtypes = [vp]
+    l.lwkzg_verifier_wait.argtypes = [vp]
+    l.lwkzg_verifier_free.argtypes = [vp]
+    l.lwkzg_verifier_free.restype = None
+    l.lwkzg_verifier_host_steps.argtypes = [C.POINTER(VerifyResult), C.c_char_p, sz, C.c_uint32, C.c_char_p, C.c_char_p, ps, ci]
     l.lwkzg_release_context.argtypes = [ps]
     l.lwkzg_reserve.argtypes = [ps, sz]
     l.lwkzg_reserve_streams.argtypes = [ps, sz, ci]
@@ -920,6 +938,54 @@ class VerifyShard:
             self.free()
         except Exception:
             pass
+
+
+class Verifier:
+    """lwkzg_verifier_*: device-resident batch verifications that do not block the calling thread. enqueue returns a VerifyResult
+    whose state turns 1 once rc / ok / first_bad / r / partial are final; the verifier keeps every result it handed out alive."""
+
+    def __init__(self, ts, max_blobs):
+        self.ts = ts   # the verifier's device scratch belongs to the setup's context
+        self.h = C.c_void_p()
+        self._results = []
+        _check("lwkzg_verifier_new", lib().lwkzg_verifier_new(C.byref(self.h), ts.ref(), max_blobs))
+
+    def enqueue(self, blobs_ptr, comm_ptr, proofs_ptr, n, stream=None):
+        """returns at once; raises KzgError (its .result is the completed VerifyResult) for what the call itself refuses"""
+        res = VerifyResult()
+        self._results = [r for r in self._results if r.state != 1][-4 * VERIFIER_DEPTH:] + [res]
+        rc = lib().lwkzg_verifier_enqueue(self.h, C.byref(res), blobs_ptr, comm_ptr, proofs_ptr, n, stream)
+        if rc != C_KZG_OK:
+            err = KzgError("lwkzg_verifier_enqueue", rc)
+            err.result = res
+            raise err
+        return res
+
+    def pending(self):
+        return lib().lwkzg_verifier_pending(self.h)
+
+    def wait(self):
+        _check("lwkzg_verifier_wait", lib().lwkzg_verifier_wait(self.h))
+
+    def free(self):
+        if self.h:
+            lib().lwkzg_verifier_free(self.h)   # waits for the calls in flight first
+            self.h = C.c_void_p()
+            self._results = []
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def verifier_host_steps(records, n, first_bad, sums3x97, ysum32, settings_ref, mode):
+    """test hook (host only): the two host steps of Verifier.enqueue on caller-supplied blocks; returns the completed VerifyResult"""
+    res = VerifyResult()
+    _check("lwkzg_verifier_host_steps",
+           lib().lwkzg_verifier_host_steps(C.byref(res), records, n, first_bad, sums3x97, ysum32, settings_ref, mode))
+    return res
 
 
 def verify_shards_finish(partials, n_shards, n_total, ts):

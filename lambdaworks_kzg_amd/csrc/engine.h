@@ -142,6 +142,7 @@ struct VerifyBuffers {
     bool owned = false;  // the device pointers above belong to this object (verify_buffers_free), not to the context
 };
 void verify_buffers_free(VerifyBuffers &v);
+C_KZG_RET verify_buffers_alloc(VerifyBuffers &v, size_t cap);   // device scratch of one batch verification of up to `cap` blobs (C_KZG_MALLOC: nothing is kept)
 
 // Up to this many blobs a verification / proof call validates its points on the host threads: ~0.2 ms per point per
 // thread against a 2 ms latency-shaped kernel. 4 per usable hardware thread, at most 64.
@@ -435,6 +436,10 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
 C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_comm, const uint8_t *d_proofs, size_t n, int mode,
                                 uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p, VerifyBuffers &vb, hipStream_t caller,
                                 uint8_t *records_out = nullptr, bool keep = false);
+// the enqueue half of verify_prepare_device (everything up to and including the transcript's copy into vb.h_rec; waits for nothing):
+// caller holds c->mu (and verify_mu unless vb.owned) and has selected the device. *recorded: the transcript is on its way to vb.h_rec
+C_KZG_RET verify_front_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_comm, const uint8_t *d_proofs, size_t n, int mode,
+                              VerifyBuffers &vb, hipStream_t caller, bool want_records, bool keep, bool *recorded);
 // the same front for n openings (C, z, y, pi) already on the device (verify_each.hip): both point sets validated, z / y checked and
 // written canonical in the mode's byte order to vb.d_rz / vb.d_r, the status words in vb.status_all; enqueued on c->stream
 C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const uint8_t *d_proofs, const uint8_t *d_z, const uint8_t *d_y,
@@ -459,6 +464,16 @@ void cell_batch_challenge(uint32_t r_raw[8], const uint8_t *distinct48, size_t m
 void cell_batch_powers(Fr pw33[33], const uint32_t r_raw[8]);
 C_KZG_RET cell_batch_finish(bool *ok, uint8_t *out4x97, const uint8_t sums[3][96], const int infs[3], const uint8_t rli48[48],
                             const KZGSettings *s);
+
+// the host's end of an asynchronous verification (verify.hip): the challenge and its power table from the transcript,
+// the partial and the verdict from what the device sent down, and the synchronous call with the same outputs (the fallback)
+void verify_async_challenge(uint8_t r_be[32], Fr pw33[33], const uint8_t *records, size_t n, bool le);
+C_KZG_RET verify_async_verdict(bool *ok, uint8_t *partial, const uint8_t sums96[3][96], const int infs[3], const uint8_t ysum_be[32],
+                               const KZGSettings *own);
+C_KZG_RET verify_batch_device_full(bool *ok, uint8_t r_be[32], uint8_t *partial, const uint8_t *d_blobs, const uint8_t *d_comm,
+                                   const uint8_t *d_proofs, size_t n, const KZGSettings *s, int mode, hipStream_t caller);
+// verify_async.hip: the calls in flight of every verifier of this context have completed (free_trusted_setup, before the context goes)
+void verifiers_drain(const Ctx *c);
 
 // G2 / pairing side (g2_pairing.hip, host only)
 bool g2_fill_values(g2_t *out65, const uint8_t *g2_bytes, size_t n2);

@@ -1,5 +1,5 @@
 // engine_internal.h -- what crosses between the engine's own translation units, and nothing else. Included only by engine.hip,
-// verify_front.hip, control.hip, load.hip, host_api.hip, tables.hip and device_api.hip; the rest of the library (verify.hip,
+// verify_front.hip, verify_async.hip, control.hip, load.hip, host_api.hip, tables.hip and device_api.hip; the rest of the library (verify.hip,
 // verify_each.hip, cells*_api.hip, cells_verify_each.hip, recover_api.hip, multi.hip) sees the engine through engine.h, the entry points'
 // guard through abi_guard.h, the carver through carve.h and the EIP-7594 compute paths' shared code through cells_common.h.
 #pragma once

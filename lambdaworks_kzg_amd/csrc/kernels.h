@@ -184,12 +184,19 @@ constexpr int kVmsmRows = 2 * kVmsmDigits;       // rows per point: [2^(8 j)]P a
 constexpr int kVmsmSteps = kVmsmDigits - 1;      // rows per half beyond the point itself
 constexpr int kVmsmMaxTerms = 64;                // terms per slice (one workgroup of k_vmsm_accumulate), at most
 constexpr size_t kVmsmPinBytes = 33 * 32 + 3 * 96 + 3 * 4 + 52;  // the pinned host block of a verification: powers up, sums down
+// the same block under an asynchronous verification (verify_async.hip): behind the sums and their flags a skip word on its way up (1: the
+// batch was rejected, every launch behind r exits at once) and sum r^i y_i (32 bytes, k_verify_ysum) on its way down
+constexpr size_t kVmsmPinSums = 33 * 32, kVmsmPinInfs = kVmsmPinSums + 3 * 96, kVmsmPinSkip = kVmsmPinInfs + 3 * 4, kVmsmPinYsum = kVmsmPinSkip + 4;
+static_assert(kVmsmPinYsum + 32 <= kVmsmPinBytes, "the asynchronous verification's words fit the pinned block");
+constexpr int kVmsmPwSkip = 33, kVmsmPwYsum = 34, kVmsmPwSlots = 35;   // Fr-sized slots of vm_pw on the device: the 33 powers, the skip word, sum r^i y_i
 constexpr int kVmsmListCap = 24;                 // rows of one digit value a slice lists before its lane falls back to a scan
 // rows of two point sets in one launch, beside the challenge hash: tab_*[row * n + i]; tmp: 15 x 2n XYZZ, pre: 15 x 2n field elements
 void launch_vmsm_multiples2(const G1Affine29 *pts_a, const int32_t *kind_a, G1Affine29 *tab_a, const G1Affine29 *pts_b,
                             const int32_t *kind_b, G1Affine29 *tab_b, G1Xyzz29 *tmp, F29<2> *pre, size_t n, hipStream_t st, bool apart = false);
 // pw: 33 Fr in Montgomery form, r^(2^k) for k = 0..31 and r^first; sc_a / sc_b: 8 words per term (lo | hi of a_i = r^(first+i), b_i = a_i z_i)
-void launch_vmsm_scalars(const uint8_t *z_bytes, int le, const Fr *pw, uint32_t *sc_a, uint32_t *sc_b, size_t n, hipStream_t st);
+// skip (here and in the two launches below; nullptr for every synchronous caller): a device word that, when set, makes the launch exit at once
+void launch_vmsm_scalars(const uint8_t *z_bytes, int le, const Fr *pw, uint32_t *sc_a, uint32_t *sc_b, size_t n, hipStream_t st,
+                         const uint32_t *skip = nullptr);
 uint32_t vmsm_terms_per_slice(size_t n);
 size_t vmsm_slices(size_t n);
 size_t vmsm_max_slices(size_t cap);
@@ -197,9 +204,13 @@ size_t vmsm_max_slices(size_t cap);
 // sc_c: the scalars of the third sum (over tab_c) when they are not sc_a (the cell batch's weights of its distinct commitments)
 void launch_vmsm_accumulate(const uint32_t *sc_a, const uint32_t *sc_b, const G1Affine29 *tab_p, const int32_t *kind_p,
                             const G1Affine29 *tab_c, const int32_t *kind_c, G1Xyzz29 *partial, size_t n, hipStream_t st,
-                            const uint32_t *sc_c = nullptr);
+                            const uint32_t *sc_c = nullptr, const uint32_t *skip = nullptr);
 // bsum: 3 x 256 XYZZ; out96 / inf: the three sums, affine big-endian x | y and an infinity flag each (what launch_xyzz29_to_affine_be leaves)
-void launch_vmsm_reduce(const G1Xyzz29 *partial, G1Xyzz29 *bsum, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st);
+void launch_vmsm_reduce(const G1Xyzz29 *partial, G1Xyzz29 *bsum, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st,
+                        const uint32_t *skip = nullptr);
+// verify_async.hip: out32 = sum_{i < n} r^(first + i) y_i, canonical big-endian; y32: the y bytes in the mode's byte order (canonical), pw: as
+// launch_vmsm_scalars takes it. One workgroup; skip as above
+void launch_verify_ysum(const uint8_t *y32, int le, const Fr *pw, uint8_t *out32, size_t n, hipStream_t st, const uint32_t *skip = nullptr);
 // records[160 i] = C_i | z_i | y_i | pi_i from the device-resident pieces; *first_bad = lowest index with a status word set (pre-set to 0xffffffff)
 void launch_verify_records(const uint8_t *canon_c, const uint8_t *z32, const uint8_t *y32, const uint8_t *canon_p, const int32_t *status,
                            uint8_t *records, uint32_t *first_bad, size_t n, hipStream_t st);

@@ -696,6 +696,80 @@ bool point_from_bytes(HXyzz &p, const uint8_t *in97) {
 
 }  // namespace
 
+// ---- the host's end of an asynchronous verification (verify_async.hip) -------------------------------------------------
+// Both steps run as host functions on the runtime's callback thread there, under the rules written above them: no HIP call, no
+// set_error, no lock that a thread may hold while it waits for the GPU. What they call in this file keeps to that (fixed_base_of's mutex
+// guards a pointer swap; pairing_verdict only reports a NULL g2_values, which a verifier never has).
+//
+// step 1: r over the transcript, canonical big-endian as lwkzg_batch_challenge_host writes it, and the table launch_vmsm_scalars and
+// launch_verify_ysum take for a batch that starts at r^0
+void verify_async_challenge(uint8_t r_be[32], Fr pw33[33], const uint8_t *records, size_t n, bool le) {
+    const HFr r_mont = batch_challenge_mont(records, n, le);
+    const uint32_t one_limbs[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+    hfr_to_be(r_be, r_mont * hfr_raw(one_limbs));
+    HFr sq = r_mont;
+    for (int k = 0; k < 32; k++) {
+        pw33[k] = sq.to_fe();
+        sq = sq * sq;
+    }
+    pw33[32] = HFr::one().to_fe();
+}
+
+static void partial_to_bytes(uint8_t *partial, const HXyzz sums[3], const HFr &ysum) {
+    memset(partial, 0, kPartial);
+    for (int k = 0; k < 3; k++) point_to_bytes(partial + 97 * k, sums[k]);
+    hfr_to_be(partial + 291, ysum);
+}
+
+// the partial and the verdict from the three sums and sum r^i y_i (canonical limbs): the tail of both forms below
+static C_KZG_RET verdict_from_sums(bool *ok, uint8_t *partial, const HXyzz sums[3], const uint32_t ys_raw[8], const KZGSettings *s) {
+    partial_to_bytes(partial, sums, hfr_raw(ys_raw));
+    HostPoint g;
+    if (!s->g2_values || !setup_generator(g, s)) return C_KZG_ERROR;
+    return batch_verdict(ok, sums, generator_mul(g.a, ys_raw), s);
+}
+
+// step 2: the three sums as launch_vmsm_reduce leaves them and sum r^i y_i as k_verify_ysum leaves it -> the partial (the format of
+// lwkzg_verify_shard_partial) and the verdict, with the generator and the G2 points of `own` (the verifier's copy of them)
+C_KZG_RET verify_async_verdict(bool *ok, uint8_t *partial, const uint8_t sums96[3][96], const int infs[3], const uint8_t ysum_be[32],
+                               const KZGSettings *own) {
+    *ok = false;
+    uint32_t ys_raw[8];
+    raw_from_be<8>(ys_raw, ysum_be);
+    if (raw_geq<8>(ys_raw, FrParams::MOD)) return C_KZG_ERROR;   // (the kernel writes a canonical value)
+    HXyzz sums[3];
+    for (int k = 0; k < 3; k++) {
+        sums[k] = HXyzz::infinity();
+        if (infs[k]) continue;
+        uint32_t raw[12];
+        G1Affine a;
+        raw_from_be<12>(raw, sums96[k]);
+        a.x = fe_from_raw<FpParams>(raw);
+        raw_from_be<12>(raw, sums96[k] + 48);
+        a.y = fe_from_raw<FpParams>(raw);
+        sums[k] = HXyzz::from_affine(HFp::from_fe(a.x), HFp::from_fe(a.y));
+    }
+    return verdict_from_sums(ok, partial, sums, ys_raw, own);
+}
+
+// the synchronous device call with the outputs of the asynchronous one (r, the partial), for a verifier whose settings run the
+// experiment arm LWKZG_VERIFY_MSM=0: on the calling thread, complete when it returns. first_bad is not reported on this path.
+C_KZG_RET verify_batch_device_full(bool *ok, uint8_t r_be[32], uint8_t *partial, const uint8_t *d_blobs, const uint8_t *d_comm,
+                                   const uint8_t *d_proofs, size_t n, const KZGSettings *s, int mode, hipStream_t caller) {
+    *ok = false;
+    Shard sh;
+    C_KZG_RET rc = shard_begin(sh, d_blobs, d_comm, d_proofs, n, s, mode, false, true, caller);
+    if (rc != C_KZG_OK) return rc;
+    Fr pw[33];   // (the challenge's bytes by step 1's own body; its table is not needed here)
+    verify_async_challenge(r_be, pw, sh.records.data(), n, mode == LWKZG_MODE_CKZG);
+    HXyzz sums[3];
+    HFr ysum;
+    if (shard_partial(sh, sh.records.data(), n, 0, sums, ysum, nullptr) != C_KZG_OK) return C_KZG_ERROR;
+    uint32_t ys_raw[8];
+    hfr_to_raw(ys_raw, ysum);
+    return verdict_from_sums(ok, partial, sums, ys_raw, s);
+}
+
 // ---- the host's end of the cell proof batch (cells_verify_api.hip) ------------------------------------------------
 // r = SHA-256("RCKZGCBATCH__V1_" | le64(4096) | le64(64) | le64(m) | le64(n) | the m distinct commitments | the n digests), read in the
 // mode's byte order and reduced: canonical limbs

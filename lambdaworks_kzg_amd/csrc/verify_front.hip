@@ -70,12 +70,12 @@ static size_t carve_vmsm(VerifyBuffers &v, uint8_t *base, size_t cap) {
     cv.take(v.sc_b, 32 * cap);
     cv.take(v.vm_partial, 3 * vmsm_max_slices(cap) * 256 * sizeof(G1Xyzz29));
     cv.take(v.vm_bsum, 3 * 256 * sizeof(G1Xyzz29));
-    cv.take(v.vm_pw, 33 * sizeof(Fr));
+    cv.take(v.vm_pw, kVmsmPwSlots * sizeof(Fr));   // (behind the 33 powers: the skip word and sum r^i y_i of an asynchronous verification)
     return cv.bytes();
 }
 
 // device scratch of one batch verification of up to `cap` blobs
-static C_KZG_RET verify_buffers_alloc(VerifyBuffers &v, size_t cap) {
+C_KZG_RET verify_buffers_alloc(VerifyBuffers &v, size_t cap) {
     const size_t nblk = lincomb3_blocks(cap);
     bool ok = hipMalloc((void **)&v.pts_c, cap * sizeof(G1Affine29)) == hipSuccess &&
               hipMalloc((void **)&v.pts_p, cap * sizeof(G1Affine29)) == hipSuccess &&
@@ -538,12 +538,14 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
 // stream hashes ALL blobs in one launch over the caller's commitment bytes; where the validation's canonical bytes differ from the
 // caller's (a valid point in a non-canonical encoding) that blob's challenge is taken again over the canonical ones -- a launch that
 // exits at once otherwise. Then chunk by chunk: parse, y = p(z). `caller`: the stream the inputs were produced on (may be null).
-C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_comm, const uint8_t *d_proofs, size_t n, int mode,
-                                uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p, VerifyBuffers &vb, hipStream_t caller,
-                                uint8_t *records_out, bool keep) {
-    if (!vb.owned) vb.hold = std::unique_lock<std::mutex>(c->verify_mu);
-    std::lock_guard<std::mutex> lk(c->mu);
-    LWK_HIP(hipSetDevice(c->device));
+//
+// verify_front_device is the ENQUEUE half of that and waits for nothing: the per-blob pass and, where the caller wants the transcript and
+// the scratch has room for it (*recorded), k_verify_records and the ONE copy into vb.h_rec. verify_prepare_device is that plus the wait;
+// an asynchronous verifier (verify_async.hip) is that plus two host functions in stream order. Caller holds c->mu (and verify_mu unless
+// vb.owned) and has selected the device.
+C_KZG_RET verify_front_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_comm, const uint8_t *d_proofs, size_t n, int mode,
+                              VerifyBuffers &vb, hipStream_t caller, bool want_records, bool keep, bool *recorded) {
+    *recorded = false;
     const int le = mode == LWKZG_MODE_CKZG;
     const int bad = le ? kStatusBadArgs : kStatusError;
     hipStream_t st = c->stream, sv = c->vstream, sc = c->aux[0];
@@ -632,13 +634,29 @@ C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d
         }
     }
     if (keep) return C_KZG_OK;   // per-item verification (verify_each.hip) reads the statuses, z and y where they are
-    if (records_out && vb.d_rec && vb.h_rec && vb.rec_cap >= n) {
+    if (want_records && vb.d_rec && vb.h_rec && vb.rec_cap >= n) {
         // r06: the transcript C | z | y | pi per blob assembled by a kernel and ONE copy into pinned memory, the lowest rejected index in its
         // last word -- where r05 made four copies into pageable vectors, a fifth for the status words, and the host interleaved
         uint32_t *d_flag = (uint32_t *)(vb.d_rec + 160 * n);
         LWK_HIP(hipMemsetAsync(d_flag, 0xff, 4, st));
         launch_verify_records(vb.canon_dev, vb.d_rz, vb.d_r, vb.canon_dev + 48 * n, vb.status_all, vb.d_rec, d_flag, n, st);
         LWK_HIP(hipMemcpyAsync(vb.h_rec, vb.d_rec, 160 * n + 4, hipMemcpyDeviceToHost, st));
+        *recorded = true;
+    }
+    return C_KZG_OK;
+}
+
+C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_comm, const uint8_t *d_proofs, size_t n, int mode,
+                                uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p, VerifyBuffers &vb, hipStream_t caller,
+                                uint8_t *records_out, bool keep) {
+    if (!vb.owned) vb.hold = std::unique_lock<std::mutex>(c->verify_mu);
+    std::lock_guard<std::mutex> lk(c->mu);
+    LWK_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    bool recorded = false;
+    const C_KZG_RET rc = verify_front_device(c, d_blobs, d_comm, d_proofs, n, mode, vb, caller, records_out != nullptr, keep, &recorded);
+    if (rc != C_KZG_OK || keep) return rc;
+    if (recorded) {
         LWK_HIP(hipStreamSynchronize(st));
         uint32_t first_bad;
         memcpy(&first_bad, vb.h_rec + 160 * n, 4);

@@ -102,7 +102,9 @@ void launch_vmsm_multiples2(const G1Affine29 *pts_a, const int32_t *kind_a, G1Af
 // a = r^(first + i), b = a z_i (z_i as the per-blob pass left its bytes), both split as lo + hi z^2; sc_a / sc_b hold lo | hi, 32
 // little-endian bytes per term: byte 16 h + j is the digit of row 16 h + j.
 __global__ __launch_bounds__(64) void k_vmsm_scalars(const uint8_t *__restrict__ z_bytes, int le, const Fr *__restrict__ pw,
-                                                     uint32_t *__restrict__ sc_a, uint32_t *__restrict__ sc_b, uint32_t n) {
+                                                     uint32_t *__restrict__ sc_a, uint32_t *__restrict__ sc_b, uint32_t n,
+                                                     const uint32_t *__restrict__ skip) {
+    if (skip && *skip) return;  // a rejected batch of an asynchronous verification (verify_async.hip): nothing behind r runs
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fr a = pw[32];
@@ -131,9 +133,10 @@ __global__ __launch_bounds__(64) void k_vmsm_scalars(const uint8_t *__restrict__
     }
 }
 
-void launch_vmsm_scalars(const uint8_t *z_bytes, int le, const Fr *pw, uint32_t *sc_a, uint32_t *sc_b, size_t n, hipStream_t st) {
+void launch_vmsm_scalars(const uint8_t *z_bytes, int le, const Fr *pw, uint32_t *sc_a, uint32_t *sc_b, size_t n, hipStream_t st,
+                         const uint32_t *skip) {
     ProfScope p("k_vmsm_scalars", st);
-    hipLaunchKernelGGL(k_vmsm_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, z_bytes, le, pw, sc_a, sc_b, (uint32_t)n);
+    hipLaunchKernelGGL(k_vmsm_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, z_bytes, le, pw, sc_a, sc_b, (uint32_t)n, skip);
 }
 
 // ---- behind r: bucket accumulation -------------------------------------------------------------------------------------------------
@@ -145,11 +148,13 @@ void launch_vmsm_scalars(const uint8_t *z_bytes, int le, const Fr *pw, uint32_t 
 __global__ __launch_bounds__(256) void k_vmsm_accumulate(const uint32_t *__restrict__ sc_a, const uint32_t *__restrict__ sc_b,
                                                          const uint32_t *__restrict__ sc_c, const G1Affine29 *__restrict__ tab_p, const int32_t *__restrict__ kind_p,
                                                          const G1Affine29 *__restrict__ tab_c, const int32_t *__restrict__ kind_c,
-                                                         G1Xyzz29 *__restrict__ partial, uint32_t n, uint32_t terms, uint32_t list_cap) {
+                                                         G1Xyzz29 *__restrict__ partial, uint32_t n, uint32_t terms, uint32_t list_cap,
+                                                         const uint32_t *__restrict__ skip) {
     __shared__ uint32_t dig_w[kVmsmMaxTerms * 8];
     __shared__ uint32_t count[256];
     __shared__ uint16_t list[256][kVmsmListCap];
     __shared__ uint8_t live[kVmsmMaxTerms];
+    if (skip && *skip) return;  // (the whole workgroup, before its first barrier)
     const uint8_t *dig = (const uint8_t *)dig_w;
     const int set = blockIdx.y, tid = threadIdx.x;
     const uint32_t base = blockIdx.x * terms;
@@ -211,19 +216,21 @@ size_t vmsm_max_slices(size_t cap) {
 
 void launch_vmsm_accumulate(const uint32_t *sc_a, const uint32_t *sc_b, const G1Affine29 *tab_p, const int32_t *kind_p,
                             const G1Affine29 *tab_c, const int32_t *kind_c, G1Xyzz29 *partial, size_t n, hipStream_t st,
-                            const uint32_t *sc_c) {
+                            const uint32_t *sc_c, const uint32_t *skip) {
     ProfScope p("k_vmsm_accumulate", st);
     const uint32_t terms = vmsm_terms_per_slice(n);
     const int lc = knobs().vmsm_list_cap;
     const uint32_t list_cap = lc > 0 && lc < kVmsmListCap ? (uint32_t)lc : (uint32_t)kVmsmListCap;
     hipLaunchKernelGGL(k_vmsm_accumulate, dim3((unsigned)vmsm_slices(n), 3), dim3(256), 0, st, sc_a, sc_b, sc_c ? sc_c : sc_a, tab_p, kind_p, tab_c,
                        kind_c,
-                       partial, (uint32_t)n, terms, list_cap);
+                       partial, (uint32_t)n, terms, list_cap, skip);
 }
 
 // ---- behind r: the slices' sums per bucket (a wave per bucket) ----------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_vmsm_bucket_sums(const G1Xyzz29 *__restrict__ partial, G1Xyzz29 *__restrict__ bsum, uint32_t slices) {
+__global__ __launch_bounds__(64) void k_vmsm_bucket_sums(const G1Xyzz29 *__restrict__ partial, G1Xyzz29 *__restrict__ bsum, uint32_t slices,
+                                                         const uint32_t *__restrict__ skip) {
     __shared__ G1Xyzz29i sh[64];   // (field products inlined: these kernels are dependent chains, a call boundary per product is pure latency)
+    if (skip && *skip) return;
     const int b = blockIdx.x + 1, set = blockIdx.y, t = threadIdx.x;
     const G1Xyzz29i *part = (const G1Xyzz29i *)partial;
     G1Xyzz29i acc = G1Xyzz29i::infinity();
@@ -238,8 +245,10 @@ __global__ __launch_bounds__(64) void k_vmsm_bucket_sums(const G1Xyzz29 *__restr
 }
 
 // ---- behind r: sum_b b B_b = sum_{k >= 1} (sum_{b >= k} B_b): suffix scan, tree, and the affine big-endian result ---------------------
-__global__ __launch_bounds__(256) void k_vmsm_weighted(const G1Xyzz29 *__restrict__ bsum, uint8_t *__restrict__ out96, int32_t *__restrict__ inf) {
+__global__ __launch_bounds__(256) void k_vmsm_weighted(const G1Xyzz29 *__restrict__ bsum, uint8_t *__restrict__ out96, int32_t *__restrict__ inf,
+                                                       const uint32_t *__restrict__ skip) {
     __shared__ G1Xyzz29i sh[256];
+    if (skip && *skip) return;
     const int set = blockIdx.x, b = threadIdx.x;
     G1Xyzz29i v = b >= 1 ? ((const G1Xyzz29i *)bsum)[set * 256 + b] : G1Xyzz29i::infinity();
     sh[b] = v;
@@ -276,13 +285,13 @@ __global__ __launch_bounds__(256) void k_vmsm_weighted(const G1Xyzz29 *__restric
     raw_to_be<12>(o + 48, raw);
 }
 
-void launch_vmsm_reduce(const G1Xyzz29 *partial, G1Xyzz29 *bsum, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st) {
+void launch_vmsm_reduce(const G1Xyzz29 *partial, G1Xyzz29 *bsum, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st, const uint32_t *skip) {
     {
         ProfScope p("k_vmsm_bucket_sums", st);
-        hipLaunchKernelGGL(k_vmsm_bucket_sums, dim3(255, 3), dim3(64), 0, st, partial, bsum, (uint32_t)vmsm_slices(n));
+        hipLaunchKernelGGL(k_vmsm_bucket_sums, dim3(255, 3), dim3(64), 0, st, partial, bsum, (uint32_t)vmsm_slices(n), skip);
     }
     ProfScope p("k_vmsm_weighted", st);
-    hipLaunchKernelGGL(k_vmsm_weighted, dim3(3), dim3(256), 0, st, bsum, out96, inf);
+    hipLaunchKernelGGL(k_vmsm_weighted, dim3(3), dim3(256), 0, st, bsum, out96, inf, skip);
 }
 
 // ---- the transcript, assembled where its pieces are (device-resident verification) -----------------------------------------------------
