@@ -744,6 +744,8 @@ static bool launch_direct_t(const DirectPlanRt &plan, const uint64_t *table, siz
         }
         {
             ProfScope p("k_commit_tail", st);
+            // (tests/test_gpu_full_chunk_flags.py runs flagged blobs through BOTH instantiations and relies on this condition to reach them:
+            // 1024 blobs on a settings object with one context take <true>, 1023 take <false>)
             if (n_blobs >= 1024 && !fill)   // a chip's worth of blobs and nobody beside us: one wave per SIMD
                 hipLaunchKernelGGL(k_commit_tail<true>, dim3((unsigned)n_blobs), dim3(64), 0, st, (const uint32_t *)lane_scratch, sums, redo, out48,
                                    kDirThreads);

@@ -1,7 +1,10 @@
 """Run by tests/test_gpu_commit_tail.py in fresh processes (the library reads its environment once), one per arm of LWKZG_COMMIT_TAIL:
 commitments and proofs of fixed batches that take one workgroup per blob on the direct table (n >= 512), printed as JSON. The arms --
 k_commit_tail behind the second pass with the clears riding on the parse kernel (shipped; any value but 0), and fold / second pass /
-finalize as launches of their own behind two fill launches (0) -- compute the same group elements and must print the same bytes."""
+finalize as launches of their own behind two fill launches (0) -- compute the same group elements and must print the same bytes.
+The flags_* legs (tests/test_gpu_full_chunk_flags.py reads them) run tests/flag_cases.py's batches, whose special blobs raise the redo flag
+in the accumulation or in the fold, on the launch sets a FULL chunk takes: a fresh process has no second context, so nothing is ever
+"busy beside us" and 1024 blobs take the one-wave-per-SIMD builds (k_commit_tail<true>, k_direct_fold_lanes_asm_alone)."""
 import ctypes as C
 import json
 import os
@@ -14,34 +17,13 @@ import torch  # noqa: E402
 import blobs as B  # noqa: E402
 import lambdaworks_kzg_amd as K  # noqa: E402
 from lambdaworks_kzg_amd import capi  # noqa: E402
+from flag_cases import fold_collision_scalars, full_chunk_batch  # noqa: E402
 
 R = B.R
 SIZES = (512, 513, 1024, 1500)
 # scalar sets that make lanes meet P = +-Q on a setup whose 4096 points are all the generator (tests/test_gpu_setups_unstructured.py)
 ADVERSARIAL = [[1] * 4096, [1, R - 1] * 2048, [3] * 4096, [(1 << 16) + 1] * 4096, list(range(1, 4097)), [R - 1] * 4096, [0] * 4095 + [5],
                [2, 2, R - 4, 7] * 1024]
-TAU = 1337   # the secret of tests/golden/trusted_setup.txt
-# (a, b, others random): lanes a and b of a blob's one workgroup end with equal (odd blobs: opposite) sums and every other scalar of
-# theirs is zero, so the pair meets in the FOLD, not in the accumulation: 3 and 67 are two of the four lane sums one fold thread adds in
-# sequence, 5 and 37 meet at the first level of the tree, 5 and 6 at its last, 200 and 9 in between
-FOLD_PAIRS = [(3, 67, True), (5, 37, True), (5, 6, False), (200, 9, False)]
-
-
-def fold_collision_scalars(blob):
-    """scalars of blob `blob` of the fold-collision batch (one workgroup per blob: lane t owns the scalars t, t + 256, ...)"""
-    import random
-    rnd = random.Random(88000 + blob)
-    a, b, others = FOLD_PAIRS[(blob // 2) % len(FOLD_PAIRS)]
-    ss = [0] * 4096
-    if others:   # the lanes of other fold threads carry random sums; they join behind the level where a and b meet
-        for i in range(4096):
-            if (i % 256) % 64 not in (a % 64, b % 64):
-                ss[i] = rnd.randrange(R)
-    ss[a] = rnd.randrange(1, R)
-    ss[b] = ss[a] * pow(TAU, a - b, R) % R       # s_b tau^b = s_a tau^a
-    if blob % 2:
-        ss[b] = (R - ss[b]) % R
-    return ss
 
 
 def _dev(b):
@@ -68,6 +50,46 @@ def _profiled(fn):
     finally:
         capi.profile_enable(False)
     return r, capi.profile_report()
+
+
+FLAG_SEED = 1   # tests/test_flag_cases_cpu.py proves the special blobs of this seed
+
+
+def _flag_legs(ts, tag, out):
+    """flagged blobs on the launch sets of 1024 blobs (the ALONE builds) and of 1023 (the shareable ones; uneven shares of the second
+    pass), each with the library's profile of the call; then an honest batch on the same settings"""
+    for n in (1024, 1023):
+        data, _ = full_chunk_batch(n, FLAG_SEED)
+        (got, bad), prof = _profiled(lambda: _commit_device(ts.ref(), data, n))
+        out["%s_flags_%d" % (tag, n)] = {"commitments": got.hex(), "status_sum": bad, "profile": prof}
+        if n == 1024:
+            honest = B.synthetic_batch(52000 + n, n)
+            (got, bad), prof = _profiled(lambda: _commit_device(ts.ref(), honest, n))
+            out["%s_honest_after_flags_1024" % tag] = {"commitments": got.hex(), "status_sum": bad, "profile": prof}
+    if tag != "default":
+        return
+    # the same scalars as 1024 MSMs over the setup (no parse kernel of the commitment call in front: the flags are cleared by a memset),
+    # and as ONE MSM of 2^22 terms over the tiled setup: no compressed output per tile, so the lane fold is a launch of its own
+    n = 1024
+    data, _ = full_chunk_batch(n, FLAG_SEED)
+    d_in = _dev(data)
+    d_out = torch.zeros(48 * n, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+
+    def lincomb():
+        capi.g1_lincomb_setup_device(d_out.data_ptr(), d_in.data_ptr(), n, ts)
+        torch.cuda.synchronize()
+        return bytes(d_out.cpu().numpy().tobytes())
+    got, prof = _profiled(lincomb)
+    out["lincomb_flags_1024"] = {"commitments": got.hex(), "status_sum": 0, "profile": prof}
+    d_one = torch.zeros(48, dtype=torch.uint8, device="cuda")
+
+    def tiled():
+        capi.g1_msm_tiled_device(d_one.data_ptr(), d_in.data_ptr(), n * 4096, ts)
+        torch.cuda.synchronize()
+        return bytes(d_one.cpu().numpy().tobytes())
+    got, prof = _profiled(tiled)
+    out["tiled_flags_1024"] = {"commitments": got.hex(), "status_sum": 0, "profile": prof}
 
 
 def main():
@@ -97,6 +119,7 @@ def main():
             K.compute_blob_kzg_proof_batch_device(d_proof.data_ptr(), d_blobs.data_ptr(), d_comm.data_ptr(), n, ts)
             torch.cuda.synchronize()
             out["proofs_1024"] = bytes(d_proof.cpu().numpy().tobytes()).hex()
+        _flag_legs(ts, tag, out)
 
     # equal and opposite lane sums inside the fold (the flag is raised behind the second pass), on the 14-bit table
     n = 512
@@ -135,6 +158,11 @@ def main():
     data = B.synthetic_batch(53000, n, big_endian=False)
     got, bad = _commit_device(ts.ref(), data, n)
     out["ckzg_lagrange_512"] = {"commitments": got.hex(), "status_sum": bad}
+    # the Lagrange-form twins of the flagged batch: the same collisions among the points [l_i(tau)]G (the clears are memsets here)
+    n = 1024
+    data, _ = full_chunk_batch(n, FLAG_SEED, lagrange=True)
+    (got, bad), prof = _profiled(lambda: _commit_device(ts.ref(), data, n))
+    out["ckzg_lagrange_flags_1024"] = {"commitments": got.hex(), "status_sum": bad, "profile": prof}
     ts.free()
     print(json.dumps(out))
 

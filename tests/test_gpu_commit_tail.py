@@ -3,6 +3,7 @@ launch (direct.hip: k_commit_tail -- fold, inversion and compression; the status
 its way) against the launch set it replaces (LWKZG_COMMIT_TAIL=0: two fill launches, parse, accumulate, fold, second pass, finalize), in
 fresh processes. Both arms compute the same group elements and compress them: every byte must agree, and a sample is held against
 the CPU oracle and the closed forms. tests/commit_tail_worker.py is what each process runs."""
+import functools
 import json
 import os
 import subprocess
@@ -16,7 +17,9 @@ from conftest import R, ROOT, tau_closed_form
 pytestmark = pytest.mark.gpu
 
 
-def _run(arm):
+@functools.lru_cache(maxsize=None)
+def run_arm(arm):
+    """the worker's report on one arm; run once per session (tests/test_gpu_full_chunk_flags.py reads the same two reports)"""
     e = dict(os.environ, LWKZG_EXPERIMENTAL="1", LWKZG_COMMIT_TAIL=str(arm))
     e.pop("LWKZG_DIRECT_BITS", None)
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "tests", "commit_tail_worker.py")], env=e).decode()
@@ -25,7 +28,7 @@ def _run(arm):
 
 @pytest.fixture(scope="module")
 def arms():
-    return {arm: _run(arm) for arm in (0, 1)}
+    return {arm: run_arm(arm) for arm in (0, 1)}
 
 
 def _without_profiles(r):
@@ -83,7 +86,7 @@ def test_ckzg_mode_on_the_lagrange_form_against_the_oracle(arms, oracle, oracle_
 def test_pairs_that_meet_in_the_fold_are_repaired_in_the_tail(arms, oracle):
     """equal and opposite lane sums raise the flag in the fold, behind the second pass: the tail wave folds that blob again with the
     complete addition. Every commitment against the closed form, and the profiles of the two arms show which launch did the repair."""
-    from commit_tail_worker import fold_collision_scalars
+    from flag_cases import fold_collision_scalars
     got = _split(arms[1]["fold_collisions_512"]["commitments"])
     assert len(got) == 512
     bad = [b for b in range(512) if got[b] != tau_closed_form(oracle, fold_collision_scalars(b))]

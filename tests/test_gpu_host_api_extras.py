@@ -67,13 +67,13 @@ def test_default_engine_exactly_one_colliding_lane_per_blob(K, oracle):
     row equal / opposite to its accumulator, late in its walk; the redo pass must put every such blob right (closed form).
     tests/test_gpu_parity.py runs the same on the 10 / 12 / 14 / 15 / 16-bit tables."""
     import random
-    from test_gpu_parity import _one_colliding_lane_blob
+    from flag_cases import one_colliding_lane_blob
     ts = K.TrustedSetup.from_file(SETUP_PATH)
     try:
         c = ts.direct_table_bits()
         assert c in (10, 11, 12, 13)
         rnd = random.Random(4099)
-        sets = [_one_colliding_lane_blob(rnd, c, negate=(b % 2 == 1)) for b in range(512)]
+        sets = [one_colliding_lane_blob(rnd, c, negate=(b % 2 == 1)) for b in range(512)]
         data = b"".join(b"".join(x.to_bytes(32, "big") for x in ss) for ss in sets)
         got = K.blob_to_kzg_commitment_batch(data, ts)
         bad = [b for b in range(len(sets)) if got[b] != tau_closed_form(oracle, sets[b])]

@@ -723,23 +723,6 @@ def test_direct_adversarial_digits_closed_form(K, direct_setup, oracle):
         assert g == tau_closed_form(oracle, ss)
 
 
-def _one_colliding_lane_blob(rnd, c, negate):
-    """Random full-range scalars, except that ONE lane of the direct kernel meets a table row equal to (negate: opposite to) its
-    accumulator, once, late: with P_k = [tau^k]G, s_i = +-e tau^2048 (i < 256: the lane's first scalar in every launch geometry),
-    s_(i + 256 m) = 0 for m = 1 .. 7 (skipped), s_(i + 2048) = e -- after the 255 bits of s_i the lane holds +-[e]P_(i + 2048) and the
-    next row it gathers is [e]P_(i + 2048)."""
-    ss = [rnd.randrange(R) for _ in range(4096)]
-    i = rnd.randrange(256)
-    e = rnd.randrange(1, 1 << (c - 1))
-    for m in range(1, 8):
-        ss[i + 256 * m] = 0
-    ss[i + 2048] = e
-    ss[i] = e * pow(TAU, 2048, R) % R
-    if negate:
-        ss[i] = (R - ss[i]) % R
-    return ss
-
-
 @pytest.mark.parametrize("n", [8, 40, 200, 1024])
 def test_direct_exactly_one_colliding_lane_per_blob(K, direct_setup, oracle, n):
     """the hand-scheduled accumulation has no P = +-Q branches; a lane that meets one must raise its blob's redo flag so
@@ -748,13 +731,38 @@ def test_direct_exactly_one_colliding_lane_per_blob(K, direct_setup, oracle, n):
     of k MOD0 for k >= 17, passes this test too: with the row coordinates as the table build leaves them -- Montgomery outputs,
     below p but for one in about a thousand -- P = U2 - X1 stays under 17 p; the missed case needs a row coordinate >= p, which
     tests/test_direct_asm_cpu.py produces on the simulated lane. What this test pins is the whole redo path, one lane at a time.)"""
+    from flag_cases import one_colliding_lane_blob
     ts, c = direct_setup
     rnd = random.Random(4100 + n + c)
-    sets = [_one_colliding_lane_blob(rnd, c, negate=(b % 2 == 1)) for b in range(n)]
+    sets = [one_colliding_lane_blob(rnd, c, negate=(b % 2 == 1)) for b in range(n)]
     data = b"".join(b"".join(x.to_bytes(32, "big") for x in ss) for ss in sets)
     got = K.blob_to_kzg_commitment_batch(data, ts)
     bad = [b for b in range(n) if got[b] != tau_closed_form(oracle, sets[b])]
     assert not bad, (len(bad), bad[:8])
+
+
+def test_direct_flagged_blobs_in_a_full_chunk_device_resident(K, direct_setup, bucket_setup, oracle):
+    """The test above never launches more than 512 blobs at once (a host-pointer call is cut into slices of half a chunk). Here 1024
+    device-resident blobs go out as ONE launch set -- k_commit_tail<true>, four flags to a row of the second pass -- on every table
+    width, the 16-bit table `bench.py` times among them: tests/flag_cases.py's batch, whose special blobs raise the flag in the
+    accumulation, in the fold, or in both (tests/test_flag_cases_cpu.py proves that). Special blobs, their neighbours and a sample
+    against the closed form; ALL blobs against the bucket engine (an independent algorithm), compared on the device."""
+    import torch
+    from flag_cases import full_chunk_batch, wrong_blobs
+    ts, _ = direct_setup
+    n = 1024
+    data, specials = full_chunk_batch(n, 1)
+    d_blobs = _dev(data)
+    d_got = torch.zeros(48 * n, dtype=torch.uint8, device="cuda")
+    d_want = torch.zeros(48 * n, dtype=torch.uint8, device="cuda")
+    d_status = torch.full((2 * n,), 7, dtype=torch.int32, device="cuda")
+    K.blob_to_kzg_commitment_batch_device(d_got.data_ptr(), d_blobs.data_ptr(), n, ts, None, d_status.data_ptr())
+    K.blob_to_kzg_commitment_batch_device(d_want.data_ptr(), d_blobs.data_ptr(), n, bucket_setup, None, d_status[n:].data_ptr())
+    torch.cuda.synchronize()
+    assert int(d_status.abs().sum()) == 0
+    bad = wrong_blobs(oracle, data, specials, _host(d_got))
+    assert not bad, (len(bad), bad[:8])
+    assert torch.equal(d_got, d_want), torch.nonzero((d_got != d_want).view(n, 48).any(dim=1)).flatten()[:8].tolist()
 
 
 @pytest.mark.parametrize("n", [1, 3, 64, 200, 700, 1024])
