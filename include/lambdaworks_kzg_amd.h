@@ -416,8 +416,9 @@ C_KZG_RET lwkzg_verify_shards_finish(bool *ok, const uint8_t *partials /* n_shar
  *   lwkzg_verifier_wait     until pending == 0.
  *   lwkzg_verifier_free     waits first; NULL is fine. free_trusted_setup on settings that still have verifiers waits for their calls in
  *                           flight; such a verifier answers C_KZG_BADARGS to further enqueues and is still freed with this call.
- * Not covered: host-pointer batches (they are upload-bound), lwkzg_multi_*, the cell verifications (they de-duplicate commitments on the
- * host mid-call), and stream capture -- enqueue on a capturing stream is not supported. With the experiment arm LWKZG_VERIFY_MSM=0 the
+ * Not covered: host-pointer batches (they are upload-bound), lwkzg_multi_*, the per-item verifications, and stream capture -- enqueue on
+ * a capturing stream is not supported. The cell proof batch has a verifier of its own: lwkzg_cell_verifier_* below, which groups the
+ * commitments on the GPU instead of de-duplicating them on the host mid-call. With the experiment arm LWKZG_VERIFY_MSM=0 the
  * enqueue runs the synchronous call and completes *result before it returns (first_bad is then not reported). */
 #define LWKZG_VERIFIER_DEPTH 4
 typedef struct {
@@ -576,6 +577,71 @@ C_KZG_RET lwkzg_cell_verify_partials(uint8_t *out, const Bytes48 *commitments, c
  * n > 0, an index >= 128 or an unknown mode: C_KZG_BADARGS. */
 C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
                                           const Bytes48 *proofs, size_t n, int mode);
+
+/* lwkzg_verify_cell_kzg_proof_batch_device without a parked host thread: a CELL VERIFIER takes device-resident cell batches on the
+ * caller's stream and answers each into a LwkzgCellVerifyResult, in stream order. The contract is
+ * lwkzg_verifier_*'s above, line by line; what differs is said here.
+ *   lwkzg_cell_verifier_new      allocates everything a call of up to max_cells items needs: a device block (the batch's buffers and the
+ *                                grouping's table of at least 2 max_cells slots), a pinned block, events, job slots, the settings'
+ *                                workspace for one MSM slot; copies g2_values[0] and g2_values[64] (the settings must carry all 65 G2
+ *                                points); draws the 64-bit seed of the grouping's slot hash; derives the Lagrange form when the settings
+ *                                answer in c-kzg mode. The only call of the five that may allocate or synchronise the device.
+ *                                C_KZG_BADARGS: NULL arguments, max_cells == 0, settings without g2_values; C_KZG_MALLOC: no memory.
+ *   lwkzg_cell_verifier_enqueue  the synchronous device call's inputs (device pointers, 16-byte aligned, produced on `stream`; NULL =
+ *                                already complete), verdict, codes and precedence -- written to *result. It returns once everything is
+ *                                enqueued: no wait for a stream or an event, no allocation (a settings object switched to c-kzg mode
+ *                                AFTER lwkzg_cell_verifier_new derives its Lagrange form inside the first enqueue). The commitments are
+ *                                never brought to the host to be grouped: rows, m and the row and column lists are made by kernels.
+ *                                    any index >= 128       result->rc C_KZG_BADARGS in both modes, decided first whatever else is
+ *                                                           wrong; first_bad the lowest such item
+ *                                    a proof or a distinct commitment that is not a compressed point of G1 (infinity allowed), a cell
+ *                                    element not below r    result->rc the mode's code (C_KZG_ERROR reference, C_KZG_BADARGS c-kzg);
+ *                                                           first_bad the lowest item whose own cell, proof or commitment is at fault
+ *                                                           (a bad commitment counts at the item it was first seen at)
+ *                                    otherwise              result->rc C_KZG_OK, ok the verdict, m the number of distinct commitments,
+ *                                                           partials exactly as lwkzg_cell_verify_partials writes them
+ *                                A rejected batch is an answer: the call returns C_KZG_OK, and nothing behind r runs on its unvalidated
+ *                                points or unchecked indices (partials are then zero). n == 0 completes on the spot with ok = 1 in BOTH
+ *                                modes. Argument and capacity errors (NULL v or result, n above max_cells, NULL inputs with n > 0, freed
+ *                                settings) complete *result on the spot with C_KZG_BADARGS, a failing enqueue with C_KZG_ERROR, and are
+ *                                the call's return value. Up to LWKZG_VERIFIER_DEPTH calls may be in flight per verifier; ONE MORE WAITS
+ *                                FOR THE OLDEST. Context lock, two verifiers on two streams, lwkzg_reserve_streams first: as above.
+ *   lwkzg_cell_verifier_pending / _wait / _free   as lwkzg_verifier_pending / _wait / _free; free_trusted_setup waits for the calls in
+ *                                flight of the settings' cell verifiers too.
+ * Not covered: host-pointer batches, the per-item form, stream capture. */
+typedef struct {
+    int32_t  state;      /* 0 = pending, 1 = complete; written LAST, with release order */
+    int32_t  rc;         /* the C_KZG_RET the synchronous device call would have returned */
+    int32_t  ok;         /* 0 / 1: its *ok */
+    uint32_t first_bad;  /* lowest item at fault, 0xffffffff = none */
+    uint32_t m;          /* distinct commitments (0 when the call completed on the spot) */
+    uint8_t  partials[LWKZG_CELL_VERIFY_PARTIAL_BYTES]; /* as lwkzg_cell_verify_partials writes them; zero unless rc == C_KZG_OK */
+} LwkzgCellVerifyResult;
+typedef struct LwkzgCellVerifier LwkzgCellVerifier;
+C_KZG_RET lwkzg_cell_verifier_new(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_cells);
+C_KZG_RET lwkzg_cell_verifier_enqueue(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, const void *commitments48_dev,
+                                      const void *cell_indices_dev, const void *cells_dev, const void *proofs48_dev, size_t n, void *stream);
+int       lwkzg_cell_verifier_pending(const LwkzgCellVerifier *v);   /* calls enqueued and not yet complete, -1 = bad handle */
+C_KZG_RET lwkzg_cell_verifier_wait(LwkzgCellVerifier *v);            /* until pending == 0 */
+void      lwkzg_cell_verifier_free(LwkzgCellVerifier *v);            /* waits first; NULL is fine */
+/* Host-only test hook: the two host steps of an enqueue back to back on caller-supplied blocks, with the G2 points of *s. No GPU, no
+ * context; *out is complete when it returns. distinct48: the m distinct commitments; digests32: the n per-cell digests; bad_index: the
+ * lowest item with an index >= 128 (0xffffffff: none); status: 2 n fault words -- [i] item i's own (a cell element, its proof),
+ * [n + j] distinct commitment j's; first_item: m words; sums3x97: P | RLP | RLC in the device's order (flag 1 | x 48 | y 48 each);
+ * rli48: the interpolant's commitment, compressed. A rejected batch reads nothing behind what decides it. */
+C_KZG_RET lwkzg_cell_verifier_host_steps(LwkzgCellVerifyResult *out, const uint8_t *distinct48, size_t m, const uint8_t *digests32, size_t n,
+                                         uint32_t bad_index, const int32_t *status, const uint32_t *first_item, const uint8_t *sums3x97,
+                                         const uint8_t *rli48, const KZGSettings *s, int mode);
+/* Test hook: the grouping kernels alone on device inputs (n commitments of 48 bytes, n uint64 indices; the current device), every output
+ * brought to host arrays: rows n, *m_out, distinct48 48 n (the m distinct commitments in order of first occurrence, then infinity
+ * encodings), first_item n (m used), perm_row n / row_off n + 1 (m + 1 used), perm_col n / col_off 129, *bad_index (the lowest i with an
+ * index >= 128, 0xffffffff: none; such items are in no column). The order inside a group of perm_row / perm_col is not defined. seed:
+ * of the keyed slot hash; hash_mask is ANDed with the hash (0xffffffff in a verifier; 0 puts every key on one probe chain).
+ * Synchronous. C_KZG_BADARGS: NULL pointers, n == 0; C_KZG_ERROR: the kernels' error word was raised. */
+C_KZG_RET lwkzg_cell_group_device(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, uint32_t *first_item, uint32_t *perm_row,
+                                  uint32_t *row_off, uint32_t *perm_col, uint32_t *col_off, uint32_t *bad_index,
+                                  const void *commitments48_dev, const void *cell_indices_dev, size_t n, uint64_t seed, uint32_t hash_mask,
+                                  void *stream);
 
 /* Per-item cell verification: n independent lwkzg_verify_cell_kzg_proof_batch calls of ONE item each, in one. For every i, ok_out[i]
  * (0/1) and rc_out[i] (a C_KZG_RET) are exactly the (*ok, return code) of the batch call on item i alone, in the mode the settings

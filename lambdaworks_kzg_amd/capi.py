@@ -47,6 +47,12 @@ class VerifyResult(C.Structure):
                 ("r", C.c_uint8 * 32), ("partial", C.c_uint8 * 328)]
 
 
+class CellVerifyResult(C.Structure):
+    """LwkzgCellVerifyResult: where an asynchronous cell verification answers. state is written last (0 = pending, 1 = complete)."""
+    _fields_ = [("state", C.c_int32), ("rc", C.c_int32), ("ok", C.c_int32), ("first_bad", C.c_uint32), ("m", C.c_uint32),
+                ("partials", C.c_uint8 * (32 + 4 * 97))]
+
+
 # every symbol include/lambdaworks_kzg_amd.h declares
 EXPORTED_SYMBOLS = [
     "load_trusted_setup", "load_trusted_setup_file", "free_trusted_setup", "blob_to_kzg_commitment",
@@ -86,6 +92,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_trusted_setup_check",
     "lwkzg_verifier_new", "lwkzg_verifier_enqueue", "lwkzg_verifier_pending", "lwkzg_verifier_wait", "lwkzg_verifier_free",
     "lwkzg_verifier_host_steps",
+    "lwkzg_cell_verifier_new", "lwkzg_cell_verifier_enqueue", "lwkzg_cell_verifier_pending", "lwkzg_cell_verifier_wait",
+    "lwkzg_cell_verifier_free", "lwkzg_cell_verifier_host_steps", "lwkzg_cell_group_device",
 ]
 
 _lib = None
@@ -173,6 +181,16 @@ def lib():
     l.lwkzg_verifier_free.argtypes = [vp]
     l.lwkzg_verifier_free.restype = None
     l.lwkzg_verifier_host_steps.argtypes = [C.POINTER(VerifyResult), C.c_char_p, sz, C.c_uint32, C.c_char_p, C.c_char_p, ps, ci]
+    pu32 = C.POINTER(C.c_uint32)
+    l.lwkzg_cell_verifier_new.argtypes = [C.POINTER(vp), ps, sz]
+    l.lwkzg_cell_verifier_enqueue.argtypes = [vp, C.POINTER(CellVerifyResult), vp, vp, vp, vp, sz, vp]
+    l.lwkzg_cell_verifier_pending.argtypes = [vp]
+    l.lwkzg_cell_verifier_wait.argtypes = [vp]
+    l.lwkzg_cell_verifier_free.argtypes = [vp]
+    l.lwkzg_cell_verifier_free.restype = None
+    l.lwkzg_cell_verifier_host_steps.argtypes = [C.POINTER(CellVerifyResult), C.c_char_p, sz, C.c_char_p, sz, C.c_uint32, pi32, pu32,
+                                                 C.c_char_p, C.c_char_p, ps, ci]
+    l.lwkzg_cell_group_device.argtypes = [pu32, pu32, C.c_char_p, pu32, pu32, pu32, pu32, pu32, pu32, vp, vp, sz, C.c_uint64, C.c_uint32, vp]
     l.lwkzg_release_context.argtypes = [ps]
     l.lwkzg_reserve.argtypes = [ps, sz]
     l.lwkzg_reserve_streams.argtypes = [ps, sz, ci]
@@ -986,6 +1004,74 @@ def verifier_host_steps(records, n, first_bad, sums3x97, ysum32, settings_ref, m
     _check("lwkzg_verifier_host_steps",
            lib().lwkzg_verifier_host_steps(C.byref(res), records, n, first_bad, sums3x97, ysum32, settings_ref, mode))
     return res
+
+
+class CellVerifier:
+    """lwkzg_cell_verifier_*: device-resident cell proof batch verifications that do not block the calling thread. enqueue returns a
+    CellVerifyResult whose state turns 1 once rc / ok / first_bad / m / partials are final; the verifier keeps every result it handed
+    out alive."""
+
+    def __init__(self, ts, max_cells):
+        self.ts = ts   # the verifier's device scratch belongs to the setup's context
+        self.h = C.c_void_p()
+        self._results = []
+        _check("lwkzg_cell_verifier_new", lib().lwkzg_cell_verifier_new(C.byref(self.h), ts.ref(), max_cells))
+
+    def enqueue(self, comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream=None):
+        """returns at once; raises KzgError (its .result is the completed CellVerifyResult) for what the call itself refuses"""
+        res = CellVerifyResult()
+        self._results = [r for r in self._results if r.state != 1][-4 * VERIFIER_DEPTH:] + [res]
+        rc = lib().lwkzg_cell_verifier_enqueue(self.h, C.byref(res), comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream)
+        if rc != C_KZG_OK:
+            err = KzgError("lwkzg_cell_verifier_enqueue", rc)
+            err.result = res
+            raise err
+        return res
+
+    def pending(self):
+        return lib().lwkzg_cell_verifier_pending(self.h)
+
+    def wait(self):
+        _check("lwkzg_cell_verifier_wait", lib().lwkzg_cell_verifier_wait(self.h))
+
+    def free(self):
+        if self.h:
+            lib().lwkzg_cell_verifier_free(self.h)   # waits for the calls in flight first
+            self.h = C.c_void_p()
+            self._results = []
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def cell_verifier_host_steps(distinct48, m, digests32, n, bad_index, status, first_item, sums3x97, rli48, settings_ref, mode):
+    """test hook (host only): the two host steps of CellVerifier.enqueue on caller-supplied blocks; status: 2 n fault words (items, then
+    distinct commitments) or None, first_item: m indices or None. Returns the completed CellVerifyResult"""
+    res = CellVerifyResult()
+    st = (C.c_int32 * len(status))(*status) if status is not None else None
+    fi = (C.c_uint32 * len(first_item))(*first_item) if first_item is not None else None
+    _check("lwkzg_cell_verifier_host_steps",
+           lib().lwkzg_cell_verifier_host_steps(C.byref(res), distinct48, m, digests32, n, bad_index, st, fi, sums3x97, rli48, settings_ref,
+                                                mode))
+    return res
+
+
+def cell_group_device(comm_ptr, indices_ptr, n, seed, hash_mask=0xffffffff, stream=None):
+    """test hook: the grouping kernels of a cell verifier on DEVICE inputs (48 n commitment bytes, n uint64 indices). Returns a dict:
+    rows, m, distinct (48 n bytes, padded with infinity encodings), first_item (m), perm_row, row_off (m + 1), perm_col, col_off (129),
+    bad_index. The order inside a group of perm_row / perm_col is not defined."""
+    u32 = C.c_uint32
+    rows, first, perm_row, row_off, perm_col = (u32 * n)(), (u32 * n)(), (u32 * n)(), (u32 * (n + 1))(), (u32 * n)()
+    col_off, m, bad = (u32 * 129)(), u32(0), u32(0)
+    distinct = C.create_string_buffer(48 * n)
+    _check("lwkzg_cell_group_device",
+           lib().lwkzg_cell_group_device(rows, C.byref(m), distinct, first, perm_row, row_off, perm_col, col_off, C.byref(bad), comm_ptr,
+                                         indices_ptr, n, seed, hash_mask, stream))
+    return {"rows": list(rows), "m": m.value, "distinct": distinct.raw, "first_item": list(first)[:m.value], "perm_row": list(perm_row),
+            "row_off": list(row_off)[:m.value + 1], "perm_col": list(perm_col), "col_off": list(col_off), "bad_index": bad.value}
 
 
 def verify_shards_finish(partials, n_shards, n_total, ts):

@@ -11,8 +11,8 @@
 //    consumes), coefficient t scaled by h_k^-t / 64, and the 128 columns summed into the 64 coefficients of I(X) = sum a_i I_i(X),
 //    written as canonical limbs into one 4096-scalar MSM slot whose other 4032 scalars are zero.
 //
-// Items are grouped by row and by column on the host (a counting sort over the indices it holds anyway): perm_* lists the items
-// of group g at [off[g], off[g + 1]).
+// Items are grouped by row and by column on the host (a counting sort over the indices it holds anyway) or, for an asynchronous
+// verifier, by cell_group.hip on the device: perm_* lists the items of group g at [off[g], off[g + 1]), in any order.
 #include "kernels.h"
 #include "cell_interp.cuh"
 #include "glv.cuh"
@@ -126,7 +126,8 @@ void launch_cellv_digests(const uint8_t *cells, const uint8_t *proofs48, const u
 // for the weights and the column sums; sc_a / sc_b are the split forms of a_i and b_i.
 __global__ __launch_bounds__(64) void k_cellv_scalars(const Fr *__restrict__ pw, const uint64_t *__restrict__ idx, const Fr *__restrict__ tw_fwd,
                                                       Fr *__restrict__ a_mont, uint32_t *__restrict__ sc_a, uint32_t *__restrict__ sc_b,
-                                                      uint32_t n) {
+                                                      uint32_t n, const uint32_t *__restrict__ skip) {
+    if (skip && *skip) return;  // a rejected batch of an asynchronous verifier (cells_verify_async.hip): its indices are unchecked
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fr a = pw[32];
@@ -144,11 +145,15 @@ __global__ __launch_bounds__(64) void k_cellv_scalars(const Fr *__restrict__ pw,
     store_split(sc_b, i, raw);
 }
 
-// w_j = sum of a_i over the items of row j, one wave per row
+// w_j = sum of a_i over the items of row j, one wave per row. m_dev (optional): the number of rows where only the device knows it -- the
+// launch then covers n rows and the workgroups at j >= *m_dev leave (all of a workgroup, before its first barrier, as under skip)
 __global__ __launch_bounds__(64) void k_cellv_row_weights(const Fr *__restrict__ a_mont, const uint32_t *__restrict__ perm_row,
-                                                          const uint32_t *__restrict__ row_off, uint32_t *__restrict__ sc_c) {
+                                                          const uint32_t *__restrict__ row_off, uint32_t *__restrict__ sc_c,
+                                                          const uint32_t *__restrict__ m_dev, const uint32_t *__restrict__ skip) {
     __shared__ Fr sh[64];
+    if (skip && *skip) return;
     const uint32_t j = blockIdx.x, t = threadIdx.x;
+    if (m_dev && j >= *m_dev) return;
     const uint32_t lo = row_off[j], hi = row_off[j + 1];
     Fr acc = Fr::zero();
     for (uint32_t s = lo + t; s < hi; s += 64) acc = acc + a_mont[perm_row[s]];
@@ -165,13 +170,33 @@ __global__ __launch_bounds__(64) void k_cellv_row_weights(const Fr *__restrict__
 }
 
 void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b,
-                          const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t n, size_t m, hipStream_t st) {
+                          const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t n, size_t m, hipStream_t st,
+                          const uint32_t *m_dev, const uint32_t *skip) {
     {
         ProfScope p("k_cellv_scalars", st);
-        hipLaunchKernelGGL(k_cellv_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pw, idx, tw_fwd, a_mont, sc_a, sc_b, (uint32_t)n);
+        hipLaunchKernelGGL(k_cellv_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pw, idx, tw_fwd, a_mont, sc_a, sc_b, (uint32_t)n,
+                           skip);
     }
     ProfScope p("k_cellv_row_weights", st);
-    hipLaunchKernelGGL(k_cellv_row_weights, dim3((unsigned)m), dim3(64), 0, st, (const Fr *)a_mont, perm_row, row_off, sc_c);
+    hipLaunchKernelGGL(k_cellv_row_weights, dim3((unsigned)(m_dev ? n : m)), dim3(64), 0, st, (const Fr *)a_mont, perm_row, row_off, sc_c, m_dev,
+                       skip);
+}
+
+// ---- the fault words of an asynchronous verifier ------------------------------------------------------------------------------------
+// The validation marks item i and distinct commitment i in ONE status word. A verifier reports the lowest item at fault, and a bad
+// commitment counts where it was first seen, so the two are told apart here: fault[i] (on entry the digests' word: a cell element not
+// below r) also takes proof i's verdict, fault[n + j] is distinct commitment j's (the padding behind the m-th is infinity: never bad).
+__global__ __launch_bounds__(256) void k_cellv_fault_words(int32_t *__restrict__ fault, const int32_t *__restrict__ kind_p,
+                                                           const int32_t *__restrict__ kind_c, int bad_code, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (kind_p[i] == 2) fault[i] = bad_code;
+    fault[n + i] = kind_c[i] == 2 ? bad_code : 0;
+}
+
+void launch_cellv_fault_words(int32_t *fault, const int32_t *kind_p, const int32_t *kind_c, int bad_code, size_t n, hipStream_t st) {
+    ProfScope p("k_cellv_fault_words", st);
+    hipLaunchKernelGGL(k_cellv_fault_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fault, kind_p, kind_c, bad_code, (uint32_t)n);
 }
 
 // ---- behind r: the column sums, their interpolation, and the 64 coefficients of I(X) ------------------------------------------------
@@ -182,9 +207,11 @@ void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, F
 // canonical limbs (zero for a column nobody sampled).
 __global__ __launch_bounds__(256) void k_cellv_columns(const uint4 *__restrict__ cells, const Fr *__restrict__ a_mont,
                                                        const uint32_t *__restrict__ perm_col, const uint32_t *__restrict__ col_off,
-                                                       const Fr *__restrict__ tw_inv, Fr *__restrict__ colcoef, int le) {
+                                                       const Fr *__restrict__ tw_inv, Fr *__restrict__ colcoef, int le,
+                                                       const uint32_t *__restrict__ skip) {
     __shared__ Fr part[4][kCellElems];
     __shared__ Fr buf[kCellElems];
+    if (skip && *skip) return;  // (the whole workgroup, before its first barrier; k_cellv_coeffs then reads nothing of colcoef)
     const uint32_t k = blockIdx.x, t = threadIdx.x & 63u, v = threadIdx.x >> 6;
     const uint32_t lo = col_off[k], hi = col_off[k + 1];
     if (lo == hi) {   // (the same for the whole workgroup: no barrier is left behind)
@@ -218,11 +245,12 @@ __global__ __launch_bounds__(256) void k_cellv_columns(const uint4 *__restrict__
     colcoef[kCellElems * k + t] = (sc * c) * buf[t];
 }
 
-// scalar t of the MSM slot: the sum of the 128 columns' coefficient t for t < 64, zero above
-__global__ __launch_bounds__(256) void k_cellv_coeffs(const Fr *__restrict__ colcoef, Fr *__restrict__ slot) {
+// scalar t of the MSM slot: the sum of the 128 columns' coefficient t for t < 64, zero above. Under skip all 4096 scalars are zero: the
+// engine's launch set behind this kernel has no skip argument, so its slot is defined either way
+__global__ __launch_bounds__(256) void k_cellv_coeffs(const Fr *__restrict__ colcoef, Fr *__restrict__ slot, const uint32_t *__restrict__ skip) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     Fr acc = Fr::zero();
-    if (t < (uint32_t)kCellElems) {
+    if (t < (uint32_t)kCellElems && !(skip && *skip)) {
 #pragma unroll 1
         for (int k = 0; k < kCellsPerBlob; k++) acc = acc + colcoef[kCellElems * k + t];
     }
@@ -230,14 +258,14 @@ __global__ __launch_bounds__(256) void k_cellv_coeffs(const Fr *__restrict__ col
 }
 
 void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off, const Fr *tw_inv,
-                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st) {
+                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st, const uint32_t *skip) {
     {
         ProfScope p("k_cellv_columns", st);
         hipLaunchKernelGGL(k_cellv_columns, dim3(kCellsPerBlob), dim3(256), 0, st, (const uint4 *)cells, a_mont, perm_col, col_off, tw_inv,
-                           colcoef, le);
+                           colcoef, le, skip);
     }
     ProfScope p("k_cellv_coeffs", st);
-    hipLaunchKernelGGL(k_cellv_coeffs, dim3(kBlobElems / 256), dim3(256), 0, st, (const Fr *)colcoef, (Fr *)slot_raw);
+    hipLaunchKernelGGL(k_cellv_coeffs, dim3(kBlobElems / 256), dim3(256), 0, st, (const Fr *)colcoef, (Fr *)slot_raw, skip);
 }
 
 }  // namespace lwk

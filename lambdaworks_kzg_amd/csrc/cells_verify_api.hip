@@ -12,8 +12,7 @@
 //            variable-base sums (vmsm.hip); four points come down
 //   host     the pairing check against g2_values[64] (pairing.hip keeps its line table beside the others)
 #include "abi_guard.h"
-#include "carve.h"
-#include "cells_common.h"
+#include "cellv_bufs.h"
 #include "knobs.h"
 
 #include <string.h>
@@ -64,63 +63,14 @@ bool group_items(Grouping &g, const uint8_t *comms, const uint64_t *idx, size_t 
     return true;
 }
 
-// the device side of a batch, carved out of one allocation
-struct Bufs {
-    uint8_t *cells, *proofs, *comm_in, *canon_p, *canon_c, *digests, *out96, *rli48;
-    uint64_t *idx;
-    uint32_t *rows, *perm_row, *row_off, *perm_col, *col_off, *verdict_p, *verdict_c, *sc_a, *sc_b, *sc_c;
-    int32_t *kind_p, *kind_c, *status, *inf;
-    G1Affine29 *pts_p, *pts_c, *tab_p, *tab_c;
-    G1Xyzz29 *vm_tmp, *partial, *bsum;
-    F29<2> *vm_pre;
-    Fr *a_mont, *pw, *colcoef;
-};
-
-size_t carve(Bufs &b, uint8_t *base, size_t cap) {
-    Carver cv(base);
-    cv.take(b.cells, cap * kCellBytes);
-    cv.take(b.proofs, cap * 48);
-    cv.take(b.comm_in, cap * 48);
-    cv.take(b.canon_p, cap * 48);
-    cv.take(b.canon_c, cap * 48);
-    cv.take(b.digests, cap * 32);
-    cv.take(b.out96, 3 * 96);
-    cv.take(b.rli48, 48);
-    cv.take(b.idx, cap * 8);
-    cv.take(b.rows, cap * 4);
-    cv.take(b.perm_row, cap * 4);
-    cv.take(b.row_off, (cap + 1) * 4);
-    cv.take(b.perm_col, cap * 4);
-    cv.take(b.col_off, (kCellsPerBlob + 1) * 4);
-    cv.take(b.verdict_p, cap * 4);
-    cv.take(b.verdict_c, cap * 4);
-    cv.take(b.sc_a, cap * 32);
-    cv.take(b.sc_b, cap * 32);
-    cv.take(b.sc_c, cap * 32);
-    cv.take(b.kind_p, cap * 4);
-    cv.take(b.kind_c, cap * 4);
-    cv.take(b.status, cap * 4);
-    cv.take(b.inf, 3 * 4);
-    cv.take(b.pts_p, cap * sizeof(G1Affine29));
-    cv.take(b.pts_c, cap * sizeof(G1Affine29));
-    cv.take(b.tab_p, cap * kVmsmRows * sizeof(G1Affine29));
-    cv.take(b.tab_c, cap * kVmsmRows * sizeof(G1Affine29));
-    cv.take(b.vm_tmp, cap * 2 * kVmsmSteps * sizeof(G1Xyzz29));
-    cv.take(b.partial, 3 * vmsm_max_slices(cap) * 256 * sizeof(G1Xyzz29));
-    cv.take(b.bsum, 3 * 256 * sizeof(G1Xyzz29));
-    cv.take(b.vm_pre, cap * 2 * kVmsmSteps * sizeof(F29<2>));
-    cv.take(b.a_mont, cap * sizeof(Fr));
-    cv.take(b.pw, 33 * sizeof(Fr));
-    cv.take(b.colcoef, (size_t)kCellsPerBlob * kCellElems * sizeof(Fr));
-    return cv.bytes();
-}
+typedef CellvBufs Bufs;   // the device side of a batch, carved out of one allocation (cellv_bufs.h)
 
 // grow-only, kept with the settings object: no allocation in steady state (caller holds c->mu)
 C_KZG_RET reserve(Ctx *c, size_t n, Bufs &b) {
     if (!c->cellv_ev) LWK_HIP(hipEventCreateWithFlags(&c->cellv_ev, hipEventDisableTiming));
     if (c->cellv.cap < n) {
         size_t bytes = 0;
-        C_KZG_RET rc = grow_reserve(c->cellv, n, 256, [&](size_t cap) { Bufs probe; return bytes = carve(probe, nullptr, cap); }, nullptr);
+        C_KZG_RET rc = grow_reserve(c->cellv, n, 256, [&](size_t cap) { Bufs probe; return bytes = cellv_carve(probe, nullptr, cap); }, nullptr);
         if (rc == C_KZG_ERROR) return rc;   // the wait failed: both buffers are as they were
         if (c->cellv_pin) hipHostFree(c->cellv_pin);
         c->cellv_pin = nullptr;
@@ -134,7 +84,7 @@ C_KZG_RET reserve(Ctx *c, size_t n, Bufs &b) {
             return rc;
         }
     }
-    carve(b, c->cellv.dev, c->cellv.cap);
+    cellv_carve(b, c->cellv.dev, c->cellv.cap);
     return C_KZG_OK;
 }
 

@@ -1,0 +1,62 @@
+// cellv_bufs.h -- the device side of a cell proof batch, carved out of one allocation: shared by the synchronous call
+// (cells_verify_api.hip, the context's grow-only block) and the asynchronous verifier (cells_verify_async.hip, a block of its own).
+#pragma once
+#include "carve.h"
+#include "cells_common.h"
+
+namespace lwk {
+
+struct CellvBufs {
+    uint8_t *cells, *proofs, *comm_in, *canon_p, *canon_c, *digests, *out96, *rli48;
+    uint64_t *idx;
+    uint32_t *rows, *perm_row, *row_off, *perm_col, *col_off, *verdict_p, *verdict_c, *sc_a, *sc_b, *sc_c;
+    int32_t *kind_p, *kind_c, *status, *inf;
+    G1Affine29 *pts_p, *pts_c, *tab_p, *tab_c;
+    G1Xyzz29 *vm_tmp, *partial, *bsum;
+    F29<2> *vm_pre;
+    Fr *a_mont, *pw, *colcoef;
+};
+
+constexpr size_t kCellvPwSlots = 34;   // Fr-sized slots of pw: the 33 powers, then a slot for the asynchronous verifier's skip word
+
+// staging: room for the cells, proofs and indices of a host-pointer call (a verifier reads its inputs where they are)
+inline size_t cellv_carve(CellvBufs &b, uint8_t *base, size_t cap, bool staging = true) {
+    Carver cv(base);
+    cv.take(b.cells, staging ? cap * kCellBytes : 0);
+    cv.take(b.proofs, staging ? cap * 48 : 0);
+    cv.take(b.comm_in, cap * 48);
+    cv.take(b.canon_p, cap * 48);
+    cv.take(b.canon_c, cap * 48);
+    cv.take(b.digests, cap * 32);
+    cv.take(b.out96, 3 * 96);
+    cv.take(b.rli48, 48);
+    cv.take(b.idx, staging ? cap * 8 : 0);
+    cv.take(b.rows, cap * 4);
+    cv.take(b.perm_row, cap * 4);
+    cv.take(b.row_off, (cap + 1) * 4);
+    cv.take(b.perm_col, cap * 4);
+    cv.take(b.col_off, (kCellsPerBlob + 1) * 4);
+    cv.take(b.verdict_p, cap * 4);
+    cv.take(b.verdict_c, cap * 4);
+    cv.take(b.sc_a, cap * 32);
+    cv.take(b.sc_b, cap * 32);
+    cv.take(b.sc_c, cap * 32);
+    cv.take(b.kind_p, cap * 4);
+    cv.take(b.kind_c, cap * 4);
+    cv.take(b.status, cap * 4);
+    cv.take(b.inf, 3 * 4);
+    cv.take(b.pts_p, cap * sizeof(G1Affine29));
+    cv.take(b.pts_c, cap * sizeof(G1Affine29));
+    cv.take(b.tab_p, cap * kVmsmRows * sizeof(G1Affine29));
+    cv.take(b.tab_c, cap * kVmsmRows * sizeof(G1Affine29));
+    cv.take(b.vm_tmp, cap * 2 * kVmsmSteps * sizeof(G1Xyzz29));
+    cv.take(b.partial, 3 * vmsm_max_slices(cap) * 256 * sizeof(G1Xyzz29));
+    cv.take(b.bsum, 3 * 256 * sizeof(G1Xyzz29));
+    cv.take(b.vm_pre, cap * 2 * kVmsmSteps * sizeof(F29<2>));
+    cv.take(b.a_mont, cap * sizeof(Fr));
+    cv.take(b.pw, kCellvPwSlots * sizeof(Fr));
+    cv.take(b.colcoef, (size_t)kCellsPerBlob * kCellElems * sizeof(Fr));
+    return cv.bytes();
+}
+
+}  // namespace lwk

@@ -437,7 +437,10 @@ static void small_proof_host_fn(void *p) {
 
 void ctx_destroy(Ctx *c) {
     if (!c) return;
-    if (!c->is_twin) verifiers_drain(c);   // asynchronous verifiers of these settings (verify_async.hip): their calls in flight complete first
+    if (!c->is_twin) {   // asynchronous verifiers of these settings (verify_async.hip, cells_verify_async.hip): their calls in flight complete first
+        verifiers_drain(c);
+        cell_verifiers_drain(c);
+    }
     hipSetDevice(c->device);
     hipDeviceSynchronize();  // every stream of the context, and the callers' streams that ran its work
     if (Ctx *t = c->twin.load(std::memory_order_acquire)) {

@@ -305,11 +305,48 @@ void launch_cellv_digests(const uint8_t *cells, const uint8_t *proofs48, const u
                           int32_t *status, int bad_code, int le, size_t n, hipStream_t st);
 // pw: as launch_vmsm_scalars takes it. a_mont[i] = r^i (Montgomery); sc_a / sc_b: the split forms of r^i and r^i c_{idx[i]};
 // sc_c[j], j < m: the split form of the sum of r^i over the items perm_row[row_off[j] .. row_off[j + 1])
+// m_dev (nullptr for every synchronous caller): m where only the device knows it (cell_group.hip) -- the weights' launch then covers n
+// rows and m is not read. skip (here and below; nullptr for every synchronous caller): as the vmsm launches' skip word
 void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b,
-                          const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t n, size_t m, hipStream_t st);
+                          const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t n, size_t m, hipStream_t st,
+                          const uint32_t *m_dev = nullptr, const uint32_t *skip = nullptr);
 // slot_raw: 4096 canonical scalars, the first 64 the coefficients of sum_i r^i I_i(X), the rest zero. perm_col / col_off (129 words): the
-// items by column; colcoef: 128 x 64 Fr of scratch
+// items by column; colcoef: 128 x 64 Fr of scratch. Under skip slot_raw is 4096 zero scalars (the MSM behind it takes no skip word)
 void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off, const Fr *tw_inv,
-                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st);
+                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st, const uint32_t *skip = nullptr);
+// cells_verify_async.hip: fault (2 n words) -- [i] keeps the digests' word of item i and takes proof i's verdict, [n + j] is distinct
+// commitment j's -- from the kinds the validation left
+void launch_cellv_fault_words(int32_t *fault, const int32_t *kind_p, const int32_t *kind_c, int bad_code, size_t n, hipStream_t st);
+
+// ---- grouping the items of a cell proof batch on the device (cell_group.hip, pieces in cell_group.cuh)
+// Scratch and outputs of one grouping, all device memory. Capacities for n items over a table of `slots` slots (cell_group.cuh:
+// group_table_slots): table slots words, slot_of n, slot_row slots, row_cnt n, col_cnt 128, head kGroupHeadWords; rows n, first_item n,
+// distinct 48 n, perm_row n, row_off n + 1, perm_col n, col_off 129.
+constexpr int kGroupHeadM = 0, kGroupHeadBad = 1, kGroupHeadErr = 2, kGroupHeadWords = 4;
+struct CellGroupBufs {
+    uint32_t *table, *slot_of, *slot_row;
+    uint32_t *row_cnt, *col_cnt;   // col_cnt is ONE piece with head: col_cnt 128 words | head (a single fill clears them)
+    // [kGroupHeadM] = m; [kGroupHeadBad] = ~(the lowest i with idx[i] >= 128), 0 when there is none (so that the fill's zero means
+    // "none" and the lanes take a maximum); [kGroupHeadErr] != 0: a probe ran out of slots or met a slot no lane had claimed
+    uint32_t *head;
+    uint32_t *rows, *first_item, *perm_row, *row_off, *perm_col, *col_off;
+    uint8_t *distinct;   // the m distinct commitments in order of first occurrence, then infinity encodings up to n
+};
+// the scratch of a grouping of up to cap items out of a Carver (carve.h) -- any type with its take(); the outputs stay the caller's
+template <class Carver_>
+inline void cell_group_carve(CellGroupBufs &g, Carver_ &cv, size_t cap, size_t slots) {
+    cv.take(g.table, slots * 4);
+    cv.take(g.slot_of, cap * 4);
+    cv.take(g.slot_row, slots * 4);
+    cv.take(g.row_cnt, cap * 4);
+    cv.take(g.col_cnt, (128 + kGroupHeadWords) * 4);
+    g.head = (uint32_t *)((uintptr_t)g.col_cnt + 128 * 4);
+    cv.take(g.first_item, cap * 4);
+}
+// n commitments (48 bytes each, 8-byte aligned) and n indices -> rows, m, distinct, first_item and the two lists as group_items
+// (cells_verify_api.hip) makes them on the host; the order inside a group of perm_row / perm_col is not defined. seed / hash_mask: of the
+// slot hash (cell_group.cuh). Six launches and three fills on st; nothing is read back
+void launch_cell_group(const uint8_t *comms48, const uint64_t *idx, size_t n, size_t slots, uint64_t seed, uint32_t hash_mask,
+                       const CellGroupBufs &g, hipStream_t st);
 
 }  // namespace lwk
