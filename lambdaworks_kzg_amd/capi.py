@@ -958,36 +958,37 @@ class VerifyShard:
             pass
 
 
-class Verifier:
-    """lwkzg_verifier_*: device-resident batch verifications that do not block the calling thread. enqueue returns a VerifyResult
-    whose state turns 1 once rc / ok / first_bad / r / partial are final; the verifier keeps every result it handed out alive."""
+class _AsyncVerifier:
+    """what Verifier and CellVerifier share; a kind names the prefix of its C symbols (_PREFIX) and its result type (_RESULT)"""
 
-    def __init__(self, ts, max_blobs):
+    def __init__(self, ts, max_items):
         self.ts = ts   # the verifier's device scratch belongs to the setup's context
         self.h = C.c_void_p()
         self._results = []
-        _check("lwkzg_verifier_new", lib().lwkzg_verifier_new(C.byref(self.h), ts.ref(), max_blobs))
+        _check(self._PREFIX + "new", self._fn("new")(C.byref(self.h), ts.ref(), max_items))
 
-    def enqueue(self, blobs_ptr, comm_ptr, proofs_ptr, n, stream=None):
-        """returns at once; raises KzgError (its .result is the completed VerifyResult) for what the call itself refuses"""
-        res = VerifyResult()
+    def _fn(self, name):
+        return getattr(lib(), self._PREFIX + name)
+
+    def _enqueue(self, *args):
+        res = self._RESULT()
         self._results = [r for r in self._results if r.state != 1][-4 * VERIFIER_DEPTH:] + [res]
-        rc = lib().lwkzg_verifier_enqueue(self.h, C.byref(res), blobs_ptr, comm_ptr, proofs_ptr, n, stream)
+        rc = self._fn("enqueue")(self.h, C.byref(res), *args)
         if rc != C_KZG_OK:
-            err = KzgError("lwkzg_verifier_enqueue", rc)
+            err = KzgError(self._PREFIX + "enqueue", rc)
             err.result = res
             raise err
         return res
 
     def pending(self):
-        return lib().lwkzg_verifier_pending(self.h)
+        return self._fn("pending")(self.h)
 
     def wait(self):
-        _check("lwkzg_verifier_wait", lib().lwkzg_verifier_wait(self.h))
+        _check(self._PREFIX + "wait", self._fn("wait")(self.h))
 
     def free(self):
         if self.h:
-            lib().lwkzg_verifier_free(self.h)   # waits for the calls in flight first
+            self._fn("free")(self.h)   # waits for the calls in flight first
             self.h = C.c_void_p()
             self._results = []
 
@@ -996,6 +997,19 @@ class Verifier:
             self.free()
         except Exception:
             pass
+
+
+class Verifier(_AsyncVerifier):
+    """lwkzg_verifier_*: device-resident batch verifications that do not block the calling thread. enqueue returns a VerifyResult
+    whose state turns 1 once rc / ok / first_bad / r / partial are final; the verifier keeps every result it handed out alive."""
+    _PREFIX, _RESULT = "lwkzg_verifier_", VerifyResult
+
+    def __init__(self, ts, max_blobs):
+        super().__init__(ts, max_blobs)
+
+    def enqueue(self, blobs_ptr, comm_ptr, proofs_ptr, n, stream=None):
+        """returns at once; raises KzgError (its .result is the completed VerifyResult) for what the call itself refuses"""
+        return self._enqueue(blobs_ptr, comm_ptr, proofs_ptr, n, stream)
 
 
 def verifier_host_steps(records, n, first_bad, sums3x97, ysum32, settings_ref, mode):
@@ -1006,45 +1020,18 @@ def verifier_host_steps(records, n, first_bad, sums3x97, ysum32, settings_ref, m
     return res
 
 
-class CellVerifier:
+class CellVerifier(_AsyncVerifier):
     """lwkzg_cell_verifier_*: device-resident cell proof batch verifications that do not block the calling thread. enqueue returns a
     CellVerifyResult whose state turns 1 once rc / ok / first_bad / m / partials are final; the verifier keeps every result it handed
     out alive."""
+    _PREFIX, _RESULT = "lwkzg_cell_verifier_", CellVerifyResult
 
     def __init__(self, ts, max_cells):
-        self.ts = ts   # the verifier's device scratch belongs to the setup's context
-        self.h = C.c_void_p()
-        self._results = []
-        _check("lwkzg_cell_verifier_new", lib().lwkzg_cell_verifier_new(C.byref(self.h), ts.ref(), max_cells))
+        super().__init__(ts, max_cells)
 
     def enqueue(self, comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream=None):
         """returns at once; raises KzgError (its .result is the completed CellVerifyResult) for what the call itself refuses"""
-        res = CellVerifyResult()
-        self._results = [r for r in self._results if r.state != 1][-4 * VERIFIER_DEPTH:] + [res]
-        rc = lib().lwkzg_cell_verifier_enqueue(self.h, C.byref(res), comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream)
-        if rc != C_KZG_OK:
-            err = KzgError("lwkzg_cell_verifier_enqueue", rc)
-            err.result = res
-            raise err
-        return res
-
-    def pending(self):
-        return lib().lwkzg_cell_verifier_pending(self.h)
-
-    def wait(self):
-        _check("lwkzg_cell_verifier_wait", lib().lwkzg_cell_verifier_wait(self.h))
-
-    def free(self):
-        if self.h:
-            lib().lwkzg_cell_verifier_free(self.h)   # waits for the calls in flight first
-            self.h = C.c_void_p()
-            self._results = []
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return self._enqueue(comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream)
 
 
 def cell_verifier_host_steps(distinct48, m, digests32, n, bad_index, status, first_item, sums3x97, rli48, settings_ref, mode):

@@ -17,48 +17,28 @@
 //   caller's stream <--event-- (work enqueued behind the call sees the verdict)
 //
 // Calls on one verifier share its device block and pinned block and run one after the other: on one context by stream order, across
-// the settings' two contexts (pick_ctx) by the verifier's last_done event. The job slots are verifier_ring.h as it stands.
+// the settings' two contexts (pick_ctx) by the verifier's last_done event. The job slots and the protocol of a failing enqueue are
+// verifier_ring.h; the handle's head, the enqueue around enqueue_on, pending / wait / free and the host functions' rules are
+// async_verifier.h, shared with verify_async.hip.
 #include "abi_guard.h"
+#include "async_verifier.h"
 #include "cell_group.cuh"
 #include "cellv_bufs.h"
-#include "engine_internal.h"
-#include "verifier_ring.h"
-
-#include <string.h>
 
 #include <chrono>
 #include <new>
 #include <random>
-#include <set>
 
 namespace lwk {
 
 namespace {
 
 constexpr uint64_t kCellVerifierMagic = 0x4c574b5a43564659ull;  // "LWKZCVFY"
-constexpr uint32_t kNoneBad = 0xffffffffu;
 constexpr size_t kPinPowers = 33 * sizeof(Fr) + 4;   // the powers and, behind them, the skip word: one copy up
 constexpr size_t kPinSums = 3 * 96 + 3 * 4 + 48;     // the three sums, their flags, RLI: 348 bytes down
 
-struct CellVerifier;
-struct CellJob {
-    CellVerifier *v = nullptr;
-    LwkzgCellVerifyResult *res = nullptr;
-    size_t n = 0;
-    int mode = 0;
-    uint32_t first_bad = kNoneBad, m = 0;
-    int32_t rc = 0;         // a rejected batch's code
-    bool failed = false;    // host function 1 could not do its work
-};
-typedef VerifierRing<CellJob, LWKZG_VERIFIER_DEPTH> Ring;
-
-struct CellVerifier {
-    uint64_t magic = kCellVerifierMagic;
-    Ctx *ctx = nullptr;
-    uint64_t ctx_generation = 0;
-    const KZGSettings *s = nullptr;   // read by the enqueuing thread only, and only while the context is live (the mode)
-    int device = 0;
-    size_t cap = 0, slots = 0;
+struct CellVerifier : AsyncVerifier {
+    size_t slots = 0;
     uint64_t seed = 0;                // of the slot hash, drawn once
     uint8_t *dev = nullptr;           // one block: CellvBufs, the grouping's scratch, the fault words
     CellvBufs b;
@@ -68,17 +48,18 @@ struct CellVerifier {
     uint32_t *h_head = nullptr, *h_first = nullptr;
     int32_t *h_fault = nullptr;
     uint8_t *h_dig = nullptr, *h_comm = nullptr, *h_up = nullptr, *h_sums = nullptr;
-    hipEvent_t ev_in = nullptr, ev_fork = nullptr, ev_rows = nullptr, last_done = nullptr;
-    Ctx *last_ctx = nullptr;          // the context whose stream recorded last_done (under enq_mu)
+    hipEvent_t ev_in = nullptr, ev_fork = nullptr, ev_rows = nullptr;
     // g2_values[0] and g2_values[64] of the settings, copied at creation: all the host functions ever see of them
     g2_t g2[65];
     KZGSettings own;
-    std::mutex enq_mu;                // enqueues of one verifier, one at a time; never taken by a host function
-    Ring ring;
+    CellVerifier(Ctx *c, const KZGSettings *s, size_t max_cells) : AsyncVerifier(kCellVerifierMagic, c, s, max_cells) {}
+    void free_own() {
+        if (dev) (void)hipFree(dev);
+        if (pin) (void)hipHostFree(pin);
+        for (hipEvent_t e : {ev_in, ev_fork, ev_rows})
+            if (e) (void)hipEventDestroy(e);
+    }
 };
-
-std::mutex g_cell_verifiers_mu;       // the set below; never taken by a host function
-std::set<CellVerifier *> g_cell_verifiers;
 
 size_t carve_device(CellVerifier *v, uint8_t *base) {
     const size_t used = cellv_carve(v->b, base, v->cap, false);
@@ -104,12 +85,6 @@ size_t carve_pinned(CellVerifier *v, uint8_t *base) {
     cv.take(v->h_up, kPinPowers);
     cv.take(v->h_sums, kPinSums);
     return cv.bytes();
-}
-
-void complete_now(LwkzgCellVerifyResult *res, C_KZG_RET rc, bool ok) {
-    res->rc = (int32_t)rc;
-    res->ok = ok ? 1 : 0;
-    Ring::publish(&res->state);
 }
 
 // the lowest item at fault: an item's own word (a cell element, its proof), or a distinct commitment's at the item it was first seen at
@@ -149,17 +124,16 @@ void r_bytes(uint8_t out32[32], const uint32_t r_raw[8], int mode) {
 }
 
 // ---- the two host functions ------------------------------------------------------------------------------------------------------
-// The rules written above verifier_host_fn1 (verify_async.hip) hold for both: no HIP call, no lock that a thread may hold while it waits
-// for a stream or an event, nothing thrown, the mode and n from the job slot, the caller's KZGSettings never read. What they call keeps
-// to them: cell_batch_challenge and cell_batch_powers hash and multiply; cell_batch_finish's pairing takes fixed_q_lines' cache mutex
-// (pairing.hip), which guards a search and a push_back and is never held across a wait for the GPU or across the lines' computation;
-// its two set_error calls (a NULL g2_values, an interpolant's commitment that is no point) cannot happen with a verifier's own copy of
-// the G2 points and the engine's own compressed output, and would only write the runtime thread's own error text.
+// Their rules are async_verifier.h's. What they call keeps to them: cell_batch_challenge and cell_batch_powers hash and multiply;
+// cell_batch_finish's pairing takes fixed_q_lines' cache mutex (pairing.hip), which guards a search and a push_back and is never held
+// across a wait for the GPU or across the lines' computation; its two set_error calls (a NULL g2_values, an interpolant's commitment
+// that is no point) cannot happen with a verifier's own copy of the G2 points and the engine's own compressed output, and would only
+// write the runtime thread's own error text.
 
 // behind the copies of the head, the fault words, the digests and the padded commitments
 void cell_verifier_host_fn1(void *p) {
-    CellJob *j = (CellJob *)p;
-    CellVerifier *v = j->v;
+    AsyncJob *j = (AsyncJob *)p;
+    CellVerifier *v = static_cast<CellVerifier *>(j->v);
     uint32_t skip = 1;
     try {
         const uint32_t m = v->h_head[kGroupHeadM], bad_index = ~v->h_head[kGroupHeadBad];
@@ -168,9 +142,9 @@ void cell_verifier_host_fn1(void *p) {
             j->failed = true;
         } else {
             uint32_t r_raw[8];
-            if (decide_or_challenge(r_raw, &j->first_bad, &j->rc, v->h_comm, m, v->h_dig, j->n, bad_index, v->h_fault, v->h_first, j->mode)) {
+            if (decide_or_challenge(r_raw, &j->first_bad, &j->code, v->h_comm, m, v->h_dig, j->n, bad_index, v->h_fault, v->h_first, j->mode)) {
                 cell_batch_powers((Fr *)v->h_up, r_raw);
-                r_bytes(j->res->partials, r_raw, j->mode);
+                r_bytes(((LwkzgCellVerifyResult *)j->res)->partials, r_raw, j->mode);
                 skip = 0;
             }
         }
@@ -182,25 +156,20 @@ void cell_verifier_host_fn1(void *p) {
 
 // behind the copy of the three sums and RLI: the pairing, the partials, the state word last, the slot freed
 void cell_verifier_host_fn2(void *p) {
-    CellJob *j = (CellJob *)p;
-    CellVerifier *v = j->v;
-    LwkzgCellVerifyResult *res = j->res;
+    AsyncJob *j = (AsyncJob *)p;
+    CellVerifier *v = static_cast<CellVerifier *>(j->v);
+    LwkzgCellVerifyResult *res = (LwkzgCellVerifyResult *)j->res;
     C_KZG_RET rc = C_KZG_ERROR;
     bool ok = false;
     try {
         if (j->failed) {
             rc = C_KZG_ERROR;
         } else if (j->first_bad != kNoneBad) {
-            rc = (C_KZG_RET)j->rc;
+            rc = (C_KZG_RET)j->code;
         } else {
             uint8_t sums[3][96], rli48[48];
             int infs[3];
-            for (int k = 0; k < 3; k++) {
-                memcpy(sums[k], v->h_sums + 96 * k, 96);
-                int32_t f;
-                memcpy(&f, v->h_sums + 3 * 96 + 4 * k, 4);
-                infs[k] = f;
-            }
+            sums_from_pinned(sums, infs, v->h_sums, v->h_sums + 3 * 96);
             memcpy(rli48, v->h_sums + 3 * 96 + 12, 48);
             rc = cell_batch_finish(&ok, res->partials + 32, sums, infs, rli48, &v->own);
         }
@@ -214,28 +183,13 @@ void cell_verifier_host_fn2(void *p) {
     v->ring.release(j);   // (the verifier may be gone as soon as this returns)
 }
 
-void host_noop_fn(void *) {}
-
-void cell_verifier_destroy(CellVerifier *v) {
-    hipSetDevice(v->device);
-    hipDeviceSynchronize();   // device memory of its own, freed whether or not the context still exists
-    if (v->dev) (void)hipFree(v->dev);
-    if (v->pin) (void)hipHostFree(v->pin);
-    for (hipEvent_t e : {v->ev_in, v->ev_fork, v->ev_rows, v->last_done})
-        if (e) (void)hipEventDestroy(e);
-    v->magic = 0;
-    delete v;
-}
-
 // the workspace a call on context c takes: one MSM slot
 C_KZG_RET reserve_for(Ctx *c) {
     std::lock_guard<std::mutex> lk(c->mu);
     LWK_HIP(hipSetDevice(c->device));
     C_KZG_RET rc = ctx_reserve(c, 1);
     if (rc != C_KZG_OK) return rc;
-    // the runtime's first-use costs of a host function on this stream are paid here, not in the first call
-    if (hipLaunchHostFunc(c->stream, host_noop_fn, nullptr) != hipSuccess) (void)hipGetLastError();
-    (void)hipStreamSynchronize(c->stream);
+    stream_warm_host_fn(c->stream);
     return C_KZG_OK;
 }
 
@@ -260,13 +214,8 @@ C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, 
         return C_KZG_BADARGS;
     }
     ensure_lagrange(c, mode_of(s));
-    CellVerifier *v = new (std::nothrow) CellVerifier();
+    CellVerifier *v = new (std::nothrow) CellVerifier(c, s, max_cells);
     if (!v) return C_KZG_MALLOC;
-    v->ctx = c;
-    v->ctx_generation = c->generation;
-    v->s = s;
-    v->device = c->device;
-    v->cap = max_cells;
     v->slots = group_table_slots(max_cells);
     v->seed = draw_seed(v);
     memset(v->g2, 0, sizeof v->g2);
@@ -296,20 +245,11 @@ C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, 
             carve_pinned(v, v->pin);
         }
     }
-    if (rc != C_KZG_OK) {
-        cell_verifier_destroy(v);
-        return rc == C_KZG_MALLOC ? C_KZG_MALLOC : C_KZG_ERROR;
-    }
-    {
-        std::lock_guard<std::mutex> lk(g_cell_verifiers_mu);
-        g_cell_verifiers.insert(v);
-    }
-    *out = (LwkzgCellVerifier *)v;
-    return C_KZG_OK;
+    return async_verifier_new_end(out, v, rc);
 }
 
 // everything of one call on context c, enqueued; caller holds c->mu. *hf: host functions handed to the runtime so far
-C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, CellJob *j, const uint8_t *comms, const uint64_t *idx, const uint8_t *cells, const uint8_t *proofs,
+C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t *comms, const uint64_t *idx, const uint8_t *cells, const uint8_t *proofs,
                      hipStream_t caller, int *hf) {
     LWK_HIP(hipSetDevice(c->device));
     C_KZG_RET rc = ctx_reserve(c, 1);   // (at once unless this context was made after the verifier)
@@ -320,8 +260,7 @@ C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, CellJob *j, const uint8_t *comms, 
     hipStream_t st = c->stream, side = c->aux[1];
     const uint32_t *d_m = v->g.head + kGroupHeadM;
     uint32_t *d_skip = (uint32_t *)(b.pw + 33);
-    // the verifier's scratch: behind its previous call, whichever of the two contexts ran that
-    if (v->last_ctx && v->last_ctx != c) LWK_HIP(hipStreamWaitEvent(st, v->last_done, 0));
+    if ((rc = async_enqueue_head(v, c)) != C_KZG_OK) return rc;
     if (caller && caller != st) {   // the inputs were produced on the caller's stream
         LWK_HIP(hipEventRecord(v->ev_in, caller));
         LWK_HIP(hipStreamWaitEvent(st, v->ev_in, 0));
@@ -361,72 +300,28 @@ C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, CellJob *j, const uint8_t *comms, 
     LWK_HIP(hipGetLastError());
     LWK_HIP(hipLaunchHostFunc(st, cell_verifier_host_fn2, j));
     *hf = 2;
-    LWK_HIP(hipEventRecord(v->last_done, st));
-    v->last_ctx = c;
-    if (caller && caller != st) LWK_HIP(hipStreamWaitEvent(caller, v->last_done, 0));   // work behind the call sees the verdict
-    return C_KZG_OK;
+    return async_enqueue_tail(v, c, caller);
 }
 
-C_KZG_RET cell_verifier_enqueue_impl(CellVerifier *v, LwkzgCellVerifyResult *res, const uint8_t *comms, const uint64_t *idx, const uint8_t *cells,
-                                     const uint8_t *proofs, size_t n, hipStream_t caller) {
-    if (!res) return C_KZG_BADARGS;
-    memset(res, 0, sizeof *res);   // state = 0
-    res->first_bad = kNoneBad;
-    auto refuse = [&](C_KZG_RET rc) {
-        complete_now(res, rc, false);
-        return rc;
-    };
-    if (!v || v->magic != kCellVerifierMagic) return refuse(C_KZG_BADARGS);
-    if (!ctx_is_live(v->ctx, v->ctx_generation)) {
-        set_error("lwkzg_cell_verifier_enqueue: the verifier's trusted setup is no longer loaded");
-        return refuse(C_KZG_BADARGS);
-    }
-    if (n > v->cap) {
-        set_error("lwkzg_cell_verifier_enqueue: %zu cells, the verifier was created for %zu", n, v->cap);
-        return refuse(C_KZG_BADARGS);
-    }
+C_KZG_RET cell_verifier_enqueue_impl(const LwkzgCellVerifier *handle, LwkzgCellVerifyResult *res, const uint8_t *comms, const uint64_t *idx,
+                                     const uint8_t *cells, const uint8_t *proofs, size_t n, hipStream_t caller) {
+    AsyncVerifier *base;
+    const C_KZG_RET refused = async_enqueue_checks(&base, handle, kCellVerifierMagic, res, n, "lwkzg_cell_verifier_enqueue", "cells");
+    if (refused != C_KZG_OK) return refused;
+    CellVerifier *v = static_cast<CellVerifier *>(base);
     if (n == 0) {   // the consensus specs' and c-kzg-4844 2.x's rule for cells, in both modes
         complete_now(res, C_KZG_OK, true);
         return C_KZG_OK;
     }
-    if (!comms || !idx || !cells || !proofs) return refuse(C_KZG_BADARGS);
+    if (!comms || !idx || !cells || !proofs) return async_refuse(res, C_KZG_BADARGS);
     const int mode = mode_of(v->s);
     ensure_lagrange(v->ctx, mode);   // (a load unless the mode changed to c-kzg after lwkzg_cell_verifier_new)
     std::lock_guard<std::mutex> enq(v->enq_mu);
-    // while a call of this verifier is in flight the next one follows it on the same context (stream order); otherwise the settings'
-    // usual choice for a caller stream
-    Ctx *c = v->last_ctx && v->ring.pending() > 0 ? v->last_ctx : pick_ctx(v->ctx, caller);
-    CellJob *j = v->ring.acquire();   // the one place this call may wait: LWKZG_VERIFIER_DEPTH calls are in flight
-    *j = CellJob();
-    j->v = v;
-    j->res = res;
-    j->n = n;
-    j->mode = mode;
-    int hf = 0;
-    C_KZG_RET rc;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        rc = enqueue_on(v, c, j, comms, idx, cells, proofs, caller, &hf);
-        // a failing enqueue, and only that: whatever was handed to the runtime runs before the slot and the result are touched again
-        if (rc != C_KZG_OK && hf) (void)hipStreamSynchronize(c->stream);
-    }
-    if (rc == C_KZG_OK) return C_KZG_OK;
-    (void)hipGetLastError();
-    if (hf < 2) {   // (behind host function 2 the result is complete and the slot free already)
-        complete_now(res, C_KZG_ERROR, false);
-        v->ring.release(j);
-    }
-    return C_KZG_ERROR;
+    return async_enqueue(v, res, n, mode, caller,
+                         [&](Ctx *c, AsyncJob *j, int *hf) { return enqueue_on(v, c, j, comms, idx, cells, proofs, caller, hf); });
 }
 
 }  // namespace
-
-void cell_verifiers_drain(const Ctx *c) {
-    if (!c) return;
-    std::lock_guard<std::mutex> lk(g_cell_verifiers_mu);
-    for (CellVerifier *v : g_cell_verifiers)
-        if (v->ctx == c) v->ring.wait();
-}
 
 }  // namespace lwk
 
@@ -441,34 +336,14 @@ C_KZG_RET lwkzg_cell_verifier_new(LwkzgCellVerifier **out, const KZGSettings *s,
 C_KZG_RET lwkzg_cell_verifier_enqueue(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, const void *commitments48_dev,
                                       const void *cell_indices_dev, const void *cells_dev, const void *proofs48_dev, size_t n, void *stream) {
     return guarded("lwkzg_cell_verifier_enqueue", [&] {
-        return cell_verifier_enqueue_impl((CellVerifier *)v, result, (const uint8_t *)commitments48_dev, (const uint64_t *)cell_indices_dev,
+        return cell_verifier_enqueue_impl(v, result, (const uint8_t *)commitments48_dev, (const uint64_t *)cell_indices_dev,
                                           (const uint8_t *)cells_dev, (const uint8_t *)proofs48_dev, n, (hipStream_t)stream);
     });
 }
 
-int lwkzg_cell_verifier_pending(const LwkzgCellVerifier *v) {
-    CellVerifier *w = (CellVerifier *)v;
-    if (!w || w->magic != kCellVerifierMagic) return -1;
-    return w->ring.pending();
-}
-
-C_KZG_RET lwkzg_cell_verifier_wait(LwkzgCellVerifier *v) {
-    CellVerifier *w = (CellVerifier *)v;
-    if (!w || w->magic != kCellVerifierMagic) return C_KZG_BADARGS;
-    w->ring.wait();
-    return C_KZG_OK;
-}
-
-void lwkzg_cell_verifier_free(LwkzgCellVerifier *v) {
-    CellVerifier *w = (CellVerifier *)v;
-    if (!w || w->magic != kCellVerifierMagic) return;
-    w->ring.wait();
-    {
-        std::lock_guard<std::mutex> lk(g_cell_verifiers_mu);
-        g_cell_verifiers.erase(w);
-    }
-    cell_verifier_destroy(w);
-}
+int lwkzg_cell_verifier_pending(const LwkzgCellVerifier *v) { return async_verifier_pending(v, kCellVerifierMagic); }
+C_KZG_RET lwkzg_cell_verifier_wait(LwkzgCellVerifier *v) { return async_verifier_wait(v, kCellVerifierMagic); }
+void lwkzg_cell_verifier_free(LwkzgCellVerifier *v) { async_verifier_free<CellVerifier>(v, kCellVerifierMagic); }
 
 C_KZG_RET lwkzg_cell_verifier_host_steps(LwkzgCellVerifyResult *out, const uint8_t *distinct48, size_t m, const uint8_t *digests32, size_t n,
                                          uint32_t bad_index, const int32_t *status, const uint32_t *first_item, const uint8_t *sums3x97,
@@ -477,10 +352,7 @@ C_KZG_RET lwkzg_cell_verifier_host_steps(LwkzgCellVerifyResult *out, const uint8
     memset(out, 0, sizeof *out);
     out->first_bad = kNoneBad;
     out->m = (uint32_t)m;
-    auto refuse = [&] {
-        complete_now(out, C_KZG_BADARGS, false);
-        return C_KZG_BADARGS;
-    };
+    auto refuse = [&] { return async_refuse(out, C_KZG_BADARGS); };
     if (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG) return refuse();
     if (n == 0 || m == 0 || m > n) return refuse();
     // what each outcome reads: a bad index nothing; a fault word the words and first_item; an honest batch everything
@@ -501,14 +373,7 @@ C_KZG_RET lwkzg_cell_verifier_host_steps(LwkzgCellVerifyResult *out, const uint8
         r_bytes(out->partials, r_raw, mode);
         uint8_t sums[3][96];
         int infs[3];
-        bool well_formed = true;
-        for (int k = 0; k < 3; k++) {
-            const uint8_t *p = sums3x97 + 97 * k;
-            infs[k] = p[0] == 1;
-            well_formed = well_formed && p[0] <= 1;
-            memcpy(sums[k], p + 1, 96);
-        }
-        rc = well_formed ? cell_batch_finish(&ok, out->partials + 32, sums, infs, rli48, s) : C_KZG_BADARGS;
+        rc = sums_from_97(sums, infs, sums3x97) ? cell_batch_finish(&ok, out->partials + 32, sums, infs, rli48, s) : C_KZG_BADARGS;
     } catch (...) {
         rc = C_KZG_ERROR;
     }

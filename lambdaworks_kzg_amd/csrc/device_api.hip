@@ -1,6 +1,6 @@
 // device_api.hip -- the device-resident C ABI: the reserve calls and every lwkzg_*_device compute entry point (device pointers in and out,
 // asynchronous on the caller's stream).
-#include "engine_internal.h"
+#include "async_verifier.h"
 
 #include <string.h>
 
@@ -14,7 +14,6 @@ extern "C" {
 // everything a device-resident call of up to max_batch blobs would otherwise allocate or synchronise for on first use: the workspace,
 // the pinned staging of the host-assisted challenge paths (once, at its final size), and -- for settings that answer in c-kzg mode --
 // the Lagrange form of the setup
-static void host_noop_fn(void *) {}
 static C_KZG_RET reserve_ctx(Ctx *c, size_t max_batch) {
     std::lock_guard<std::mutex> lk(c->mu);
     LWK_HIP(hipSetDevice(c->device));
@@ -31,9 +30,7 @@ static C_KZG_RET reserve_ctx(Ctx *c, size_t max_batch) {
         host_pool_warm();   // the host threads exist and have run once
         // the runtime's own first-use costs of a host function on each helper stream (its callback machinery: the first host-assisted
         // call of a process took ~6 ms longer than the second, gpurun_out r05/gpu23) are paid here too
-        for (hipStream_t hs : {c->aux[0], c->aux[1], c->vstream})
-            if (hipLaunchHostFunc(hs, host_noop_fn, nullptr) != hipSuccess) (void)hipGetLastError();
-        for (hipStream_t hs : {c->aux[0], c->aux[1], c->vstream}) (void)hipStreamSynchronize(hs);
+        for (hipStream_t hs : {c->aux[0], c->aux[1], c->vstream}) stream_warm_host_fn(hs);
     }
     // a caller that announces batches of more than a chunk gets the device-side double buffer of the long host-pointer batches now (256 MiB)
     // instead of inside its first long call; the twin context never runs host-pointer batches

@@ -472,10 +472,6 @@ C_KZG_RET verify_async_verdict(bool *ok, uint8_t *partial, const uint8_t sums96[
                                const KZGSettings *own);
 C_KZG_RET verify_batch_device_full(bool *ok, uint8_t r_be[32], uint8_t *partial, const uint8_t *d_blobs, const uint8_t *d_comm,
                                    const uint8_t *d_proofs, size_t n, const KZGSettings *s, int mode, hipStream_t caller);
-// verify_async.hip: the calls in flight of every verifier of this context have completed (free_trusted_setup, before the context goes)
-void verifiers_drain(const Ctx *c);
-// cells_verify_async.hip: the same for the cell verifiers
-void cell_verifiers_drain(const Ctx *c);
 
 // G2 / pairing side (g2_pairing.hip, host only)
 bool g2_fill_values(g2_t *out65, const uint8_t *g2_bytes, size_t n2);

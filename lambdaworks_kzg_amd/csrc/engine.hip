@@ -8,6 +8,7 @@
 // verify_front.hip (the verification front), control.hip (the process-wide controls), load.hip (setup load, free and image),
 // host_api.hip (the host-pointer batch ABI), tables.hip (the two forms of the setup and their direct tables), device_api.hip
 // (the reserve calls and the _device entry points).
+#include "async_verifier.h"
 #include "engine_internal.h"
 #include "hostfp.h"
 
@@ -437,10 +438,7 @@ static void small_proof_host_fn(void *p) {
 
 void ctx_destroy(Ctx *c) {
     if (!c) return;
-    if (!c->is_twin) {   // asynchronous verifiers of these settings (verify_async.hip, cells_verify_async.hip): their calls in flight complete first
-        verifiers_drain(c);
-        cell_verifiers_drain(c);
-    }
+    if (!c->is_twin) async_verifiers_drain(c);   // asynchronous verifiers of these settings, of either kind: their calls in flight complete first
     hipSetDevice(c->device);
     hipDeviceSynchronize();  // every stream of the context, and the callers' streams that ran its work
     if (Ctx *t = c->twin.load(std::memory_order_acquire)) {

@@ -138,3 +138,19 @@ def test_new_symbols_are_declared_exported_and_bound(K):
     assert (res.state, res.rc) == (1, K.C_KZG_BADARGS)
     assert l.lwkzg_verifier_pending(None) == -1 and l.lwkzg_verifier_wait(None) == K.C_KZG_BADARGS
     l.lwkzg_verifier_free(None)
+
+
+def test_a_null_handle_is_answered_alike_by_both_kinds(K):
+    """the entry points the two kinds share (csrc/async_verifier.h): pending -1, wait BADARGS, enqueue BADARGS with the result
+    complete -- zeroed but for state, rc and first_bad --, and BADARGS with nothing to complete when the result is NULL too"""
+    l = K.lib()
+    for prefix, result, pointers in (("lwkzg_verifier_", K.VerifyResult, 3), ("lwkzg_cell_verifier_", K.CellVerifyResult, 4)):
+        fn = lambda name: getattr(l, prefix + name)
+        assert fn("pending")(None) == -1 and fn("wait")(None) == K.C_KZG_BADARGS
+        res = result()
+        C.memset(C.byref(res), 0xa5, C.sizeof(res))
+        assert fn("enqueue")(None, C.byref(res), *([None] * pointers), 5, None) == K.C_KZG_BADARGS
+        assert (res.state, res.rc, res.ok, res.first_bad) == (1, K.C_KZG_BADARGS, 0, NONE_BAD)
+        assert bytes(res)[16:] == bytes(C.sizeof(res) - 16)
+        assert fn("enqueue")(None, None, *([None] * pointers), 5, None) == K.C_KZG_BADARGS
+        fn("free")(None)

@@ -144,7 +144,8 @@ for s in shapes:
         p = per[(s, k)]
         line = "  (%s) %-36s %8.3f [%8.3f .. %8.3f] ms" % (k, what, statistics.median(p), min(p), max(p))
         if k != "a":
-            line += "   inside enqueue: %.3f ms per call" % statistics.median(inside[(s, k)])
+            q = inside[(s, k)]
+            line += "   inside enqueue: %.3f [%.3f .. %.3f] ms per call" % (statistics.median(q), min(q), max(q))
         say(line)
     pa, pb = per[(s, "a")], per[(s, "b")]
     diff, rng = statistics.median(pb) - statistics.median(pa), max(pa) - min(pa)

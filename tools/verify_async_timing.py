@@ -99,7 +99,8 @@ def measure(ts, label):
         med = statistics.median(per[k])
         line = "  (%s) %-44s %7.3f [%7.3f .. %7.3f] ms   %9.0f blobs/s" % (k, what, med, min(per[k]), max(per[k]), n / med * 1e3)
         if k != "a":
-            line += "   inside enqueue: %.3f ms per call (%.1f %%)" % (statistics.median(inside[k]), 100 * statistics.median(inside[k]) / med)
+            line += "   inside enqueue: %.3f [%.3f .. %.3f] ms per call (%.1f %%)" % (
+                statistics.median(inside[k]), min(inside[k]), max(inside[k]), 100 * statistics.median(inside[k]) / med)
         say(line)
     rate = {k: n / statistics.median(per[k]) * 1e3 for k in per}
     spread = {k: n / min(per[k]) * 1e3 - n / max(per[k]) * 1e3 for k in per}
