@@ -123,7 +123,7 @@ C_KZG_RET verify_blob_kzg_proof(bool *ok, const Blob *blob, const Bytes48 *commi
                                 const Bytes48 *proof_bytes, const KZGSettings *s);
 
 /* src/lib.rs:525-614. n == 0 -> C_KZG_OK with *ok = false in reference mode (src/lib.rs:538-543) and *ok = true in
- * c-kzg mode (the reference's own vector verify_blob_kzg_proof_batch_case_a271b78b8e869d69).
+ * c-kzg mode (the reference's own vector verify_blob_kzg_proof_batch_case_a271b78b8e869d69) and in eth mode (the consensus specs).
  * Batches of more than 1024 blobs are uploaded into a device buffer of n * 131072 bytes that the settings object keeps (grow-only, freed by
  * free_trusted_setup): 4096 blobs 12.1 ms, of which 9.6 are the upload; lwkzg_verify_blob_kzg_proof_batch_device takes blobs that are
  * already in HBM (5.3 ms). */
@@ -139,8 +139,23 @@ C_KZG_RET verify_blob_kzg_proof_batch(bool *ok, const Blob *blobs, const Bytes48
  *   LWKZG_MODE_CKZG: what the c-kzg-4844 vectors under the reference's tests/ encode -- canonical
  *       little-endian scalars are evaluations on the bit-reversed 4096th roots of unity (inverse NTT
  *       in front of the same MSM), little-endian z/y/digest, invalid input is C_KZG_BADARGS.
+ *   LWKZG_MODE_ETH ("consensus-specs mode"): the encoding of the consensus specs since Deneb, of c-kzg-4844 from 1.0 on and of every
+ *       mainnet client -- c-kzg mode with BIG-endian canonical field elements (blob elements, z, y, cells, challenge outputs; an
+ *       element, z or y not below r is C_KZG_BADARGS), the blobs evaluations on the bit-reversed domain, and the specs' transcripts:
+ *       compute_challenge hashes "FSBLOBVERIFY_V1_" | be128(4096) | blob | commitment (8 zero bytes, then be64(4096)) and the batch
+ *       challenge "RCKZGBATCH___V1_" | be64(4096) | be64(n) | n x (C | z | y | proof) with z and y big-endian; both digests are read
+ *       big-endian and reduced. Every other rule is c-kzg mode's (infinity allowed as a commitment or proof, its non-canonical
+ *       encodings re-hashed over the canonical bytes, C_KZG_BADARGS, an empty blob batch verifies, the z-on-the-domain branch). In
+ *       this mode the bytes of commitments, proofs, y, cells, cell proofs and recovered cells, and the verdicts, are c-kzg-4844 2.x's.
+ *       The mode runs on the Lagrange form of the setup exactly as c-kzg mode does: moving a settings object between the two moves
+ *       or derives no table. (The cell batch's transcript stays the library's own in every mode -- see
+ *       lwkzg_verify_cell_kzg_proof_batch: the per-cell digests use le64(row) | le64(k) and the header le64 fields; in eth mode only
+ *       the reading of that digest into r, and the r bytes of the partials, follow the mode: big-endian. The spec's single
+ *       sequential hash over n x 2112 bytes would put milliseconds of serial SHA-256 in front of the sums, and the verdict does not
+ *       depend on it.)
+ *   "The mode's byte order" in the notes below: big-endian in reference and eth mode, little-endian in c-kzg mode.
  * lwkzg_set_mode sets the process-wide DEFAULT (initial value from the environment variable LWKZG_MODE,
- * "reference"|"ckzg"); lwkzg_settings_set_mode gives ONE settings object a mode of its own, which wins over the default
+ * "reference"|"ckzg"|"eth"); lwkzg_settings_set_mode gives ONE settings object a mode of its own, which wins over the default
  * (mode -1 hands it back to the default), so two consumers in one process can use different semantics. Every entry
  * point resolves its mode once, when it is entered: a change does not affect calls already in flight.
  * Cost of lwkzg_settings_set_mode: it brings the settings' MSM tables to the new mode's form (lwkzg_direct_table_forms below). The
@@ -151,6 +166,7 @@ C_KZG_RET verify_blob_kzg_proof_batch(bool *ok, const Blob *blobs, const Bytes48
  * settings object that merely follows the default gets the Lagrange form on its first c-kzg call, and only if it fits beside. */
 #define LWKZG_MODE_REFERENCE 0
 #define LWKZG_MODE_CKZG 1
+#define LWKZG_MODE_ETH 2
 int lwkzg_set_mode(int mode); /* returns the previous default, or -1 if `mode` is invalid */
 int lwkzg_get_mode(void);
 int lwkzg_settings_set_mode(const KZGSettings *s, int mode); /* returns the mode calls on `s` answered in before, -1 on error */
@@ -281,6 +297,7 @@ C_KZG_RET lwkzg_setup_import_device(KZGSettings *out, const void *image_dev);
  * reference blst_fp convention; every call, free_trusted_setup and the setup image work on it), with two differences: it answers in
  * c-kzg mode from the start, as after lwkzg_settings_set_mode(s, LWKZG_MODE_CKZG) -- the table the load picks is built in the
  * Lagrange form first; another mode may be set afterwards --, and its Lagrange form is live at once, taken from the input.
+ * A mainnet consumer calls lwkzg_settings_set_mode(&s, LWKZG_MODE_ETH) after the load; it is free (both modes run on the Lagrange form).
  * One-section form: the monomial points are derived on the device (4096 MSMs over the Lagrange points). Three-section form: nothing is
  * derived; both sections are validated and held against each other (a random polynomial committed over each: two MSMs), and the load
  * fails closed on a mismatch, which c-kzg itself does not check.
@@ -549,7 +566,10 @@ C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_mixed_device(void *recovered_cells_
  * byte equality in order of first occurrence (m rows), a two-level transcript
  *     d_i = SHA-256(le64(row_i) | le64(k_i) | cell_i | proof_i)                                    (on the GPU, one hash per cell)
  *     r   = SHA-256("RCKZGCBATCH__V1_" | le64(4096) | le64(64) | le64(m) | le64(n) | the m distinct commitments | d_0 .. d_(n-1))
- * read in the mode's byte order and reduced, and one pairing check e(RLC - RLI + RLP, G2) e(-P, g2_values[64]) == 1 over
+ * read in the mode's byte order and reduced (this transcript is the library's own in EVERY mode, LWKZG_MODE_ETH included: there only
+ * the reading of the digest into r, and the r bytes of lwkzg_cell_verify_partials, are the mode's -- big-endian; the consensus specs'
+ * single sequential hash over n x 2112 bytes would put milliseconds of serial SHA-256 in front of the sums, and the verdict does not
+ * depend on the transcript), and one pairing check e(RLC - RLI + RLP, G2) e(-P, g2_values[64]) == 1 over
  * P = sum r^i pi_i, RLP = sum r^i c_(k_i) pi_i, RLC = sum_j (sum_(row_i = j) r^i) C_j and RLI = [sum r^i I_i(tau)]G1 (I_i: the
  * interpolant of cell i on its coset). The settings must carry all 65 G2 points.
  * Returns: C_KZG_BADARGS for ok == NULL, NULL pointers with n > 0 or an index >= 128 (decided on the host before any device work); the
@@ -713,10 +733,13 @@ C_KZG_RET lwkzg_pairing_product_is_one(bool *ok, const uint8_t *g1_compressed, c
 /* Host-only test hook: digests[i] = SHA-256("FSBLOBVERIFY_V1_" | le64(4096) | le64(0) | blobs[i] | commitments[i]),
  * the compute_challenge message (src/utils.rs:120-144), as the host-pointer proof entry points compute it. */
 C_KZG_RET lwkzg_challenge_digests_host(uint8_t *digests32, const uint8_t *blobs, const uint8_t *commitments48, size_t n);
+/* the same for `mode`'s message: modes 0 and 1 hash what the hook above hashes, LWKZG_MODE_ETH hashes
+ * "FSBLOBVERIFY_V1_" | be128(4096) | blobs[i] | commitments[i]. C_KZG_BADARGS for an unknown mode. */
+C_KZG_RET lwkzg_challenge_digests_host_mode(uint8_t *digests32, const uint8_t *blobs, const uint8_t *commitments48, size_t n, int mode);
 
 /* Host-only: the batch challenge of verify_blob_kzg_proof_batch (src/utils.rs:166-206) over a transcript of n_total 160-byte records
  * (lwkzg_verify_shard_begin*'s output, all shards in order): r = SHA-256("RCKZGBATCH___V1_" | le64(4096) | le64(n_total) | records) read as a
- * field element in `mode`'s byte order and reduced; r_out = its canonical value, 32 bytes big-endian. What every shard derives inside
+ * field element in `mode`'s byte order and reduced (LWKZG_MODE_ETH: the header's two fields are be64); r_out = its canonical value, 32 bytes big-endian. What every shard derives inside
  * lwkzg_verify_shard_partial; exposed so that a sharded verifier can log / cross-check it (tests hold it against hashlib). */
 C_KZG_RET lwkzg_batch_challenge_host(uint8_t r_out[32], const uint8_t *records_all, size_t n_total, int mode);
 

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LWKZG_LIBRARY") or os.path.join(_HERE, "lib", "liblambdaworks_kzg.so")  # override: A/B builds
 
 C_KZG_OK, C_KZG_BADARGS, C_KZG_ERROR, C_KZG_MALLOC = 0, 1, 2, 3
-MODE_REFERENCE, MODE_CKZG = 0, 1
+MODE_REFERENCE, MODE_CKZG, MODE_ETH = 0, 1, 2   # MODE_ETH: the consensus specs' encoding (big-endian evaluation form, c-kzg-4844 2.x)
 FIELD_ELEMENTS_PER_BLOB = 4096
 BYTES_PER_BLOB = 4096 * 32
 BYTES_PER_COMMITMENT = 48
@@ -67,7 +67,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_device_count", "lwkzg_set_device", "lwkzg_version", "lwkzg_last_error",
     "lwkzg_profile_enable", "lwkzg_profile_reset", "lwkzg_profile_report",
     "lwkzg_msm_window_bits", "lwkzg_msm_num_windows", "lwkzg_pairing_product_is_one",
-    "lwkzg_challenge_digests_host", "lwkzg_batch_challenge_host", "lwkzg_g1_msm_tiled_device", "lwkzg_g1_sum_compressed",
+    "lwkzg_challenge_digests_host", "lwkzg_challenge_digests_host_mode", "lwkzg_batch_challenge_host", "lwkzg_g1_msm_tiled_device", "lwkzg_g1_sum_compressed",
     "lwkzg_commit_and_prove_batch_device", "lwkzg_enable_direct_table", "lwkzg_direct_table_bits", "lwkzg_direct_table_forms", "lwkzg_enable_direct_table_forms", "lwkzg_direct_num_windows", "lwkzg_direct_row_bytes",
     "lwkzg_compute_challenges_device",
     "lwkzg_timing_report", "lwkzg_runtime_init", "lwkzg_knob_report", "lwkzg_last_proof_schedule",
@@ -220,6 +220,7 @@ def lib():
     l.lwkzg_profile_report.restype = sz
     l.lwkzg_pairing_product_is_one.argtypes = [C.POINTER(C.c_bool), C.c_char_p, C.c_char_p, sz]
     l.lwkzg_challenge_digests_host.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, sz]
+    l.lwkzg_challenge_digests_host_mode.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, sz, ci]
     l.lwkzg_batch_challenge_host.argtypes = [C.c_char_p, C.c_char_p, sz, ci]
     l.lwkzg_g1_msm_tiled_device.argtypes = [vp, vp, sz, ps, vp]
     l.lwkzg_g1_sum_compressed.argtypes = [C.c_char_p, C.c_char_p, sz]
@@ -423,7 +424,7 @@ class TrustedSetup:
         _check("lwkzg_reserve_streams", lib().lwkzg_reserve_streams(self.ref(), n, caller_streams))
 
     def set_mode(self, mode):
-        """This settings object's own semantics (MODE_REFERENCE / MODE_CKZG; -1 = follow the process-wide default)."""
+        """This settings object's own semantics (MODE_REFERENCE / MODE_CKZG / MODE_ETH; -1 = follow the process-wide default)."""
         prev = lib().lwkzg_settings_set_mode(self.ref(), mode)
         if prev < 0:
             raise KzgError("lwkzg_settings_set_mode", C_KZG_BADARGS)
@@ -1169,6 +1170,16 @@ def challenge_digests_host(blobs, commitments):
     assert len(blobs) == n * BYTES_PER_BLOB
     out = C.create_string_buffer(32 * max(n, 1))
     _check("lwkzg_challenge_digests_host", lib().lwkzg_challenge_digests_host(out, blobs, commitments, n))
+    raw = out.raw
+    return [raw[32 * i:32 * i + 32] for i in range(n)]
+
+
+def challenge_digests_host_mode(blobs, commitments, mode):
+    """the compute_challenge digests of `mode`'s message (host only); MODE_ETH: the consensus specs' be128(4096) degree field"""
+    n = len(commitments) // 48
+    assert len(blobs) == n * BYTES_PER_BLOB
+    out = C.create_string_buffer(32 * max(n, 1))
+    _check("lwkzg_challenge_digests_host_mode", lib().lwkzg_challenge_digests_host_mode(out, blobs, commitments, n, mode))
     raw = out.raw
     return [raw[32 * i:32 * i + 32] for i in range(n)]
 

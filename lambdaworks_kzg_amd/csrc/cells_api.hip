@@ -21,7 +21,7 @@ namespace lwk {
 
 void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st, bool fk20) {
     Workspace &w = c->ws;
-    const int le = mode == LWKZG_MODE_CKZG;
+    const int le = mode_rules(mode).le();
     if (cells) launch_cells_extend(w.scalars, c->tw_fwd, c->tw28_fwd, w.fr, (Fr *)w.scalars2, cells, le, m, st);
     if (proofs48 && fk20) {
         (void)fk20_proofs(c, proofs48, m, st);   // (launches only without the hook's copy; behind the extension: both write ws.scalars2)
@@ -119,8 +119,8 @@ C_KZG_RET cells_device(Ctx *c, uint8_t *cells, uint8_t *proofs48, const uint8_t 
                        size_t n_call) {
     return cells_chunks(c, cells, proofs48, n, mode, st, status, [&](size_t off, size_t m, int32_t *stt) {
         const uint8_t *b = blobs + off * (size_t)kBlobBytes;
-        if (mode == LWKZG_MODE_REFERENCE) launch_parse_be_reduce(b, c->ws.scalars, m * kBlobElems, st);
-        else launch_blob_evaluations_to_coefficients(b, c->ws.scalars, c->tw28_inv, stt, m, st);
+        if (!mode_rules(mode).evaluation_form) launch_parse_be_reduce(b, c->ws.scalars, m * kBlobElems, st);
+        else launch_blob_evaluations_to_coefficients(b, c->ws.scalars, c->tw28_inv, stt, m, st, mode_rules(mode).le());
     }, n_call);
 }
 

@@ -15,7 +15,7 @@ static_assert(kProofChunk * kProofsPerBlob == kMaxChunk, "a chunk of blobs fills
 
 inline size_t min_sz(size_t a, size_t b) { return a < b ? a : b; }
 
-inline C_KZG_RET bad_input(int mode) { return mode == LWKZG_MODE_CKZG ? C_KZG_BADARGS : C_KZG_ERROR; }
+inline C_KZG_RET bad_input(int mode) { return mode_rules(mode).bad; }
 
 // The device pipeline of n blobs on st, a chunk at a time (8 blobs with proofs, 512 without); the caller holds the context's lock and the
 // workspace. coefficients(off, m, stt) enqueues the step that leaves the coefficients of blobs off .. off + m in ws.scalars and a

@@ -123,7 +123,7 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
                           const uint8_t *cells, const uint8_t *proofs, size_t n, const KZGSettings *s, int mode, bool device_inputs,
                           hipStream_t caller) {
     const auto t0 = std::chrono::steady_clock::now();
-    const int le = mode == LWKZG_MODE_CKZG;
+    const int le = mode_rules(mode).le();
     Grouping g;
     if (!device_inputs && !group_items(g, comms, idx, n)) {   // before any device work: decidable without a GPU
         set_error("verify_cell_kzg_proof_batch: a cell index is not below %d", kCellsPerBlob);
@@ -260,7 +260,7 @@ C_KZG_RET cell_batch_impl(bool *ok, uint8_t *partials, const void *comms, const 
                                    (const uint8_t *)proofs, n, s, mode, device_inputs, caller);
     if (rc != C_KZG_OK) return rc;
     if (partials) {
-        if (mode == LWKZG_MODE_CKZG) raw_to_le<8>(partials, r_raw);
+        if (mode_rules(mode).little_endian) raw_to_le<8>(partials, r_raw);
         else raw_to_be<8>(partials, r_raw);
     }
     const auto t0 = std::chrono::steady_clock::now();
@@ -304,7 +304,7 @@ C_KZG_RET lwkzg_cell_verify_partials(uint8_t *out, const Bytes48 *commitments, c
 
 C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *commitments, const uint64_t *cell_indices, const Cell *cells,
                                           const Bytes48 *proofs, size_t n, int mode) {
-    if (!r_out || (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG)) return C_KZG_BADARGS;
+    if (!r_out || !mode_known(mode)) return C_KZG_BADARGS;
     if (n && (!commitments || !cell_indices || !cells || !proofs)) return C_KZG_BADARGS;
     return guarded("lwkzg_cell_batch_challenge_host", [&]() -> C_KZG_RET {
         Grouping g;
@@ -320,8 +320,8 @@ C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *comm
             sha256_fast(&digests[32 * i], msg.data(), msg.size());
         }
         uint32_t r_raw[8];
-        cell_batch_challenge(r_raw, g.distinct.data(), g.m, digests.data(), n, mode == LWKZG_MODE_CKZG);
-        if (mode == LWKZG_MODE_CKZG) raw_to_le<8>(r_out, r_raw);
+        cell_batch_challenge(r_raw, g.distinct.data(), g.m, digests.data(), n, mode_rules(mode).little_endian);
+        if (mode_rules(mode).little_endian) raw_to_le<8>(r_out, r_raw);
         else raw_to_be<8>(r_out, r_raw);
         return C_KZG_OK;
     });

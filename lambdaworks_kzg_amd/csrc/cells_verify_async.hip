@@ -114,12 +114,12 @@ bool decide_or_challenge(uint32_t r_raw[8], uint32_t *first_bad, int32_t *rc, co
         *rc = bad_input(mode);
         return false;
     }
-    cell_batch_challenge(r_raw, distinct48, m, digests32, n, mode == LWKZG_MODE_CKZG);
+    cell_batch_challenge(r_raw, distinct48, m, digests32, n, mode_rules(mode).little_endian);
     return true;
 }
 
 void r_bytes(uint8_t out32[32], const uint32_t r_raw[8], int mode) {
-    if (mode == LWKZG_MODE_CKZG) raw_to_le<8>(out32, r_raw);
+    if (mode_rules(mode).little_endian) raw_to_le<8>(out32, r_raw);
     else raw_to_be<8>(out32, r_raw);
 }
 
@@ -256,7 +256,7 @@ C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t *comms,
     if (rc != C_KZG_OK) return rc;
     CellvBufs &b = v->b;
     const size_t n = j->n;
-    const int le = j->mode == LWKZG_MODE_CKZG, bad = (int)bad_input(j->mode);
+    const int le = mode_rules(j->mode).le(), bad = (int)bad_input(j->mode);
     hipStream_t st = c->stream, side = c->aux[1];
     const uint32_t *d_m = v->g.head + kGroupHeadM;
     uint32_t *d_skip = (uint32_t *)(b.pw + 33);
@@ -353,7 +353,7 @@ C_KZG_RET lwkzg_cell_verifier_host_steps(LwkzgCellVerifyResult *out, const uint8
     out->first_bad = kNoneBad;
     out->m = (uint32_t)m;
     auto refuse = [&] { return async_refuse(out, C_KZG_BADARGS); };
-    if (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG) return refuse();
+    if (!mode_known(mode)) return refuse();
     if (n == 0 || m == 0 || m > n) return refuse();
     // what each outcome reads: a bad index nothing; a fault word the words and first_item; an honest batch everything
     if (bad_index == kNoneBad && (!status || !first_item)) return refuse();

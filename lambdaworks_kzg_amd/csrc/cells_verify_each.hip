@@ -201,7 +201,7 @@ C_KZG_RET cell_each_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *points_out, 
         return C_KZG_BADARGS;
     }
     const int mode = mode_of(s);
-    const int le = mode == LWKZG_MODE_CKZG;
+    const int le = mode_rules(mode).le();
     Ctx *c = ctx_of(s);
     if (!c) return C_KZG_ERROR;
     if (!s->g2_values) {

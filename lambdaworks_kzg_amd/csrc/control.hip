@@ -18,7 +18,7 @@ static std::atomic<int> g_mode{-1};
 static int mode_now() {
     int m = g_mode.load(std::memory_order_relaxed);
     if (m < 0) {
-        m = knobs().mode ? LWKZG_MODE_CKZG : LWKZG_MODE_REFERENCE;   // LWKZG_MODE
+        m = mode_known(knobs().mode) ? knobs().mode : LWKZG_MODE_REFERENCE;   // LWKZG_MODE
         int expect = -1;
         if (!g_mode.compare_exchange_strong(expect, m)) m = expect;
     }
@@ -40,7 +40,7 @@ extern "C" {
 
 int lwkzg_set_mode(int mode) {
     int prev = mode_now();
-    if (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG) return -1;
+    if (!mode_known(mode)) return -1;
     g_mode.store(mode);
     return prev;
 }
@@ -54,7 +54,7 @@ int lwkzg_get_mode(void) { return mode_now(); }
 // mode's form -- the cost of a lwkzg_enable_direct_table call of that width (0.9 s of kernels at 16 bits plus whatever hipMalloc
 // waits for). Nothing happens when the tables already suit the mode. The process-wide default (lwkzg_set_mode) never moves a table.
 int lwkzg_settings_set_mode(const KZGSettings *s, int mode) {
-    if (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG && mode != -1) return -1;
+    if (!mode_known(mode) && mode != -1) return -1;
     Ctx *c = ctx_of(s);  // hand-built settings get their context here
     if (!c) return -1;
     const int prev = lwk::mode_of(s);

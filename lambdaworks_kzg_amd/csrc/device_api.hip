@@ -132,9 +132,10 @@ C_KZG_RET lwkzg_compute_challenges_device(void *z32_dev, const void *blobs_dev, 
     C_KZG_RET rc = ctx_reserve(c, n);
     if (rc != C_KZG_OK) return rc;
     if (n > kMaxChunk && (rc = ws_long_reserve(c, n)) != C_KZG_OK) return rc;
-    const int le = mode_of(s) == LWKZG_MODE_CKZG;
+    const ModeRules mr = mode_rules(mode_of(s));
+    const int le = mr.le();
     Fr *z = n > kMaxChunk ? c->ws.z_long : c->ws.z;
-    launch_challenge((const uint8_t *)blobs_dev, (const uint8_t *)commitments48_dev, z, le, n, st);
+    launch_challenge((const uint8_t *)blobs_dev, (const uint8_t *)commitments48_dev, z, mr.hash_rule(), n, st);
     launch_fr_mont_to_bytes(z, (uint8_t *)z32_dev, le, n, st);
     return C_KZG_OK;
 }

@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/lambdaworks_kzg_amd.h"
 #include "kernels.h"
+#include "mode_rules.h"
 #include "front.h"
 
 namespace lwk {
@@ -467,7 +468,7 @@ C_KZG_RET cell_batch_finish(bool *ok, uint8_t *out4x97, const uint8_t sums[3][96
 
 // the host's end of an asynchronous verification (verify.hip): the challenge and its power table from the transcript,
 // the partial and the verdict from what the device sent down, and the synchronous call with the same outputs (the fallback)
-void verify_async_challenge(uint8_t r_be[32], Fr pw33[33], const uint8_t *records, size_t n, bool le);
+void verify_async_challenge(uint8_t r_be[32], Fr pw33[33], const uint8_t *records, size_t n, int mode);
 C_KZG_RET verify_async_verdict(bool *ok, uint8_t *partial, const uint8_t sums96[3][96], const int infs[3], const uint8_t ysum_be[32],
                                const KZGSettings *own);
 C_KZG_RET verify_batch_device_full(bool *ok, uint8_t r_be[32], uint8_t *partial, const uint8_t *d_blobs, const uint8_t *d_comm,

@@ -348,12 +348,13 @@ static void launch_host_wake(Ctx *c) {
 struct ChunkHashArgs {
     SmallProofHost *h;
     size_t first, count;
+    bool be_fields;   // the mode's transcript (mode_rules.h)
 };
 static void chunk_midstate_host_fn(void *p) {   // the one-pass commit-and-prove: the commitment-free 2048 blocks of a chunk's hashes
     ChunkHashArgs *a = (ChunkHashArgs *)p;
     SmallProofHost &h = *a->h;
     try {
-        challenge_midstates_host((uint32_t *)(h.dig + 32 * a->first), h.blobs + a->first * (size_t)kBlobBytes, a->count);
+        challenge_midstates_host((uint32_t *)(h.dig + 32 * a->first), h.blobs + a->first * (size_t)kBlobBytes, a->count, a->be_fields);
     } catch (...) {
         memset(h.dig + 32 * a->first, 0, 32 * a->count);
     }
@@ -363,7 +364,7 @@ static void chunk_hash_host_fn(void *p) {
     ChunkHashArgs *a = (ChunkHashArgs *)p;
     SmallProofHost &h = *a->h;
     try {
-        challenge_digests_host(h.dig + 32 * a->first, h.blobs + a->first * (size_t)kBlobBytes, h.comm + 48 * a->first, a->count);
+        challenge_digests_host(h.dig + 32 * a->first, h.blobs + a->first * (size_t)kBlobBytes, h.comm + 48 * a->first, a->count, a->be_fields);
     } catch (...) {
         memset(h.dig + 32 * a->first, 0, 32 * a->count);   // (host_parallel_for does not throw; a wrong digest would show as a wrong proof, never silently)
     }
@@ -376,12 +377,12 @@ static void chunk_hash_host_fn(void *p) {
 // the host functions already queued -- so that the caller can return the error without leaving work running against its buffers and
 // the context's staging.
 static C_KZG_RET chunk_host_functions(Ctx *c, const uint8_t *blobs, size_t n, hipStream_t sc, hipStream_t sf, hipStream_t join,
-                                      void (*fn)(void *), const char *prof_name, bool record_hashed = false) {
+                                      void (*fn)(void *), const char *prof_name, bool be_fields, bool record_hashed = false) {
     SmallProofHost &h = c->sph;
     const size_t per = (n + mid_proof_chunks() - 1) / mid_proof_chunks();
     std::vector<ChunkHashArgs *> args;
     for (size_t first = 0; first < n; first += per) {
-        ChunkHashArgs *a = new (std::nothrow) ChunkHashArgs{&h, first, n - first < per ? n - first : per};
+        ChunkHashArgs *a = new (std::nothrow) ChunkHashArgs{&h, first, n - first < per ? n - first : per, be_fields};
         if (!a) {
             for (ChunkHashArgs *b : args) delete b;
             return C_KZG_MALLOC;
@@ -418,6 +419,7 @@ struct SmallProofArgs {
     SmallProofHost *h;
     size_t n;
     int32_t bad;
+    bool be_fields;
 };
 
 // runs on the runtime's callback thread, in stream order, between the copies out and the copies back: no HIP calls in here
@@ -425,7 +427,7 @@ static void small_proof_host_fn(void *p) {
     SmallProofArgs *a = (SmallProofArgs *)p;
     SmallProofHost &h = *a->h;
     try {
-        challenge_digests_host(h.dig, h.blobs, h.comm, a->n);     // compute_challenge, src/utils.rs:120-154, over the caller's commitment bytes
+        challenge_digests_host(h.dig, h.blobs, h.comm, a->n, a->be_fields);     // compute_challenge, src/utils.rs:120-154, over the caller's commitment bytes
         std::vector<int> vrc(a->n);
         host_validate_commitments(h.comm, h.canon, vrc.data(), a->n);  // src/lib.rs:372-375: decompress + subgroup check; canonical re-compression
         for (size_t i = 0; i < a->n; i++) h.code[i] = vrc[i] == 2 ? a->bad : 0;
@@ -899,17 +901,17 @@ void host_finish_compress(uint8_t out[48], const G1Xyzz29 &sum) {
 // one has none. A PROOF's quotient is computed in coefficient form (Horner / Ruffini); it moves to the Lagrange form, by one forward
 // transform, only when that is where the settings' one direct table is.
 static bool commit_on_lagrange(const Ctx *c, int mode) {
-    return mode == LWKZG_MODE_CKZG && c->lag.ready && (c->lag.direct_table || !c->direct_table);
+    return mode_rules(mode).evaluation_form && c->lag.ready && (c->lag.direct_table || !c->direct_table);
 }
 static bool proof_on_lagrange(const Ctx *c, int mode) {
-    return mode == LWKZG_MODE_CKZG && c->lag.ready && c->lag.direct_table && !c->direct_table;
+    return mode_rules(mode).evaluation_form && c->lag.ready && c->lag.direct_table && !c->direct_table;
 }
 // r05: a c-kzg-mode proof whose MSM can run on the Lagrange form at full speed (that form has a direct table, or no form has one)
 // computes its quotient in EVALUATION form (fr_ops.hip: k_eval_quotient_evalform): the blob's evaluations as they stand, one batch
 // inversion per blob, no transform in front of the quotient and none behind it. LWKZG_CKZG_EVAL_PROOFS=0 is the A/B arm (the inverse
 // transform, Horner / Ruffini, and a forward transform where the Lagrange table is the only one).
 bool proof_in_evaluation_form(const Ctx *c, int mode) {
-    return knobs().ckzg_eval_proofs && mode == LWKZG_MODE_CKZG && c->lag.ready && (c->lag.direct_table || !c->direct_table);
+    return knobs().ckzg_eval_proofs && mode_rules(mode).evaluation_form && c->lag.ready && (c->lag.direct_table || !c->direct_table);
 }
 // quotient (and y = p(z)) of n blobs whose scalars coefficients_stage left at `in`, in the form that function chose; quot = nullptr: y only
 void quotient_stage(Ctx *c, int mode, const uint32_t *in, const Fr *z, uint32_t *quot, uint8_t *y_out, int le, size_t n, hipStream_t st,
@@ -940,13 +942,15 @@ bool coefficients_stage(Ctx *c, const uint8_t *blobs, size_t n, int mode, int32_
                         uint32_t *zero, uint32_t zero_words, uint32_t *zero2, uint32_t zero2_words) {
     Workspace &w = c->ws;
     uint32_t *scalars = w.scalars + base * (size_t)kBlobElems * 8;
-    if (mode == LWKZG_MODE_REFERENCE) {
+    const ModeRules mr = mode_rules(mode);
+    if (!mr.evaluation_form) {
         launch_parse_be_reduce(blobs, scalars, n * kBlobElems, st, zero, zero_words, zero2, zero2_words);   // (zero, zero2: reference mode only -- the caller checks)
     } else if (evaluations_ok ? commit_on_lagrange(c, mode) : proof_in_evaluation_form(c, mode)) {
-        launch_copy_le_check(blobs, scalars, status, n, st);
+        if (mr.little_endian) launch_copy_le_check(blobs, scalars, status, n, st);
+        else launch_copy_be_check(blobs, scalars, status, n, st);   // (eth mode: the same limbs behind a byte swap)
         return true;
     } else {
-        launch_blob_evaluations_to_coefficients(blobs, scalars, c->tw28_inv, status, n, st);
+        launch_blob_evaluations_to_coefficients(blobs, scalars, c->tw28_inv, status, n, st, mr.le());
     }
     return false;
 }
@@ -981,7 +985,7 @@ C_KZG_RET commit_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, size
         // reference mode on one stream: the parse kernel is the first launch of the chunk, and it clears the chunk's status words and the redo
         // flags of its MSM on its way -- no fill launch in front of the parse and none in front of the accumulation (LWKZG_COMMIT_TAIL=0: both).
         // (The c-kzg front kernels write status words themselves and keep the fill in front of them.)
-        const bool parse_clears = ways == 1 && mode == LWKZG_MODE_REFERENCE && knobs().commit_tail;
+        const bool parse_clears = ways == 1 && !mode_rules(mode).evaluation_form && knobs().commit_tail;
         if (!parse_clears) LWK_HIP(hipMemsetAsync(stt, 0, m * 4, st));
         if (ways == 1) {
             const bool redo_cleared = parse_clears && direct;
@@ -1034,7 +1038,8 @@ C_KZG_RET blob_proof_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, 
         if (rc != C_KZG_OK) return rc;
     }
     Workspace &w = c->ws;
-    const int le = mode == LWKZG_MODE_CKZG;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le(), fs = mr.hash_rule();   // the byte order of digests and outputs; what the hash kernels are told
     int32_t *stt = status ? status : longcall ? w.status_long : w.status;
     Fr *z = longcall ? w.z_long : w.z;
     uint8_t *canon = longcall ? w.canon_long : w.canon48;
@@ -1068,7 +1073,7 @@ C_KZG_RET blob_proof_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, 
     if (plan.needs_staging()) {
         bool ok = sph_reserve(c, n);
         if (ok && plan.schedule == kProofSmallHost) {
-            host_args = new (std::nothrow) SmallProofArgs{&c->sph, n, le ? kStatusBadArgs : kStatusError};
+            host_args = new (std::nothrow) SmallProofArgs{&c->sph, n, mr.bad_status(), mr.be_transcript};
             ok = host_args != nullptr;
         }
         if (!ok) plan = plan_proof_call(n, warm, busy, msm_direct, false, pk);
@@ -1098,22 +1103,22 @@ C_KZG_RET blob_proof_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, 
         LWK_HIP(hipMemcpyAsync(w.zbytes, h.dig, n * 32, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemcpyAsync(canon, h.canon, n * 48, hipMemcpyHostToDevice, st));
         launch_z_from_bytes(w.zbytes, z, nullptr, le, n, st);  // digest -> Fr, reduced (utils.rs:148-154)
-        launch_challenge(blobs, canon, z, le, n, st, comm48);
+        launch_challenge(blobs, canon, z, fs, n, st, comm48);
         break;
     }
     case kProofMidCold: {
         // mid-size call, host threads cold: the GPU's hash kernel this once, and a nudge for the threads on the side stream
         LWK_HIP(hipEventRecord(c->ev_fork, st));
         LWK_HIP(hipStreamWaitEvent(c->vstream, c->ev_fork, 0));
-        launch_validate_commitments(comm48, canon, stt, le ? kStatusBadArgs : kStatusError, n, c->vstream, longcall ? w.val_pts_long : w.val_pts,
+        launch_validate_commitments(comm48, canon, stt, mr.bad_status(), n, c->vstream, longcall ? w.val_pts_long : w.val_pts,
                                     longcall ? w.val_kind_long : w.val_kind, longcall ? w.val_verdict_long : w.val_verdict);
         LWK_HIP(hipEventRecord(c->ev_join[0], c->vstream));
         // (the wake-up on a stream this call does not wait for: on the validation's stream, in front of the join event, the first call of a
         // process paid for the creation of the thread pool)
         launch_host_wake(c);
-        launch_challenge(blobs, comm48, z, le, n, st);
+        launch_challenge(blobs, comm48, z, fs, n, st);
         LWK_HIP(hipStreamWaitEvent(st, c->ev_join[0], 0));
-        launch_challenge(blobs, canon, z, le, n, st, comm48);
+        launch_challenge(blobs, canon, z, fs, n, st, comm48);
         break;
     }
     case kProofMidHost:
@@ -1137,12 +1142,12 @@ C_KZG_RET blob_proof_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, 
         LWK_HIP(hipStreamWaitEvent(c->vstream, c->ev_fork, 0));
         LWK_HIP(hipStreamWaitEvent(sc, c->ev_fork, 0));
         if (piped) LWK_HIP(hipStreamWaitEvent(sh, c->ev_fork, 0));
-        launch_validate_commitments(comm48, canon, stt, le ? kStatusBadArgs : kStatusError, n, c->vstream, longcall ? w.val_pts_long : w.val_pts,
+        launch_validate_commitments(comm48, canon, stt, mr.bad_status(), n, c->vstream, longcall ? w.val_pts_long : w.val_pts,
                                     longcall ? w.val_kind_long : w.val_kind, longcall ? w.val_verdict_long : w.val_verdict);
         LWK_HIP(hipEventRecord(c->ev_join[0], c->vstream));
         LWK_HIP(hipMemcpyAsync(h.comm, comm48, n * 48, hipMemcpyDeviceToHost, sc));
         {
-            const C_KZG_RET rch = chunk_host_functions(c, blobs, n, sc, piped ? sh : st, st, chunk_hash_host_fn, "host_challenge_chunk", piped);
+            const C_KZG_RET rch = chunk_host_functions(c, blobs, n, sc, piped ? sh : st, st, chunk_hash_host_fn, "host_challenge_chunk", mr.be_transcript, piped);
             if (rch != C_KZG_OK) {
                 hipStreamWaitEvent(st, c->ev_join[0], 0);   // the validation on the side stream: nothing of this call outlives `st`
                 return rch;
@@ -1175,7 +1180,7 @@ C_KZG_RET blob_proof_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, 
             // the second pass: only the blobs whose commitment bytes were not the canonical encoding
             LWK_HIP(hipStreamWaitEvent(st, c->ev_join[0], 0));
             launch_flag_differs48(canon, comm48, differs, n, st);
-            launch_challenge(blobs, canon, z, le, n, st, comm48);
+            launch_challenge(blobs, canon, z, fs, n, st, comm48);
             quotient_stage(c, mode, w.scalars, z, w.scalars2, nullptr, le, n, st, differs);
             launch_direct_msm_only(evf ? c->lag.direct_bits : c->direct_bits, evf ? c->lag.direct_tab.win_dev : c->direct_tab.win_dev,
                                    evf ? c->lag.direct_row_bytes : c->direct_row_bytes, w.scalars2, w.sums, differs, n, st);
@@ -1185,18 +1190,18 @@ C_KZG_RET blob_proof_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, 
         LWK_HIP(hipMemcpyAsync(w.zbytes, h.dig, n * 32, hipMemcpyHostToDevice, st));
         launch_z_from_bytes(w.zbytes, z, nullptr, le, n, st);  // digest -> Fr, reduced (utils.rs:148-154)
         LWK_HIP(hipStreamWaitEvent(st, c->ev_join[0], 0));
-        launch_challenge(blobs, canon, z, le, n, st, comm48);   // only the lanes whose canonical commitment bytes differ from the caller's
+        launch_challenge(blobs, canon, z, fs, n, st, comm48);   // only the lanes whose canonical commitment bytes differ from the caller's
         break;
     }
     case kProofGpuChains: {
         LWK_HIP(hipEventRecord(c->ev_fork, st));
         LWK_HIP(hipStreamWaitEvent(c->vstream, c->ev_fork, 0));
-        launch_validate_commitments(comm48, canon, stt, le ? kStatusBadArgs : kStatusError, n, c->vstream, longcall ? w.val_pts_long : w.val_pts,
+        launch_validate_commitments(comm48, canon, stt, mr.bad_status(), n, c->vstream, longcall ? w.val_pts_long : w.val_pts,
                                     longcall ? w.val_kind_long : w.val_kind, longcall ? w.val_verdict_long : w.val_verdict);
         LWK_HIP(hipEventRecord(c->ev_join[0], c->vstream));
-        launch_challenge(blobs, comm48, z, le, n, st);
+        launch_challenge(blobs, comm48, z, fs, n, st);
         LWK_HIP(hipStreamWaitEvent(st, c->ev_join[0], 0));
-        launch_challenge(blobs, canon, z, le, n, st, comm48);
+        launch_challenge(blobs, canon, z, fs, n, st, comm48);
         break;
     }
     }
@@ -1240,7 +1245,8 @@ C_KZG_RET commit_and_prove_batch_device(Ctx *c, uint8_t *comm_out48, uint8_t *pr
         if (rc != C_KZG_OK) return rc;
     }
     Workspace &w = c->ws;
-    const int le = mode == LWKZG_MODE_CKZG;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le(), fs = mr.hash_rule();   // the byte order of digests and outputs; what the hash kernels are told
     int32_t *stt = status ? status : longcall ? w.status_long : w.status;
     Fr *z = longcall ? w.z_long : w.z;
     uint32_t *mid = (uint32_t *)(longcall ? w.canon_long : w.canon48);  // 32 of the 48 bytes per blob this call has no other use for
@@ -1257,12 +1263,12 @@ C_KZG_RET commit_and_prove_batch_device(Ctx *c, uint8_t *comm_out48, uint8_t *pr
         hipStream_t sc = c->aux[0];
         LWK_HIP(hipStreamWaitEvent(sc, c->ev_fork, 0));
         {
-            const C_KZG_RET rch = chunk_host_functions(c, blobs, n, sc, c->vstream, st, chunk_midstate_host_fn, "host_midstate_chunk");
+            const C_KZG_RET rch = chunk_host_functions(c, blobs, n, sc, c->vstream, st, chunk_midstate_host_fn, "host_midstate_chunk", mr.be_transcript);
             if (rch != C_KZG_OK) return rch;   // (st has been made to wait for both side streams)
         }
         LWK_HIP(hipMemcpyAsync(mid, h.dig, n * 32, hipMemcpyHostToDevice, c->vstream));
     } else {
-        launch_challenge_midstate(blobs, mid, n, c->vstream);  // ALL blobs of the call: a latency chain, as long for 64 blobs as for 16k
+        launch_challenge_midstate(blobs, mid, n, c->vstream, mr.be_transcript);  // ALL blobs of the call: a latency chain, as long for 64 blobs as for 16k
     }
     LWK_HIP(hipEventRecord(c->ev_join[0], c->vstream));
     for (size_t off = 0; off < n; off += kMaxChunk) {
@@ -1271,13 +1277,14 @@ C_KZG_RET commit_and_prove_batch_device(Ctx *c, uint8_t *comm_out48, uint8_t *pr
         if (coefficients_stage(c, b, m, mode, stt + off, st)) {  // evaluations: commitment and quotient both on the Lagrange form
             msm_stages(c, w.scalars, comm_out48 + 48 * off, m, st, 0, off == 0 && !host_mid, true);
         } else if (proof_on_lagrange(c, mode)) {  // coefficients for the quotient, but the only direct table is the Lagrange one: the commitment comes from the evaluations as they stand
-            launch_copy_le_check(b, (uint32_t *)w.fr, nullptr, m, st);
+            if (le) launch_copy_le_check(b, (uint32_t *)w.fr, nullptr, m, st);
+            else launch_copy_be_check(b, (uint32_t *)w.fr, nullptr, m, st);
             msm_stages(c, (const uint32_t *)w.fr, comm_out48 + 48 * off, m, st, 0, off == 0 && !host_mid, true);
         } else {
             msm_stages(c, w.scalars, comm_out48 + 48 * off, m, st, 0, off == 0 && !host_mid);  // the first one has the hash kernel beside it
         }
         if (off == 0) LWK_HIP(hipStreamWaitEvent(st, c->ev_join[0], 0));
-        launch_challenge_finish(b, comm_out48 + 48 * off, mid + 8 * off, z + off, le, m, st);
+        launch_challenge_finish(b, comm_out48 + 48 * off, mid + 8 * off, z + off, fs, m, st);
         quotient_stage(c, mode, w.scalars, z + off, w.scalars2, nullptr, le, m, st);
         msm_stages(c, w.scalars2, proof_out48 + 48 * off, m, st, 0, false, quotient_to_msm_form(c, mode, m, st));
     }
@@ -1289,13 +1296,14 @@ C_KZG_RET point_proof_batch_device(Ctx *c, uint8_t *proof48, uint8_t *y32, const
     C_KZG_RET rc = ctx_reserve(c, n);
     if (rc != C_KZG_OK) return rc;
     Workspace &w = c->ws;
-    const int le = mode == LWKZG_MODE_CKZG;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le();
     for (size_t off = 0; off < n; off += kMaxChunk) {
         size_t m = n - off < kMaxChunk ? n - off : kMaxChunk;
         int32_t *stt = status ? status + off : w.status;
         LWK_HIP(hipMemsetAsync(stt, 0, m * 4, st));
         coefficients_stage(c, blobs + off * (size_t)kBlobBytes, m, mode, stt, st);
-        launch_z_from_bytes(z32 + 32 * off, w.z, stt, le, m, st);
+        launch_z_from_bytes(z32 + 32 * off, w.z, stt, mr.scalar_rule(), m, st);
         quotient_stage(c, mode, w.scalars, w.z, w.scalars2, y32 + 32 * off, le, m, st);
         const bool lg = quotient_to_msm_form(c, mode, m, st);
         if (sums_out && n <= kMaxChunk) *sums_out = msm_sums_stage(c, w.scalars2, m, st, 0, false, lg);   // the caller finishes on the host

@@ -149,8 +149,8 @@ C_KZG_RET fk20_points_impl(uint8_t *out, int what, const Blob *blob, const KZGSe
         Workspace &w = c->ws;
         LWK_HIP(hipMemcpyAsync(w.blobs, blob, kBlobBytes, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemsetAsync(w.status, 0, 4, st));
-        if (mode == LWKZG_MODE_REFERENCE) launch_parse_be_reduce(w.blobs, w.scalars, kBlobElems, st);
-        else launch_blob_evaluations_to_coefficients(w.blobs, w.scalars, c->tw28_inv, w.status, 1, st);
+        if (!mode_rules(mode).evaluation_form) launch_parse_be_reduce(w.blobs, w.scalars, kBlobElems, st);
+        else launch_blob_evaluations_to_coefficients(w.blobs, w.scalars, c->tw28_inv, w.status, 1, st, mode_rules(mode).le());
         LWK_HIP(fk20_proofs(c, nullptr, 1, st, e_copy, h_out));
         launch_xyzz29_to_affine_be(what == 1 ? e_copy : h_out, d_xy, d_inf, n_pts, st);
         LWK_HIP(hipMemcpyAsync(xy.data(), d_xy, xy.size(), hipMemcpyDeviceToHost, st));

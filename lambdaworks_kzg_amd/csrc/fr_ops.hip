@@ -76,6 +76,12 @@ void launch_twiddles_to28(const Fr *tw, Fr28 *tw28, hipStream_t st) {
     hipLaunchKernelGGL(k_twiddles_to28, dim3(kBlobElems / 2 / 256), dim3(256), 0, st, tw, tw28, kBlobElems / 2);
 }
 
+// a 32-byte BIG-endian element as its two 16-byte loads (first = the most significant half) -> eight limbs, least significant first
+__device__ __forceinline__ void be_element_limbs(uint32_t w[8], const uint4 &first, const uint4 &second) {
+    w[0] = __builtin_bswap32(second.w); w[1] = __builtin_bswap32(second.z); w[2] = __builtin_bswap32(second.y); w[3] = __builtin_bswap32(second.x);
+    w[4] = __builtin_bswap32(first.w);  w[5] = __builtin_bswap32(first.z);  w[6] = __builtin_bswap32(first.y);  w[7] = __builtin_bswap32(first.x);
+}
+
 struct NttLds {
     uint32_t *lo;   // [9][4096]
     uint16_t *top;  // [4096]
@@ -96,7 +102,9 @@ struct NttLds {
 // FROM_BLOB = false: `in` holds Fr values in field.cuh's Montgomery form (the transform API); true: `in` is blob bytes,
 // canonical little-endian evaluations in the order a c-kzg-4844 blob stores them (mode C): the parse, the range check
 // (an element >= r marks its blob in `status`: c-kzg's C_KZG_BADARGS) and the entry into Montgomery form happen on load.
-template <bool FROM_BLOB>
+// BLOB_BE (with FROM_BLOB; eth mode): the same evaluations as canonical BIG-endian elements -- the two 16-byte loads are the same, the
+// eight words are byte-swapped and reversed into least-significant-first limbs in front of the same range check.
+template <bool FROM_BLOB, bool BLOB_BE = false>
 __global__ __launch_bounds__(kNttThreads) void k_ntt4096(const void *__restrict__ in, Fr *__restrict__ out,
                                                          const Fr28 *__restrict__ tw, int scale_to_raw,
                                                          int32_t *__restrict__ status) {
@@ -109,6 +117,7 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt4096(const void *__restrict_
             const uint4 *src = (const uint4 *)in + 2 * (base + i);
             uint4 lo = src[0], hi = src[1];
             uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            if constexpr (BLOB_BE) be_element_limbs(w, lo, hi);
             if (raw_geq<8>(w, FrParams::MOD)) status[blockIdx.x] = kStatusBadArgs;  // benign race: same value
             return LWK_FR28_MUL_CONST(fr28_pack(w), RR);
         } else {
@@ -143,13 +152,13 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt4096(const void *__restrict_
     for (int i = tid; i < kBlobElems; i += kNttThreads) store(i, a.get(i));
 }
 
-template <bool FROM_BLOB>
+template <bool FROM_BLOB, bool BLOB_BE = false>
 static void launch_ntt_t(const void *in, Fr *out, const Fr28 *tw, int scale_to_raw, int32_t *status, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_ntt4096", st);
+    ProfScope p(BLOB_BE ? "k_ntt4096_be" : "k_ntt4096", st);
     static const hipError_t attr_set =
-        hipFuncSetAttribute((const void *)k_ntt4096<FROM_BLOB>, hipFuncAttributeMaxDynamicSharedMemorySize, kNttLdsBytes);
+        hipFuncSetAttribute((const void *)k_ntt4096<FROM_BLOB, BLOB_BE>, hipFuncAttributeMaxDynamicSharedMemorySize, kNttLdsBytes);
     (void)attr_set;
-    hipLaunchKernelGGL(k_ntt4096<FROM_BLOB>, dim3((unsigned)n_blobs), dim3(kNttThreads), kNttLdsBytes, st, in, out, tw, scale_to_raw,
+    hipLaunchKernelGGL((k_ntt4096<FROM_BLOB, BLOB_BE>), dim3((unsigned)n_blobs), dim3(kNttThreads), kNttLdsBytes, st, in, out, tw, scale_to_raw,
                        status);
 }
 
@@ -159,9 +168,11 @@ void launch_ntt4096(const Fr *in, Fr *out, const Fr28 *tw, int inverse_scale_to_
 
 // mode C front end in one launch: blob bytes (canonical little-endian evaluations, bit-reversed domain order) ->
 // canonical monomial coefficients; status[b] = kStatusBadArgs for a blob with an element >= r
+// le = 0 (eth mode): the elements are canonical big-endian
 void launch_blob_evaluations_to_coefficients(const uint8_t *blobs, uint32_t *coeffs_raw, const Fr28 *tw_inv, int32_t *status,
-                                             size_t n_blobs, hipStream_t st) {
-    launch_ntt_t<true>(blobs, (Fr *)coeffs_raw, tw_inv, 1, status, n_blobs, st);
+                                             size_t n_blobs, hipStream_t st, int le) {
+    if (le) launch_ntt_t<true>(blobs, (Fr *)coeffs_raw, tw_inv, 1, status, n_blobs, st);
+    else launch_ntt_t<true, true>(blobs, (Fr *)coeffs_raw, tw_inv, 1, status, n_blobs, st);
 }
 
 __global__ __launch_bounds__(256) void k_bitrev_permute(const Fr *__restrict__ in, Fr *__restrict__ out, size_t n) {
@@ -461,10 +472,17 @@ __global__ __launch_bounds__(256) void k_roots_brp28(const Fr28 *__restrict__ tw
 void launch_roots_brp28(const Fr28 *tw28, Fr28 *roots, hipStream_t st) {
     hipLaunchKernelGGL(k_roots_brp28, dim3(kBlobElems / 256), dim3(256), 0, st, tw28, roots);
 }
+template <bool BE = false>
 __device__ __forceinline__ Fr28 evalform_load(const uint4 *__restrict__ p) {
     const uint4 lo = p[0], hi = p[1];
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return fr28_pack(w);
+    if constexpr (BE) {   // (an eth-mode blob read in place: big-endian elements)
+        uint32_t w[8];
+        be_element_limbs(w, lo, hi);
+        return fr28_pack(w);
+    } else {
+        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        return fr28_pack(w);
+    }
 }
 // block sum of one lazy value per thread (normalised limbs in, value bound v): the sum of 256 in `out` of every thread, bound 256 v
 template <int kThreads>
@@ -497,7 +515,8 @@ __device__ __forceinline__ void evalform_block_sum2(Fr28 *sh, Fr28 &a, Fr28 &b, 
     b = sh[kThreads];
 }
 
-template <int kThreads>
+// BLOB_BE (eth mode, with `status`): `evals_raw` is a blob of canonical BIG-endian elements; every load swaps, the check is the same
+template <int kThreads, bool BLOB_BE = false>
 __global__ __launch_bounds__(kThreads) void k_eval_quotient_evalform(const uint4 *__restrict__ evals_raw, const Fr *__restrict__ z_mont,
                                                                      const Fr28 *__restrict__ roots, uint4 *__restrict__ quot_raw,
                                                                      uint8_t *__restrict__ y_out, int le, const uint32_t *__restrict__ only_if,
@@ -519,8 +538,14 @@ __global__ __launch_bounds__(kThreads) void k_eval_quotient_evalform(const uint4
 #pragma unroll 4
         for (int k = 0; k < kChunk; k++) {
             const uint4 lo = pin[2 * k * kThreads], hi = pin[2 * k * kThreads + 1];
-            const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            bad = bad || raw_geq<8>(w, FrParams::MOD);
+            if constexpr (BLOB_BE) {
+                uint32_t w[8];
+                be_element_limbs(w, lo, hi);
+                bad = bad || raw_geq<8>(w, FrParams::MOD);
+            } else {
+                const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                bad = bad || raw_geq<8>(w, FrParams::MOD);
+            }
         }
         if (bad) status[blob] = kStatusBadArgs;   // (benign race: same value)
     }
@@ -612,7 +637,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_quotient_evalform(const uint4
         }
         pre[k] = inv_k;
         if (m < 0) {   // (uniform; on the domain y is p_m and the sums are not needed)
-            const Fr28 pk = evalform_load(pin + 2 * k * kThreads);
+            const Fr28 pk = evalform_load<BLOB_BE>(pin + 2 * k * kThreads);
             acc = fr28_add(acc, fr28_mul(pk, inv_k));   // (2, 1) each
             psum = fr28_add(psum, pk);                  // (1, 1) each
             if (k == kChunk / 2) {                      // (8 x 2 units of limb at most between ripples)
@@ -630,7 +655,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_quotient_evalform(const uint4
         yc = fr28_canonical(fr28_mul(a, sh_c));
     } else {
         __syncthreads();
-        if ((m & (kThreads - 1)) == t) tree[0] = evalform_load(pin + 2 * (m - t));
+        if ((m & (kThreads - 1)) == t) tree[0] = evalform_load<BLOB_BE>(pin + 2 * (m - t));
         __syncthreads();
         yc = tree[0];   // p_m
     }
@@ -649,7 +674,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_quotient_evalform(const uint4
     for (int j = 0; j < 10; j++) part.l[j] = 0;
 #pragma unroll 1
     for (int k = 0; k < kChunk; k++) {
-        const Fr28 q = fr28_canonical(fr28_mul(fr28_sub(yc, evalform_load(pin + 2 * k * kThreads)), pre[k]));   // (6, 3) x (2, 1)
+        const Fr28 q = fr28_canonical(fr28_mul(fr28_sub(yc, evalform_load<BLOB_BE>(pin + 2 * k * kThreads)), pre[k]));   // (6, 3) x (2, 1)
         if (k * kThreads + t != m) {
             uint32_t wd[8];
             fr28_unpack(wd, q);
@@ -689,12 +714,19 @@ void launch_eval_quotient_evalform(const uint32_t *evals_raw, const Fr *z_mont, 
 }
 
 // y = p(z) of n c-kzg-mode blobs straight from their bytes (little-endian evaluations; an element >= r: status[blob] = BADARGS), no workspace,
-// any number in one launch: the evaluation of a device-resident batch verification on the Lagrange form
+// any number in one launch: the evaluation of a device-resident batch verification on the Lagrange form. le = 0 (eth mode): the blobs'
+// elements and y are big-endian, the range check is the same
 void launch_eval_y_from_blobs_evalform(const uint8_t *blobs, const Fr *z_mont, const Fr28 *roots_brp28, uint8_t *y_out, int32_t *status,
-                                       size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_eval_quotient_evalform_from_blobs", st);
-    hipLaunchKernelGGL(k_eval_quotient_evalform<256>, dim3((unsigned)n_blobs), dim3(256), 0, st, (const uint4 *)blobs, z_mont, roots_brp28,
-                       (uint4 *)nullptr, y_out, 1, (const uint32_t *)nullptr, status);
+                                       size_t n_blobs, hipStream_t st, int le) {
+    if (le) {
+        ProfScope p("k_eval_quotient_evalform_from_blobs", st);
+        hipLaunchKernelGGL(k_eval_quotient_evalform<256>, dim3((unsigned)n_blobs), dim3(256), 0, st, (const uint4 *)blobs, z_mont, roots_brp28,
+                           (uint4 *)nullptr, y_out, 1, (const uint32_t *)nullptr, status);
+    } else {
+        ProfScope p("k_eval_quotient_evalform_from_blobs_be", st);
+        hipLaunchKernelGGL((k_eval_quotient_evalform<256, true>), dim3((unsigned)n_blobs), dim3(256), 0, st, (const uint4 *)blobs, z_mont, roots_brp28,
+                           (uint4 *)nullptr, y_out, 0, (const uint32_t *)nullptr, status);
+    }
 }
 
 // flags[i] = the 48 bytes at a + 48 i differ from those at b + 48 i (a commitment whose canonical encoding is not what the caller sent)
@@ -793,6 +825,27 @@ void launch_copy_le_check(const uint8_t *blobs, uint32_t *scalars_raw, int32_t *
     hipLaunchKernelGGL(k_copy_le_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)blobs, (uint4 *)scalars_raw, status, n);
 }
 
+// eth-mode blobs on the Lagrange form: canonical BIG-endian elements. The same two 16-byte loads per element, the eight words
+// byte-swapped and reversed into the least-significant-first limbs the MSM reads, the same range check (an element >= r:
+// status[blob] = BADARGS), two 16-byte stores: one pass, memory-bound, the launch geometry of k_copy_le_check
+__global__ __launch_bounds__(256) void k_copy_be_check(const uint4 *__restrict__ blobs, uint4 *__restrict__ scalars_raw,
+                                                       int32_t *__restrict__ status, size_t n_elems) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_elems) return;
+    const uint4 first = blobs[2 * i], second = blobs[2 * i + 1];
+    uint32_t s[8];
+    be_element_limbs(s, first, second);
+    if (status && raw_geq<8>(s, FrParams::MOD)) status[i / kBlobElems] = kStatusBadArgs;
+    scalars_raw[2 * i] = make_uint4(s[0], s[1], s[2], s[3]);
+    scalars_raw[2 * i + 1] = make_uint4(s[4], s[5], s[6], s[7]);
+}
+
+void launch_copy_be_check(const uint8_t *blobs, uint32_t *scalars_raw, int32_t *status, size_t n_blobs, hipStream_t st) {
+    ProfScope p("k_copy_be_check", st);
+    const size_t n = n_blobs * kBlobElems;
+    hipLaunchKernelGGL(k_copy_be_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)blobs, (uint4 *)scalars_raw, status, n);
+}
+
 // Quotients of a proof call whose MSM runs on the Lagrange form while the quotient was computed in coefficient form (a Lagrange-form
 // table with no monomial table beside it): coefficients -> evaluations on the bit-reversed domain, i.e. a forward transform. Entry:
 // canonical raw coefficient k -> Montgomery form at position bitrev(k) (the transform is decimation in time); exit: Montgomery
@@ -845,22 +898,23 @@ void launch_fr_mont_to_bytes(const Fr *in, uint8_t *out, int le, size_t n, hipSt
 }
 
 __global__ __launch_bounds__(64) void k_z_from_bytes(const uint8_t *__restrict__ zb, Fr *__restrict__ z_mont,
-                                                     int32_t *__restrict__ status, int le, size_t n) {
+                                                     int32_t *__restrict__ status, int scalar_rule, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t s[8];
-    if (le) {
+    if (scalar_rule == kScalarLeCanonical) {
         raw_from_le<8>(s, zb + 32 * i);
         if (status && raw_geq<8>(s, FrParams::MOD)) status[i] = kStatusBadArgs;  // status == NULL: reduce silently (digests)
     } else {
         raw_from_be<8>(s, zb + 32 * i);
+        if (scalar_rule == kScalarBeCanonical && status && raw_geq<8>(s, FrParams::MOD)) status[i] = kStatusBadArgs;   // eth mode's z: big-endian AND canonical
     }
     z_mont[i] = fe_from_raw<FrParams>(s);  // reduces when >= r (reference mode)
 }
 
-void launch_z_from_bytes(const uint8_t *z_bytes, Fr *z_mont, int32_t *status, int le, size_t n, hipStream_t st) {
+void launch_z_from_bytes(const uint8_t *z_bytes, Fr *z_mont, int32_t *status, int scalar_rule, size_t n, hipStream_t st) {
     ProfScope p("k_z_from_bytes", st);
-    hipLaunchKernelGGL(k_z_from_bytes, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, z_bytes, z_mont, status, le, n);
+    hipLaunchKernelGGL(k_z_from_bytes, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, z_bytes, z_mont, status, scalar_rule, n);
 }
 
 }  // namespace lwk

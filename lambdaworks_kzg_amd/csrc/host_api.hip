@@ -33,7 +33,7 @@ static C_KZG_RET collect_status(Ctx *c, const int32_t *d_status, size_t n, size_
 // In reference mode every failure is C_KZG_ERROR (lib.rs:263,267,272,...).
 C_KZG_RET map_rc(C_KZG_RET rc, int mode) {
     if (rc == C_KZG_OK) return rc;
-    if (mode == LWKZG_MODE_REFERENCE) return C_KZG_ERROR;
+    if (mode_rules(mode).bad == C_KZG_ERROR) return C_KZG_ERROR;
     return rc;
 }
 
@@ -112,7 +112,7 @@ static void combine_run(Ctx *c, int lane, const std::vector<CombineReq *> &batch
             // clears them on its way) and the second pass that exits at once on honest data (the redo flag is a pinned word this thread
             // looks at after its one synchronisation; a flagged call -- P = +-Q inside a quad: chosen scalars only -- is repeated the long way)
             uint32_t ctr_words = 0;
-            if (zero_copy && mode == LWKZG_MODE_REFERENCE && c->direct_table) ctr_words = direct_one_blob_counter_words(c->direct_bits);
+            if (zero_copy && mode_rules(mode).parse_cannot_fail() && c->direct_table) ctr_words = direct_one_blob_counter_words(c->direct_bits);
             if (ctr_words) {
                 redo_flag = (uint32_t *)&cb.pinned_status[lane][1];
                 *redo_flag = 0;
@@ -120,7 +120,7 @@ static void combine_run(Ctx *c, int lane, const std::vector<CombineReq *> &batch
             for (size_t i = 0; i < n && ok && !zero_copy; i++)
                 ok = hipMemcpyAsync(d_blobs + i * (size_t)kBlobBytes, cb.pinned_blobs + (size_t)batch[i]->slot * kBlobBytes, kBlobBytes,
                                     hipMemcpyHostToDevice, sk) == hipSuccess;
-            const bool verdicts = !(zero_copy && mode == LWKZG_MODE_REFERENCE);
+            const bool verdicts = !(zero_copy && mode_rules(mode).parse_cannot_fail());
             if (verdicts) ok = ok && hipMemsetAsync(w.status + lo, 0, n * 4, sk) == hipSuccess;
             else cb.pinned_status[lane][0] = 0;
             if (ok) {
@@ -335,7 +335,8 @@ namespace {
 C_KZG_RET point_proofs_sliced(Ctx *c, uint8_t *proofs_out, uint8_t *ys_out, const uint8_t *blobs, const uint8_t *zs, size_t n,
                               int mode, size_t *first_bad) {
     constexpr size_t kSlice = kMaxChunk / 2;
-    const int le = mode == LWKZG_MODE_CKZG;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le();
     C_KZG_RET rc = ctx_reserve(c, kMaxChunk);
     if (rc != C_KZG_OK) return rc;
     Workspace &w = c->ws;
@@ -363,7 +364,7 @@ C_KZG_RET point_proofs_sliced(Ctx *c, uint8_t *proofs_out, uint8_t *ys_out, cons
         uint8_t *d_blobs = w.blobs + lo * (size_t)kBlobBytes;
         LWK_HIP(hipMemcpyAsync(d_blobs, blobs + off * (size_t)kBlobBytes, cnt * (size_t)kBlobBytes, hipMemcpyHostToDevice, sk));
         coefficients_stage(c, d_blobs, cnt, mode, d_status + off, sk, lo);
-        launch_z_from_bytes(d_z + 32 * off, w.z + lo, d_status + off, le, cnt, sk);
+        launch_z_from_bytes(d_z + 32 * off, w.z + lo, d_status + off, mr.scalar_rule(), cnt, sk);
         quotient_stage(c, mode, w.scalars + so, w.z + lo, w.scalars2 + so, d_y + 32 * off, le, cnt, sk);
         msm_stages(c, w.scalars2 + so, d_out + 48 * off, cnt, sk, lo, false, quotient_to_msm_form(c, mode, cnt, sk, lo));
     }
@@ -390,7 +391,8 @@ C_KZG_RET point_proofs_sliced(Ctx *c, uint8_t *proofs_out, uint8_t *ys_out, cons
 C_KZG_RET blob_proofs_sliced(Ctx *c, uint8_t *out, const uint8_t *blobs, const uint8_t *comm48, size_t n, int mode,
                              size_t *first_bad) {
     constexpr size_t kSlice = kMaxChunk / 2;
-    const int le = mode == LWKZG_MODE_CKZG;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le();
     C_KZG_RET rc = ctx_reserve(c, kMaxChunk);
     if (rc != C_KZG_OK) return rc;
     Workspace &w = c->ws;
@@ -417,7 +419,7 @@ C_KZG_RET blob_proofs_sliced(Ctx *c, uint8_t *out, const uint8_t *blobs, const u
     LWK_HIP(hipStreamWaitEvent(c->aux[0], c->ev_fork, 0));
     LWK_HIP(hipStreamWaitEvent(c->aux[1], c->ev_fork, 0));
     LWK_HIP(hipMemcpyAsync(d_comm, comm48, n * 48, hipMemcpyHostToDevice, sv));
-    launch_validate_commitments(d_comm, d_canon, d_status, le ? kStatusBadArgs : kStatusError, n, sv);  // lib.rs:372-375
+    launch_validate_commitments(d_comm, d_canon, d_status, mr.bad_status(), n, sv);  // lib.rs:372-375
     LWK_HIP(hipEventRecord(c->ev_join[kMaxSplit - 1], sv));
     bool validated = false;
     // (r06: slices on two streams stay -- the staged whole-chunk schedule of the commitments measured 84.9k against 88.1k proofs/s here)
@@ -431,7 +433,8 @@ C_KZG_RET blob_proofs_sliced(Ctx *c, uint8_t *out, const uint8_t *blobs, const u
         uint8_t *dig = h_dig.data() + 32 * off;
         // the host threads hash the slice (the digests assume canonical commitment bytes) beside its upload, which blocks this thread while
         // the runtime stages it
-        SideTask hasher([=]() { challenge_digests_host(dig, hb, hc, cnt); });
+        const bool be_fields = mr.be_transcript;
+        SideTask hasher([=]() { challenge_digests_host(dig, hb, hc, cnt, be_fields); });
         const auto ta = now();
         LWK_HIP(hipMemcpyAsync(d_blobs, hb, cnt * (size_t)kBlobBytes, hipMemcpyHostToDevice, sk));
         const auto tb = now();
@@ -451,7 +454,7 @@ C_KZG_RET blob_proofs_sliced(Ctx *c, uint8_t *out, const uint8_t *blobs, const u
             LWK_HIP(hipMemcpyAsync(d_dig + 32 * off, dig, cnt * 32, hipMemcpyHostToDevice, sk));
             launch_z_from_bytes(d_dig + 32 * off, w.z + lo, nullptr, le, cnt, sk);  // digest -> Fr, reduced (utils.rs:148-154)
         } else {  // a non-canonical (or invalid) encoding in this slice: hash the canonical bytes on the GPU
-            launch_challenge(d_blobs, d_canon + 48 * off, w.z + lo, le, cnt, sk);
+            launch_challenge(d_blobs, d_canon + 48 * off, w.z + lo, mr.hash_rule(), cnt, sk);
         }
         quotient_stage(c, mode, w.scalars + so, w.z + lo, w.scalars2 + so, nullptr, le, cnt, sk);
         msm_stages(c, w.scalars2 + so, d_out + 48 * off, cnt, sk, lo, false, quotient_to_msm_form(c, mode, cnt, sk, lo));
@@ -487,7 +490,7 @@ C_KZG_RET blob_proofs_sliced(Ctx *c, uint8_t *out, const uint8_t *blobs, const u
 // undefined behaviour that the host-UBSan run of the GPU suite caught.) Caller holds c->mu and the workspace.
 static const int kOneBlobFallback = 100;   // (not a value of the ABI: internal)
 static int blob_proof_one_host(Ctx *c, uint8_t *out48, const uint8_t *blob, const uint8_t *comm48, int mode) {
-    if (mode != LWKZG_MODE_REFERENCE || !c->direct_table || !knobs().zero_copy || peer_busy(c)) return kOneBlobFallback;
+    if (!mode_rules(mode).parse_cannot_fail() || !c->direct_table || !knobs().zero_copy || peer_busy(c)) return kOneBlobFallback;
     const uint32_t ctr_words = direct_one_blob_counter_words(c->direct_bits);
     if (!ctr_words) return kOneBlobFallback;
     if (!c->one_pin && hipHostMalloc((void **)&c->one_pin, 4096, hipHostMallocDefault) != hipSuccess) {
@@ -535,14 +538,15 @@ static C_KZG_RET blob_proof_batch_host(Ctx *c, KZGProof *out, const Blob *blobs,
         if (rc != C_KZG_OK) return rc;
         Workspace &w = c->ws;
         hipStream_t st = c->stream;
-        const int le = mode == LWKZG_MODE_CKZG;
+        const ModeRules mr = mode_rules(mode);
+    const int le = mr.le();
         const uint8_t *h_blobs = (const uint8_t *)(blobs + off), *h_comm = (const uint8_t *)(commitments + off);
         // host threads start hashing at once (the blobs are in host memory here; one GPU lane would need ~7 ms per
         // 131 KB message, a core with SHA extensions ~0.1 ms) and run beside the pageable H2D copy, which blocks
         // this thread for a few milliseconds. The digests assume the caller's commitment bytes are the canonical
         // encoding; the validation's re-compression confirms or refutes that below.
         std::vector<uint8_t> h_canon(m * 48), h_dig(m * 32);
-        SideTask hasher([&]() { challenge_digests_host(h_dig.data(), h_blobs, h_comm, m); });
+        SideTask hasher([&]() { challenge_digests_host(h_dig.data(), h_blobs, h_comm, m, mr.be_transcript); });
         LWK_HIP(hipMemcpyAsync(w.blobs, h_blobs, m * (size_t)kBlobBytes, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemcpyAsync(w.comm48, h_comm, m * 48, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemsetAsync(w.status, 0, m * 4, st));
@@ -551,11 +555,11 @@ static C_KZG_RET blob_proof_batch_host(Ctx *c, KZGProof *out, const Blob *blobs,
         // (~0.2 ms each on the 64-bit host field, against a 2 ms latency-shaped kernel). A batch: on the GPU, on an
         // auxiliary stream beside everything else.
         const bool host_validate = m <= host_small_batch_limit();
-        std::vector<int32_t> h_code(m, le ? kStatusBadArgs : kStatusError);
+        std::vector<int32_t> h_code(m, mr.bad_status());
         if (!host_validate) {
             LWK_HIP(hipEventRecord(c->ev_fork, st));
             LWK_HIP(hipStreamWaitEvent(c->vstream, c->ev_fork, 0));
-            launch_validate_commitments(w.comm48, w.canon48, w.status, le ? kStatusBadArgs : kStatusError, m, c->vstream, w.val_pts, w.val_kind, w.val_verdict);
+            launch_validate_commitments(w.comm48, w.canon48, w.status, mr.bad_status(), m, c->vstream, w.val_pts, w.val_kind, w.val_verdict);
             LWK_HIP(hipEventRecord(c->ev_join[0], c->vstream));
         }
         // GPU, main stream: parse the blobs, then the digests as soon as the host threads have them
@@ -591,7 +595,7 @@ static C_KZG_RET blob_proof_batch_host(Ctx *c, KZGProof *out, const Blob *blobs,
             // a non-canonical but valid encoding somewhere in the chunk (or an invalid point, reported through
             // status): redo the chunk with the hash taken over the canonical bytes on the GPU
             if (host_validate) LWK_HIP(hipMemcpyAsync(w.canon48, h_canon.data(), m * 48, hipMemcpyHostToDevice, st));
-            launch_challenge(w.blobs, w.canon48, w.z, le, m, st);
+            launch_challenge(w.blobs, w.canon48, w.z, mr.hash_rule(), m, st);
             coefficients_stage(c, w.blobs, m, mode, w.status, st);  // (the first attempt's forward transform may have used them as scratch)
             quotient_stage(c, mode, w.scalars, w.z, w.scalars2, nullptr, le, m, st);
             quotient_msm();

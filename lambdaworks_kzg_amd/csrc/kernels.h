@@ -6,6 +6,7 @@
 #include "g1.cuh"
 #include "fr28.cuh"
 #include "plan.h"
+#include "mode_rules.h"
 #include "recover_sets.h"
 
 namespace lwk {
@@ -106,7 +107,7 @@ void launch_build_twiddles(Fr *tw_fwd, Fr *tw_inv, hipStream_t st);
 void launch_twiddles_to28(const Fr *tw, Fr28 *tw28, hipStream_t st);
 void launch_ntt4096(const Fr *in, Fr *out, const Fr28 *tw28, int inverse_scale_to_raw, size_t n_blobs, hipStream_t st);
 void launch_blob_evaluations_to_coefficients(const uint8_t *blobs, uint32_t *coeffs_raw, const Fr28 *tw28_inv, int32_t *status,
-                                             size_t n_blobs, hipStream_t st);
+                                             size_t n_blobs, hipStream_t st, int le = 1);   // le = 0: canonical big-endian elements (eth mode)
 void launch_bitrev_permute(const Fr *in, Fr *out, size_t n_blobs, hipStream_t st);
 // c-kzg mode on the Lagrange form of the setup (fr_ops.hip): the 4096 rows of inverse-DFT coefficients whose
 // commitments are the Lagrange points; the copy + range check that replaces the transform in front of a commitment; and the forward
@@ -116,6 +117,8 @@ void launch_idft_columns(uint32_t *coeffs_raw, const Fr *tw_inv, uint32_t first,
 // whose MSM over the Lagrange form is the monomial point [tau^(first + b)]G
 void launch_dft_rows(uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t first, size_t n_rows, hipStream_t st);
 void launch_copy_le_check(const uint8_t *blobs, uint32_t *scalars_raw, int32_t *status, size_t n_blobs, hipStream_t st);
+// eth mode's twin: canonical big-endian elements -> the same least-significant-first limbs, the same range check
+void launch_copy_be_check(const uint8_t *blobs, uint32_t *scalars_raw, int32_t *status, size_t n_blobs, hipStream_t st);
 void launch_coefficients_to_evaluations(uint32_t *coeffs_raw, Fr *scratch, Fr *scratch2, const Fr28 *tw28_fwd, size_t n_blobs, hipStream_t st);
 void launch_fr_be_to_mont(const uint8_t *in_be, Fr *out, size_t n_elems, hipStream_t st);
 void launch_fr_mont_to_be(const Fr *in, uint8_t *out_be, size_t n_elems, hipStream_t st);
@@ -131,7 +134,7 @@ void launch_eval_quotient(const uint32_t *coeffs_raw, const Fr *z_mont, uint32_t
 // y = p(z) of reference-mode blobs straight from their bytes, any number in one launch (batch verification)
 void launch_eval_y_from_blobs_be(const uint8_t *blobs, const Fr *z_mont, uint8_t *y_out, size_t n_blobs, hipStream_t st);
 void launch_eval_y_from_blobs_evalform(const uint8_t *blobs, const Fr *z_mont, const Fr28 *roots_brp28, uint8_t *y_out, int32_t *status,
-                                       size_t n_blobs, hipStream_t st);   // c-kzg mode: little-endian evaluations, range-checked
+                                       size_t n_blobs, hipStream_t st, int le = 1);   // le = 1 (c-kzg mode): little-endian evaluations, range-checked; le = 0 (eth mode): big-endian, range-checked
 // the same in evaluation form (c-kzg mode on the Lagrange form): evaluations in, the quotient's evaluations out, y = p(z) by the barycentric formula
 // roots_brp28: the 4096 domain points in element order (launch_roots_brp28 writes them from the transform's twiddles, once per setup)
 void launch_roots_brp28(const Fr28 *tw28_fwd, Fr28 *roots_brp28, hipStream_t st);
@@ -139,8 +142,10 @@ void launch_eval_quotient_evalform(const uint32_t *evals_raw, const Fr *z_mont, 
                                    size_t n_blobs, hipStream_t st, const uint32_t *only_if = nullptr);
 // flags[i] = (a[48 i ..] != b[48 i ..])
 void launch_flag_differs48(const uint8_t *a, const uint8_t *b, uint32_t *flags, size_t n, hipStream_t st);
-// z bytes -> Montgomery. le = 0: big-endian, reduced. le = 1: little-endian, must be canonical else BADARGS.
-void launch_z_from_bytes(const uint8_t *z_bytes, Fr *z_mont, int32_t *status, int le, size_t n, hipStream_t st);
+// z bytes -> Montgomery. scalar_rule (mode_rules.h): kScalarBeReduced = big-endian, reduced; kScalarLeCanonical = little-endian, must be
+// canonical else BADARGS; kScalarBeCanonical = big-endian, must be canonical else BADARGS. A digest is read with status = NULL and the
+// byte order alone (ModeRules::le(), 0 or 1): reduced silently
+void launch_z_from_bytes(const uint8_t *z_bytes, Fr *z_mont, int32_t *status, int scalar_rule, size_t n, hipStream_t st);
 
 // ---- point validation (validate.hip)
 // one set of compressed G1 points on its way through the validation: in48 -> pts / kind (0 = affine, 1 = infinity, 2 = invalid), the
@@ -214,27 +219,29 @@ void launch_verify_ysum(const uint8_t *y32, int le, const Fr *pw, uint8_t *out32
 // records[160 i] = C_i | z_i | y_i | pi_i from the device-resident pieces; *first_bad = lowest index with a status word set (pre-set to 0xffffffff)
 void launch_verify_records(const uint8_t *canon_c, const uint8_t *z32, const uint8_t *y32, const uint8_t *canon_p, const int32_t *status,
                            uint8_t *records, uint32_t *first_bad, size_t n, hipStream_t st);
-// verify_each.hip: z / y of n openings checked (c-kzg: little-endian, < r; reference: big-endian, reduced) and written canonical in the
-// mode's byte order; a rejected item gets bad_code in status
-void launch_each_openings(const uint8_t *z_in, const uint8_t *y_in, uint8_t *z_out, uint8_t *y_out, int32_t *status, int bad_code, int le,
-                          size_t n, hipStream_t st);
+// verify_each.hip: z / y of n openings checked by scalar_rule (c-kzg: little-endian, < r; eth: big-endian, < r; reference: big-endian,
+// reduced) and written canonical in the mode's byte order; a rejected item gets bad_code in status
+void launch_each_openings(const uint8_t *z_in, const uint8_t *y_in, uint8_t *z_out, uint8_t *y_out, int32_t *status, int bad_code,
+                          int scalar_rule, size_t n, hipStream_t st);
 void launch_xyzz29_to_affine_be(const G1Xyzz29 *in, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st);
 
 // ---- Fiat-Shamir (sha256.hip, sha256_host.hip)
 // z = sha256("FSBLOBVERIFY_V1_" | le64(4096) | le64(0) | blob | commitment) as Fr (compute_challenge, /root/reference/src/utils.rs:120-154)
-void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, int le, size_t n, hipStream_t st,
+// hash_rule (mode_rules.h: ModeRules::hash_rule()) -- kHashDigestLe: the digest is read little-endian; kHashFieldsBe (eth mode): the degree field is be128(4096). The
+// midstate takes the degree field's rule alone (be_fields); the finish never meets that field.
+void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, int hash_rule, size_t n, hipStream_t st,
                       const uint8_t *only_if_differs_from = nullptr);
-void launch_challenge_midstate(const uint8_t *blobs, uint32_t *midstate, size_t n, hipStream_t st);
-void launch_challenge_finish(const uint8_t *blobs, const uint8_t *canon48, const uint32_t *midstate, Fr *z_mont, int le, size_t n,
+void launch_challenge_midstate(const uint8_t *blobs, uint32_t *midstate, size_t n, hipStream_t st, bool be_fields = false);
+void launch_challenge_finish(const uint8_t *blobs, const uint8_t *canon48, const uint32_t *midstate, Fr *z_mont, int hash_rule, size_t n,
                              hipStream_t st);
 // sha256_host.hip: host SHA-256 -- portable | with the SHA extensions when present | the same of prefix | msg without the concatenation
 void sha256_host(uint8_t out[32], const uint8_t *msg, size_t len);
 void sha256_fast(uint8_t out[32], const uint8_t *msg, size_t len);
 void sha256_fast_prefixed(uint8_t out[32], const uint8_t *prefix, size_t prefix_len, const uint8_t *msg, size_t len);
 // sha256_host.hip: digests[i] = SHA-256("FSBLOBVERIFY_V1_" | le64(4096) | le64(0) | blobs[i] | comms[i]) on host threads
-void challenge_digests_host(uint8_t *digests32, const uint8_t *blobs, const uint8_t *comms48, size_t n);
+void challenge_digests_host(uint8_t *digests32, const uint8_t *blobs, const uint8_t *comms48, size_t n, bool be_fields = false);   // be_fields (eth mode): | be128(4096) | in place of the two le64
 double host_hash_rate();   // bytes per second the host threads hashed in their recent long jobs (sha256_host.hip)
-void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n);   // 8 words per blob: the hash state k_challenge_finish continues from
+void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n, bool be_fields = false);   // 8 words per blob: the hash state k_challenge_finish continues from
 
 // ---- EIP-7594 cells (cells.hip)
 constexpr int kCellElems = 64;        // field elements per cell

@@ -15,7 +15,7 @@ namespace lwk {
 
 struct Knobs {
     // ---- operational ------------------------------------------------------------------------------------------------------------
-    int mode = 0;                    // LWKZG_MODE: process default semantics, "reference" (0) | "ckzg" (1)
+    int mode = 0;                    // LWKZG_MODE: process default semantics, "reference" (0) | "ckzg" (1) | "eth" (2)
     bool has_direct_bits = false;    // LWKZG_DIRECT_BITS: 0 (bucket engine) | 10..16 | "auto" (widest that fits) ; unset: 13..10 within a quarter of free HBM
     int direct_bits = 0;             //   (-1 = auto)
     int direct_row = 0;              // LWKZG_DIRECT_ROW: 0 = choose, 112 = packed rows, 128 = line-aligned rows

@@ -50,7 +50,7 @@ Knobs read_env() {
     const Reader r{k.experimental};
     constexpr bool OP = false, EXP = true;
     if (const char *e = r.get("LWKZG_MODE", OP))
-        k.mode = (!strcmp(e, "ckzg") || !strcmp(e, "c") || !strcmp(e, "C") || !strcmp(e, "1")) ? 1 : 0;
+        k.mode = (!strcmp(e, "ckzg") || !strcmp(e, "c") || !strcmp(e, "C") || !strcmp(e, "1")) ? 1 : (!strcmp(e, "eth") || !strcmp(e, "2")) ? 2 : 0;
     if (const char *e = r.get("LWKZG_DIRECT_BITS", OP)) {
         k.has_direct_bits = true;
         k.direct_bits = !strcmp(e, "auto") ? -1 : atoi(e);

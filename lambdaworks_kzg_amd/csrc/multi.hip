@@ -223,7 +223,7 @@ int lwkzg_multi_device(const LwkzgMulti *m, size_t k) { return m && k < m->dev.s
 const KZGSettings *lwkzg_multi_settings(const LwkzgMulti *m, size_t k) { return m && k < m->s.size() ? &m->s[k] : nullptr; }
 
 C_KZG_RET lwkzg_multi_set_mode(const LwkzgMulti *m, int mode) {
-    if (!m || mode < -1 || mode > LWKZG_MODE_CKZG) return C_KZG_BADARGS;
+    if (!m || mode < -1 || (mode != -1 && !mode_known(mode))) return C_KZG_BADARGS;
     for (const KZGSettings &s : m->s)
         if (lwkzg_settings_set_mode(&s, mode) < 0) return C_KZG_ERROR;
     return C_KZG_OK;

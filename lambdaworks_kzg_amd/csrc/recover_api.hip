@@ -103,7 +103,7 @@ C_KZG_RET recover_setup(Ctx *c, const Lists &l, const RecoverSets &sets, Recover
 // cells_in: the cells of blob b0 on; status: n words, 0 or the mode's rejection code
 C_KZG_RET recover_device(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, const Lists &l, const RecoverSets &sets, const RecoverSetsDev &dev,
                          const uint8_t *cells_in, size_t b0, size_t n, int mode, hipStream_t st, int32_t *status, size_t n_call) {
-    const int le = mode == LWKZG_MODE_CKZG, bad = (int)bad_input(mode);
+    const int le = mode_rules(mode).le(), bad = (int)bad_input(mode);
     return cells_chunks(c, cells_out, proofs48, n, mode, st, status, [&](size_t off, size_t m, int32_t *stt) {
         if (!l.mixed) {   // the whole chunk in one launch of each kernel
             launch_recover_coefficients(cells_in + off * *l.num_cells * kCellBytes, sets.sets[0], *l.num_cells, c->tw_fwd, c->tw_inv,

@@ -18,13 +18,16 @@ namespace lwk {
 //   2..8193   blob
 //   8194..8196 commitment
 //   8197      0x80 then zeros, 8198 zeros, 8199 zeros + 64-bit big-endian bit length
+// BE_DEG (eth mode): chunk 1 is the consensus specs' be128(4096) -- 8 zero bytes, then be64(4096). The degree field is a property of its
+// own, not the digest's byte order: reference mode has the little-endian field and reads its digest big-endian.
+template <bool BE_DEG = false>
 __device__ __forceinline__ uint4 challenge_chunk(int q, const uint4 *blob, const uint4 *comm) {
     if (q >= 2 && q < 2 + kBlobBytes / 16) {
         uint4 v = blob[q - 2];
         return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
     }
     if (q == 0) return make_uint4(0x4653424cu, 0x4f425645u, 0x52494659u, 0x5f56315fu);  // "FSBL" "OBVE" "RIFY" "_V1_"
-    if (q == 1) return make_uint4(0x00100000u, 0u, 0u, 0u);                             // 4096 little-endian, then 0
+    if (q == 1) return BE_DEG ? make_uint4(0u, 0u, 0u, 0x00001000u) : make_uint4(0x00100000u, 0u, 0u, 0u);   // 4096 little-endian, then 0 | be128(4096)
     if (q < 2 + kBlobBytes / 16 + 3) {
         uint4 v = comm[q - 2 - kBlobBytes / 16];
         return make_uint4(__builtin_bswap32(v.x), __builtin_bswap32(v.y), __builtin_bswap32(v.z), __builtin_bswap32(v.w));
@@ -46,6 +49,7 @@ __device__ __forceinline__ uint4 challenge_chunk(int q, const uint4 *blob, const
 // only_if_differs_from (optional): the fix-up pass of the optimistic pipeline -- z was already computed from
 // these (caller-supplied) commitment bytes while the validation kernel ran; lanes whose canonical bytes are
 // identical have nothing to redo, and a workgroup without any lane left exits at once.
+template <bool BE_DEG = false>
 __global__ __launch_bounds__(128) void k_challenge(const uint8_t *__restrict__ blobs, const uint8_t *__restrict__ canon48,
                                                    Fr *__restrict__ z_mont, int le, size_t n,
                                                    const uint8_t *__restrict__ only_if_differs_from) {
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(128) void k_challenge(const uint8_t *__restrict__ b
     uint4 nxt[4];
     if (role == 0) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) nxt[q] = challenge_chunk(q, blob, comm);
+        for (int q = 0; q < 4; q++) nxt[q] = challenge_chunk<BE_DEG>(q, blob, comm);
     }
     for (int it = 0; it <= kBlocks; it++) {
         if (role == 0) {
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(128) void k_challenge(const uint8_t *__restrict__ b
                 }
                 if (it + 1 < kBlocks) {  // the next block's loads fly while this one is expanded
 #pragma unroll
-                    for (int q = 0; q < 4; q++) nxt[q] = challenge_chunk(4 * (it + 1) + q, blob, comm);
+                    for (int q = 0; q < 4; q++) nxt[q] = challenge_chunk<BE_DEG>(4 * (it + 1) + q, blob, comm);
                 }
                 uint4(*dst)[64] = wk[it & 1];
 #pragma unroll
@@ -188,7 +192,7 @@ __global__ __launch_bounds__(128) void k_challenge(const uint8_t *__restrict__ b
 // the blob) are absorbed, and the chaining value goes to `midstate` (8 words per blob) instead of a challenge: the fused
 // commit-and-prove entry point runs this beside the commitment MSM and finishes with k_challenge_finish once the
 // commitments exist.
-template <bool MID>
+template <bool MID, bool BE_DEG = false>
 __global__ __launch_bounds__(256) void k_challenge_pairs(const uint8_t *__restrict__ blobs, const uint8_t *__restrict__ canon48,
                                                          Fr *__restrict__ z_mont, int le, size_t n,
                                                          const uint8_t *__restrict__ only_if_differs_from, int prio,
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(256) void k_challenge_pairs(const uint8_t *__restri
     int pblock = role;  // the block this producer is expanding (role 0: 0, 2, 4, ...; role 1: 1, 3, 5, ...)
     if (producer) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) nxt[q] = challenge_chunk(4 * pblock + q, blob, comm);
+        for (int q = 0; q < 4; q++) nxt[q] = challenge_chunk<BE_DEG>(4 * pblock + q, blob, comm);
     }
     for (int it = 0; it < kBlocks + 2; it++) {
         if (producer) {
@@ -250,7 +254,7 @@ __global__ __launch_bounds__(256) void k_challenge_pairs(const uint8_t *__restri
                     }
                     if (pblock + 2 < kBlocks) {  // this producer's next block: its loads have two intervals to land
 #pragma unroll
-                        for (int q = 0; q < 4; q++) nxt[q] = challenge_chunk(4 * (pblock + 2) + q, blob, comm);
+                        for (int q = 0; q < 4; q++) nxt[q] = challenge_chunk<BE_DEG>(4 * (pblock + 2) + q, blob, comm);
                     }
 #pragma unroll
                     for (int t = 0; t < 32; t += 4) {
@@ -323,28 +327,39 @@ __global__ __launch_bounds__(256) void k_challenge_pairs(const uint8_t *__restri
     z_mont[i] = fe_from_raw<FrParams>(sdig);  // reduced mod r
 }
 
-void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, int le, size_t n, hipStream_t st,
+void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, int hash_rule, size_t n, hipStream_t st,
                       const uint8_t *only_if_differs_from) {
     if (n == 0) return;
     const bool pairs = knobs().hash_pairs;
     const int prio = knobs().hash_prio;
+    const bool be_deg = (hash_rule & kHashFieldsBe) != 0;   // (mode_rules.h)
+    const int le = hash_rule & kHashDigestLe;                // the digest's byte order, as the kernels take it
     ProfScope p(only_if_differs_from ? "k_challenge_fixup" : "k_challenge", st);
-    if (pairs)
-        hipLaunchKernelGGL(k_challenge_pairs<false>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, blobs, canon48, z_mont, le, n,
-                           only_if_differs_from, prio, (uint32_t *)nullptr);
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (pairs && be_deg)
+        hipLaunchKernelGGL((k_challenge_pairs<false, true>), grid, dim3(256), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from, prio,
+                           (uint32_t *)nullptr);
+    else if (pairs)
+        hipLaunchKernelGGL(k_challenge_pairs<false>, grid, dim3(256), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from, prio,
+                           (uint32_t *)nullptr);
+    else if (be_deg)
+        hipLaunchKernelGGL(k_challenge<true>, grid, dim3(128), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from);
     else
-        hipLaunchKernelGGL(k_challenge, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, st, blobs, canon48, z_mont, le, n,
-                           only_if_differs_from);
+        hipLaunchKernelGGL(k_challenge<false>, grid, dim3(128), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from);
 }
 
 // ---- the challenge in two parts (fused commit-and-prove: engine.hip) ------------------------------------------------
 // part 1: everything the commitment does not touch (2048 of the 2050 blocks), beside the commitment MSM
-void launch_challenge_midstate(const uint8_t *blobs, uint32_t *midstate, size_t n, hipStream_t st) {
+void launch_challenge_midstate(const uint8_t *blobs, uint32_t *midstate, size_t n, hipStream_t st, bool be_fields) {
     if (n == 0) return;
     const int prio = knobs().hash_prio;
     ProfScope p("k_challenge_midstate", st);
-    hipLaunchKernelGGL(k_challenge_pairs<true>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, blobs, (const uint8_t *)nullptr,
-                       (Fr *)nullptr, 0, n, (const uint8_t *)nullptr, prio, midstate);
+    if (be_fields)
+        hipLaunchKernelGGL((k_challenge_pairs<true, true>), dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, blobs, (const uint8_t *)nullptr,
+                           (Fr *)nullptr, 0, n, (const uint8_t *)nullptr, prio, midstate);
+    else
+        hipLaunchKernelGGL(k_challenge_pairs<true>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, blobs, (const uint8_t *)nullptr,
+                           (Fr *)nullptr, 0, n, (const uint8_t *)nullptr, prio, midstate);
 }
 
 // part 2: the last two blocks (32 bytes of blob, the 48 commitment bytes, padding and length), one lane per blob
@@ -390,11 +405,12 @@ __global__ __launch_bounds__(64) void k_challenge_finish(const uint8_t *__restri
     z_mont[i] = fe_from_raw<FrParams>(sdig);  // reduced mod r
 }
 
-void launch_challenge_finish(const uint8_t *blobs, const uint8_t *canon48, const uint32_t *midstate, Fr *z_mont, int le, size_t n,
+void launch_challenge_finish(const uint8_t *blobs, const uint8_t *canon48, const uint32_t *midstate, Fr *z_mont, int hash_rule, size_t n,
                              hipStream_t st) {
     if (n == 0) return;
     ProfScope p("k_challenge_finish", st);
-    hipLaunchKernelGGL(k_challenge_finish, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, blobs, canon48, midstate, z_mont, le, n);
+    // (the last two blocks hold no degree field: of the hash rule only the digest's byte order matters here)
+    hipLaunchKernelGGL(k_challenge_finish, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, blobs, canon48, midstate, z_mont, hash_rule & kHashDigestLe, n);
 }
 
 }  // namespace lwk

@@ -133,13 +133,16 @@ Compress best_compress() { return have_shani() ? compress_shani : sha256_blocks_
 
 const uint8_t kChallengeHeader[32] = {'F', 'S', 'B', 'L', 'O', 'B', 'V', 'E', 'R', 'I', 'F', 'Y', '_', 'V', '1', '_',
                                       0x00, 0x10, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+// the consensus specs' header (eth mode): the degree as be128(4096)
+const uint8_t kChallengeHeaderBe[32] = {'F', 'S', 'B', 'L', 'O', 'B', 'V', 'E', 'R', 'I', 'F', 'Y', '_', 'V', '1', '_',
+                                        0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0x10, 0x00};
 
 // digest of header(32) | blob(131072) | commitment(48), the compute_challenge message
-void challenge_digest(uint8_t out[32], const uint8_t *blob, const uint8_t *comm48) {
+void challenge_digest(uint8_t out[32], const uint8_t *blob, const uint8_t *comm48, bool be_fields = false) {
     const Compress compress = best_compress();
     uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
     uint8_t blk[64];
-    memcpy(blk, kChallengeHeader, 32);
+    memcpy(blk, be_fields ? kChallengeHeaderBe : kChallengeHeader, 32);
     memcpy(blk + 32, blob, 32);
     compress(h, blk, 1);
     compress(h, blob + 32, (kBlobBytes - 64) / 64);       // 2047 whole blocks straight from the blob
@@ -454,13 +457,13 @@ void host_pool_warm() {
 // mid[8 i .. 8 i + 7] = the SHA-256 chaining value after the 2048 blocks of the compute_challenge message that do not contain a byte of
 // the commitment (header | blob without its last 32 bytes): what k_challenge_pairs<true> leaves for k_challenge_finish (sha256.hip), computed
 // on the host threads for the one-pass commit-and-prove of mid-size batches (engine.hip)
-void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n) {
+void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n, bool be_fields) {
     const Compress compress = best_compress();
     host_parallel_for_grain(n, [=](size_t i) {
         const uint8_t *blob = blobs + (size_t)kBlobBytes * i;
         uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au, 0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
         uint8_t blk[64];
-        memcpy(blk, kChallengeHeader, 32);
+        memcpy(blk, be_fields ? kChallengeHeaderBe : kChallengeHeader, 32);
         memcpy(blk + 32, blob, 32);
         compress(h, blk, 1);
         compress(h, blob + 32, (kBlobBytes - 64) / 64);   // 2047 whole blocks straight from the blob
@@ -469,9 +472,9 @@ void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n) {
 }
 
 // digests[i] = SHA-256(header | blobs[i] | comms[i]) for i < n, spread over the host threads
-void challenge_digests_host(uint8_t *digests32, const uint8_t *blobs, const uint8_t *comms48, size_t n) {
+void challenge_digests_host(uint8_t *digests32, const uint8_t *blobs, const uint8_t *comms48, size_t n, bool be_fields) {
     const int64_t t0 = now_ns();
-    host_parallel_for_grain(n, [=](size_t i) { challenge_digest(digests32 + 32 * i, blobs + (size_t)kBlobBytes * i, comms48 + 48 * i); }, host_hash_grain());
+    host_parallel_for_grain(n, [=](size_t i) { challenge_digest(digests32 + 32 * i, blobs + (size_t)kBlobBytes * i, comms48 + 48 * i, be_fields); }, host_hash_grain());
     const int64_t dt = now_ns() - t0;
     if (n >= 256 && dt > 0) {   // what this host's threads really hash per second (a cgroup quota, SMT siblings and the caller's memory all show here)
         const double rate = (double)n * kBlobBytes / ((double)dt * 1e-9);

@@ -195,7 +195,7 @@ C_KZG_RET lagrange_ensure(Ctx *c) {
 // lwkzg_enable_direct_table); lazily (first c-kzg call of a settings object that follows the process-wide default) only the
 // free-of-charge secondary build is tried. Caller holds the primary context's lock and its twin's; the device is idle.
 static void tables_follow_mode(Ctx *c, int mode, bool may_swap) {
-    const bool want_lag = mode == LWKZG_MODE_CKZG;
+    const bool want_lag = mode_rules(mode).evaluation_form;   // (c-kzg and eth mode alike: moving between the two moves nothing)
     if (want_lag && lagrange_prepare(c) != C_KZG_OK) return;
     const int bits = c->direct_bits ? c->direct_bits : c->lag.direct_bits;
     if (!bits) return;                                     // bucket engine: both forms have their 9 MB tables
@@ -246,7 +246,7 @@ static void tables_follow_mode(Ctx *c, int mode, bool may_swap) {
 // Called by every compute entry point before it takes its context: a settings object answering in c-kzg mode gets the Lagrange form
 // on first use (and a Lagrange direct table if one fits beside the monomial one). One atomic load afterwards.
 void ensure_lagrange(Ctx *c, int mode) {
-    if (mode != LWKZG_MODE_CKZG || c->lag_ready.load(std::memory_order_acquire)) return;
+    if (!mode_rules(mode).evaluation_form || c->lag_ready.load(std::memory_order_acquire)) return;
     c = c->primary;
     std::lock_guard<std::mutex> lk(c->mu);
     std::unique_lock<std::mutex> lk_twin;
@@ -281,7 +281,7 @@ C_KZG_RET enable_direct_table(const KZGSettings *s, int window_bits, size_t row_
         set_error("lwkzg_enable_direct_table_forms: forms must be 1 (monomial), 2 (Lagrange) or 3 (both)");
         return C_KZG_BADARGS;
     }
-    const int mode = forms == 2 || forms == 3 ? LWKZG_MODE_CKZG : forms == 1 ? LWKZG_MODE_REFERENCE : mode_of(s);
+    const bool want_lag = forms == 2 || forms == 3 ? true : forms == 1 ? false : mode_rules(mode_of(s)).evaluation_form;
     std::lock_guard<std::mutex> lk(c->mu);
     // the twin context launches against the same table under its own lock: keep it out as well (lock order: main, twin)
     std::unique_lock<std::mutex> lk_twin;
@@ -300,7 +300,7 @@ C_KZG_RET enable_direct_table(const KZGSettings *s, int window_bits, size_t row_
     const double t_start = wall();
     // the primary form: the one the settings' mode commits over (Lagrange only if it can be had)
     c->lag_failed = false;   // (an explicit request retries a derivation that once ran out of memory)
-    const bool primary_lag = mode == LWKZG_MODE_CKZG && lagrange_prepare(c) == C_KZG_OK;
+    const bool primary_lag = want_lag && lagrange_prepare(c) == C_KZG_OK;
     if (forms >= 2 && !primary_lag) return C_KZG_MALLOC;  // (lagrange_prepare has said why)
     form_drop(c, false);  // (the old and the new tables need not fit side by side)
     form_drop(c, true);

@@ -233,15 +233,14 @@ HXyzz generator_mul(const G1Affine &g, const uint32_t k[8]) {
     return acc;
 }
 
-// field element bytes -> canonical limbs. reference mode: big-endian, reduced; c-kzg mode: little-endian, canonical
+// field element bytes -> canonical limbs. reference mode: big-endian, reduced; c-kzg mode: little-endian, canonical; eth mode:
+// big-endian, canonical (mode_rules.h)
 bool fr_from_bytes(uint32_t raw[8], const uint8_t b[32], int mode) {
+    const ModeRules mr = mode_rules(mode);
     uint32_t t[8];
-    if (mode == LWKZG_MODE_CKZG) {
-        raw_from_le<8>(t, b);
-        if (raw_geq<8>(t, FrParams::MOD)) return false;
-    } else {
-        raw_from_be<8>(t, b);
-    }
+    if (mr.little_endian) raw_from_le<8>(t, b);
+    else raw_from_be<8>(t, b);
+    if (mr.canonical && raw_geq<8>(t, FrParams::MOD)) return false;
     Fr f = fe_from_raw<FrParams>(t);
     fe_to_raw<FrParams>(raw, f);
     return true;
@@ -349,7 +348,7 @@ void host_lincomb3(HXyzz out[3], const G1Affine29 *aff, const int32_t *kind, con
         for (int s = 0; s < 3; s++) out[s] = xyzz_add(out[s], part[3 * t + s]);
 }
 
-C_KZG_RET bad(int mode) { return mode == LWKZG_MODE_CKZG ? C_KZG_BADARGS : C_KZG_ERROR; }
+C_KZG_RET bad(int mode) { return mode_rules(mode).bad; }
 
 }  // namespace
 }  // namespace lwk
@@ -448,7 +447,7 @@ C_KZG_RET verify_blob_kzg_proof(bool *ok, const Blob *blob, const Bytes48 *commi
     }
     side_pi.join();
     if (!pi_ok) { set_error("invalid proof"); return bad(mode); }
-    if (rc != C_KZG_OK) return mode == LWKZG_MODE_REFERENCE ? C_KZG_ERROR : rc;
+    if (rc != C_KZG_OK) return mode_rules(mode).bad == C_KZG_ERROR ? C_KZG_ERROR : rc;
     uint32_t z[8], y[8];
     if (!fr_from_bytes(z, zb, mode) || !fr_from_bytes(y, yb, mode)) return C_KZG_ERROR;
     return verify_core(ok, c, z, y, pi, s);
@@ -524,7 +523,7 @@ C_KZG_RET shard_begin(Shard &sh, const uint8_t *blobs, const uint8_t *comms, con
                 memcpy(m + 112, &canon_p[48 * i], 48);
             }
     }
-    if (rc != C_KZG_OK) return mode == LWKZG_MODE_REFERENCE ? C_KZG_ERROR : rc;
+    if (rc != C_KZG_OK) return mode_rules(mode).bad == C_KZG_ERROR ? C_KZG_ERROR : rc;
     return C_KZG_OK;
 }
 
@@ -550,14 +549,21 @@ void hfr_to_be(uint8_t *out, const HFr &x) {
     raw_to_be<8>(out, t);
 }
 
-// r (utils.rs:166-206) from the n_total records of the whole batch, in Montgomery form
-HFr batch_challenge_mont(const uint8_t *records, size_t n_total, bool le) {
+// r (utils.rs:166-206) from the n_total records of the whole batch, in Montgomery form. The header's two 64-bit fields and the digest's
+// byte order are the mode's (mode_rules.h: eth mode's header is be64(4096) | be64(n), its digest read big-endian)
+HFr batch_challenge_mont(const uint8_t *records, size_t n_total, int mode) {
+    const ModeRules mr = mode_rules(mode);
+    const bool le = mr.little_endian;
     uint8_t head[32];
     memcpy(head, "RCKZGBATCH___V1_", 16);
     memset(head + 16, 0, 16);
-    head[16] = 0x00;
-    head[17] = 0x10;  // 4096 LE
-    for (int k = 0; k < 8; k++) head[24 + k] = (uint8_t)((uint64_t)n_total >> (8 * k));
+    if (mr.be_transcript) {
+        head[22] = 0x10;  // 4096 BE
+        for (int k = 0; k < 8; k++) head[31 - k] = (uint8_t)((uint64_t)n_total >> (8 * k));
+    } else {
+        head[17] = 0x10;  // 4096 LE
+        for (int k = 0; k < 8; k++) head[24 + k] = (uint8_t)((uint64_t)n_total >> (8 * k));
+    }
     uint8_t dg[32];
     sha256_fast_prefixed(dg, head, 32, records, n_total * kRecord);   // (no 160 n-byte copy of the transcript behind its header)
     uint32_t t[8], rraw[8];
@@ -572,7 +578,7 @@ HFr batch_challenge_mont(const uint8_t *records, size_t n_total, bool le) {
 // the scalars are known and before the linear combinations run (the single-process path starts [ysum]G there).
 C_KZG_RET shard_partial(Shard &sh, const uint8_t *records_all, size_t n_total, size_t first, HXyzz out[3], HFr &ysum,
                         const std::function<void(const HFr &)> &beside) {
-    const bool le = sh.mode == LWKZG_MODE_CKZG;
+    const bool le = mode_rules(sh.mode).little_endian;
     const size_t n = sh.n;
     for (int k = 0; k < 3; k++) out[k] = HXyzz::infinity();
     ysum = HFr::zero();
@@ -584,7 +590,7 @@ C_KZG_RET shard_partial(Shard &sh, const uint8_t *records_all, size_t n_total, s
         set_error("verify shard: the transcript at index %zu is not this shard's first record", first);
         return C_KZG_BADARGS;
     }
-    const HFr r_mont = batch_challenge_mont(records_all, n_total, le);
+    const HFr r_mont = batch_challenge_mont(records_all, n_total, sh.mode);
     // scalars r^i, r^i z_i (for the GPU) and sum r^i y_i (one host scalar), on the 64-bit host field. The running power
     // stays in Montgomery form; a Montgomery product with a RAW factor (z_i, y_i, 1) yields the raw product directly.
     const uint32_t one_limbs[8] = {1, 0, 0, 0, 0, 0, 0, 0};
@@ -703,8 +709,8 @@ bool point_from_bytes(HXyzz &p, const uint8_t *in97) {
 //
 // step 1: r over the transcript, canonical big-endian as lwkzg_batch_challenge_host writes it, and the table launch_vmsm_scalars and
 // launch_verify_ysum take for a batch that starts at r^0
-void verify_async_challenge(uint8_t r_be[32], Fr pw33[33], const uint8_t *records, size_t n, bool le) {
-    const HFr r_mont = batch_challenge_mont(records, n, le);
+void verify_async_challenge(uint8_t r_be[32], Fr pw33[33], const uint8_t *records, size_t n, int mode) {
+    const HFr r_mont = batch_challenge_mont(records, n, mode);
     const uint32_t one_limbs[8] = {1, 0, 0, 0, 0, 0, 0, 0};
     hfr_to_be(r_be, r_mont * hfr_raw(one_limbs));
     HFr sq = r_mont;
@@ -761,7 +767,7 @@ C_KZG_RET verify_batch_device_full(bool *ok, uint8_t r_be[32], uint8_t *partial,
     C_KZG_RET rc = shard_begin(sh, d_blobs, d_comm, d_proofs, n, s, mode, false, true, caller);
     if (rc != C_KZG_OK) return rc;
     Fr pw[33];   // (the challenge's bytes by step 1's own body; its table is not needed here)
-    verify_async_challenge(r_be, pw, sh.records.data(), n, mode == LWKZG_MODE_CKZG);
+    verify_async_challenge(r_be, pw, sh.records.data(), n, mode);
     HXyzz sums[3];
     HFr ysum;
     if (shard_partial(sh, sh.records.data(), n, 0, sums, ysum, nullptr) != C_KZG_OK) return C_KZG_ERROR;
@@ -845,7 +851,7 @@ static C_KZG_RET verify_batch_impl(bool *ok, const Blob *blobs, const Bytes48 *c
     if (n == 0) {
         // the reference answers OK with ok = false (lib.rs:538-543); c-kzg-4844 accepts the empty batch
         // (verify_blob_kzg_proof_batch_case_a271b78b8e869d69: output true) -- SURVEY Appendix B: a reference quirk, never in mode C
-        *ok = mode == LWKZG_MODE_CKZG;
+        *ok = mode_rules(mode).empty_ok;
         return C_KZG_OK;
     }
     if (n == 1 && !device_inputs) return verify_blob_kzg_proof(ok, blobs, commitments_bytes, proofs_bytes, s);  // lib.rs:544
@@ -971,7 +977,7 @@ C_KZG_RET lwkzg_verify_shards_finish(bool *ok, const uint8_t *partials, size_t n
     if (!ok) return C_KZG_BADARGS;
     *ok = false;
     if (n_total == 0) {  // lib.rs:538-543: the empty batch is OK with ok = false; c-kzg-4844 (mode C) accepts it
-        *ok = mode_of(s) == LWKZG_MODE_CKZG;
+        *ok = mode_rules(mode_of(s)).empty_ok;
         return C_KZG_OK;
     }
     if (!partials || !n_shards || !s) return C_KZG_BADARGS;
@@ -1025,12 +1031,17 @@ C_KZG_RET lwkzg_challenge_digests_host(uint8_t *digests32, const uint8_t *blobs,
     challenge_digests_host(digests32, blobs, commitments48, n);
     return C_KZG_OK;
 }
+C_KZG_RET lwkzg_challenge_digests_host_mode(uint8_t *digests32, const uint8_t *blobs, const uint8_t *commitments48, size_t n, int mode) {
+    if (!mode_known(mode) || (n && (!digests32 || !blobs || !commitments48))) return C_KZG_BADARGS;
+    challenge_digests_host(digests32, blobs, commitments48, n, mode_rules(mode).be_transcript);
+    return C_KZG_OK;
+}
 
 // the batch challenge r over a transcript of records, canonical big-endian (host only)
 C_KZG_RET lwkzg_batch_challenge_host(uint8_t r_out[32], const uint8_t *records_all, size_t n_total, int mode) {
-    if (!r_out || (!records_all && n_total) || (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG)) return C_KZG_BADARGS;
+    if (!r_out || (!records_all && n_total) || !mode_known(mode)) return C_KZG_BADARGS;
     const uint32_t one_limbs[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-    hfr_to_be(r_out, batch_challenge_mont(records_all, n_total, mode == LWKZG_MODE_CKZG) * hfr_raw(one_limbs));
+    hfr_to_be(r_out, batch_challenge_mont(records_all, n_total, mode) * hfr_raw(one_limbs));
     return C_KZG_OK;
 }
 

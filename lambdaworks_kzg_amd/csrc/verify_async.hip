@@ -83,7 +83,7 @@ void verifier_host_fn1(void *p) {
         memcpy(&j->first_bad, v->vb.h_rec + LWKZG_VERIFY_RECORD_BYTES * j->n, 4);
         if (j->first_bad == kNoneBad) {
             Fr pw[33];
-            verify_async_challenge(((LwkzgVerifyResult *)j->res)->r, pw, v->vb.h_rec, j->n, j->mode == LWKZG_MODE_CKZG);
+            verify_async_challenge(((LwkzgVerifyResult *)j->res)->r, pw, v->vb.h_rec, j->n, j->mode);
             memcpy(v->vb.h_pin, pw, sizeof pw);
             skip = 0;
         } else if (j->first_bad < j->n) {
@@ -108,7 +108,7 @@ void verifier_host_fn2(void *p) {
         if (j->failed) {
             rc = C_KZG_ERROR;
         } else if (j->first_bad != kNoneBad) {   // as verify_prepare_device and shard_begin answer a rejected input
-            rc = j->mode == LWKZG_MODE_REFERENCE || j->code != kStatusBadArgs ? C_KZG_ERROR : C_KZG_BADARGS;
+            rc = mode_rules(j->mode).bad == C_KZG_ERROR || j->code != kStatusBadArgs ? C_KZG_ERROR : C_KZG_BADARGS;
         } else {
             const uint8_t *pin = v->vb.h_pin;
             uint8_t sums[3][96];
@@ -181,7 +181,7 @@ C_KZG_RET enqueue_on(Verifier *v, Ctx *c, AsyncJob *j, const uint8_t *blobs, con
     LWK_HIP(hipSetDevice(c->device));
     VerifyBuffers &vb = v->vb;
     const size_t n = j->n;
-    const int le = j->mode == LWKZG_MODE_CKZG;
+    const int le = mode_rules(j->mode).le();
     hipStream_t st = c->stream, sy = c->aux[1];
     uint32_t *d_skip = (uint32_t *)(vb.vm_pw + kVmsmPwSkip);
     uint8_t *d_ysum = (uint8_t *)(vb.vm_pw + kVmsmPwYsum);
@@ -223,7 +223,7 @@ C_KZG_RET verifier_enqueue_impl(const LwkzgVerifier *handle, LwkzgVerifyResult *
     Verifier *v = static_cast<Verifier *>(base);
     const int mode = mode_of(v->s);
     if (n == 0) {   // the reference answers OK with ok = false, c-kzg-4844 accepts the empty batch (verify.hip: verify_batch_impl)
-        complete_now(res, C_KZG_OK, mode == LWKZG_MODE_CKZG);
+        complete_now(res, C_KZG_OK, mode_rules(mode).empty_ok);
         return C_KZG_OK;
     }
     if (!blobs || !comm || !proofs) return async_refuse(res, C_KZG_BADARGS);
@@ -268,9 +268,9 @@ C_KZG_RET lwkzg_verifier_host_steps(LwkzgVerifyResult *out, const uint8_t *recor
     if (!out) return C_KZG_BADARGS;
     memset(out, 0, sizeof *out);
     out->first_bad = first_bad;
-    if (mode != LWKZG_MODE_REFERENCE && mode != LWKZG_MODE_CKZG) return async_refuse(out, C_KZG_BADARGS);
+    if (!mode_known(mode)) return async_refuse(out, C_KZG_BADARGS);
     if (first_bad != kNoneBad) {   // a rejected input: the mode's code, and nothing else is read
-        complete_now(out, mode == LWKZG_MODE_REFERENCE ? C_KZG_ERROR : C_KZG_BADARGS, false);
+        complete_now(out, mode_rules(mode).bad, false);
         return C_KZG_OK;
     }
     if ((!records && n) || !sums3x97 || !ysum32 || !s) return async_refuse(out, C_KZG_BADARGS);
@@ -278,7 +278,7 @@ C_KZG_RET lwkzg_verifier_host_steps(LwkzgVerifyResult *out, const uint8_t *recor
     bool ok = false;
     try {
         Fr pw[33];
-        verify_async_challenge(out->r, pw, records, n, mode == LWKZG_MODE_CKZG);
+        verify_async_challenge(out->r, pw, records, n, mode);
         uint8_t sums[3][96];
         int infs[3];
         rc = sums_from_97(sums, infs, sums3x97) ? verify_async_verdict(&ok, out->partial, sums, infs, ysum32, s) : C_KZG_BADARGS;

@@ -26,31 +26,32 @@ static_assert(sizeof(PairingLine) == 2 * sizeof(Fp2), "pairing_line_table_host w
 
 namespace {
 
-// 32 bytes of a scalar in the mode's byte order -> raw limbs; false if not below r
-__device__ __forceinline__ bool each_scalar(uint32_t raw[8], const uint8_t *b, int le) {
-    if (le) raw_from_le<8>(raw, b);
+// 32 bytes of a scalar in the given byte order -> raw limbs; false if not below r (reduced or rejected: the caller's)
+__device__ __forceinline__ bool each_scalar(uint32_t raw[8], const uint8_t *b, bool little_endian) {
+    if (little_endian) raw_from_le<8>(raw, b);
     else raw_from_be<8>(raw, b);
     return !raw_geq<8>(raw, FrParams::MOD);
 }
 
 __global__ void k_each_openings(const uint8_t *z_in, const uint8_t *y_in, uint8_t *z_out, uint8_t *y_out, int32_t *status, int bad_code,
-                                int le, size_t n) {
+                                int scalar_rule, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const bool little = scalar_rule == kScalarLeCanonical, canonical = scalar_rule != kScalarBeReduced;   // (mode_rules.h)
     bool ok = true;
     for (int k = 0; k < 2; k++) {
         const uint8_t *in = (k ? y_in : z_in) + 32 * i;
         uint8_t *out = (k ? y_out : z_out) + 32 * i;
         uint32_t raw[8];
-        if (!each_scalar(raw, in, le)) {
-            if (le) {  // c-kzg: a non-canonical element is rejected (verify.hip: fr_from_bytes)
+        if (!each_scalar(raw, in, little)) {
+            if (canonical) {  // c-kzg and eth: a non-canonical element is rejected (verify.hip: fr_from_bytes)
                 ok = false;
                 continue;
             }
             Fr f = fe_from_raw<FrParams>(raw);  // reference: reduced
             fe_to_raw<FrParams>(raw, f);
         }
-        if (le) raw_to_le<8>(out, raw);
+        if (little) raw_to_le<8>(out, raw);
         else raw_to_be<8>(out, raw);
     }
     if (!ok) status[i] = bad_code;
@@ -66,8 +67,8 @@ __global__ void k_each_combine(const G1Affine29 *pts_c, const int32_t *kind_c, c
         return;
     }
     uint32_t z[8], y[8];
-    each_scalar(z, z32 + 32 * i, le);  // (canonical: the front wrote them)
-    each_scalar(y, y32 + 32 * i, le);
+    each_scalar(z, z32 + 32 * i, le != 0);  // (canonical: the front wrote them)
+    each_scalar(y, y32 + 32 * i, le != 0);
     const bool has_c = kind_c[i] == 0, has_pi = kind_p[i] == 0;
     Fp pix = Fp::zero(), piy = Fp::zero();
     if (has_pi) {
@@ -197,7 +198,7 @@ C_KZG_RET verify_each_device(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const K
         g1_beta_raw(braw);
         const Fp beta = fe_from_raw<FpParams>(braw);
         k_each_combine<<<each_blocks(n), kEachBlock, 0, st>>>(vb.pts_c, vb.kind_c, vb.pts_p, vb.kind_p, vb.status_all, vb.d_rz, vb.d_r,
-                                                             mode == LWKZG_MODE_CKZG, g, beta, pts, n);
+                                                             mode_rules(mode).le(), g, beta, pts, n);
         LWK_HIP(hipGetLastError());
         launch_each_pairing(pts, lines, d_ok, n, st);
         LWK_HIP(hipGetLastError());
@@ -209,7 +210,7 @@ C_KZG_RET verify_each_device(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const K
     // reference mode
     for (size_t i = 0; i < n; i++) {
         if (status[i] != 0) {
-            rc_out[i] = mode == LWKZG_MODE_REFERENCE ? C_KZG_ERROR : status[i];
+            rc_out[i] = mode_rules(mode).bad == C_KZG_ERROR ? C_KZG_ERROR : status[i];
             ok_out[i] = 0;
         } else if (!setup_ok) {
             rc_out[i] = C_KZG_ERROR;
@@ -252,9 +253,9 @@ C_KZG_RET verify_each_host(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const KZG
 
 }  // namespace
 
-void launch_each_openings(const uint8_t *z_in, const uint8_t *y_in, uint8_t *z_out, uint8_t *y_out, int32_t *status, int bad_code, int le,
-                          size_t n, hipStream_t st) {
-    k_each_openings<<<each_blocks(n), kEachBlock, 0, st>>>(z_in, y_in, z_out, y_out, status, bad_code, le, n);
+void launch_each_openings(const uint8_t *z_in, const uint8_t *y_in, uint8_t *z_out, uint8_t *y_out, int32_t *status, int bad_code,
+                          int scalar_rule, size_t n, hipStream_t st) {
+    k_each_openings<<<each_blocks(n), kEachBlock, 0, st>>>(z_in, y_in, z_out, y_out, status, bad_code, scalar_rule, n);
 }
 
 }  // namespace lwk

@@ -173,15 +173,16 @@ static C_KZG_RET verify_buffers_take(Ctx *c, VerifyBuffers &vb, size_t n) {
 static C_KZG_RET verify_prepare_staged(Ctx *c, const uint8_t *blobs, const uint8_t *comm48, const uint8_t *proofs48, size_t n, int mode,
                                        uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p, VerifyBuffers &vb, bool &taken) {
     taken = false;
-    const int le = mode == LWKZG_MODE_CKZG;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le(), fs = mr.hash_rule();   // the byte order of digests and outputs; what the hash kernels are told
     const bool evf = proof_in_evaluation_form(c, mode);
-    if (!knobs().host_stage || !(mode == LWKZG_MODE_REFERENCE || evf) || n > ((size_t)1 << 17)) return C_KZG_OK;
+    if (!knobs().host_stage || !(!mr.evaluation_form || evf) || n > ((size_t)1 << 17)) return C_KZG_OK;
     if (grow_reserve(c->vblobs, n, 2 * kMaxChunk, [](size_t cap) { return cap * (size_t)kBlobBytes; }, nullptr) != C_KZG_OK) return C_KZG_OK;
     uint8_t *d_all = c->vblobs.dev;
     C_KZG_RET rc = ws_long_reserve(c, n);
     if (rc != C_KZG_OK) return rc;
     taken = true;
-    const int bad = le ? kStatusBadArgs : kStatusError;
+    const int bad = mr.bad_status();
     // Four streams are at work at once here, and the runtime multiplexes a process's streams onto four hardware queues: a copy that shares
     // its queue with the validation kernels or with a 3.1 ms hash launch simply waits for them (uploads on aux[3]: 15.9 instead of 13.1 ms;
     // which side streams collide depends on what else the process has created). The uploads therefore get a HIGH-PRIORITY stream of their
@@ -197,7 +198,7 @@ static C_KZG_RET verify_prepare_staged(Ctx *c, const uint8_t *blobs, const uint8
                 n, n_gpu, every, slice, n_host, host_hash_rate() * 1e-9);
     std::vector<uint8_t> dig(32 * (n_host ? n_host : 1));
     SideTask hasher;   // joined by its destructor on every exit (digests assume canonical commitment bytes; the comparison below confirms or refutes that)
-    if (n_host) hasher.start([&, n_gpu, n_host]() { challenge_digests_host(dig.data(), blobs + n_gpu * (size_t)kBlobBytes, comm48 + 48 * n_gpu, n_host); });
+    if (n_host) hasher.start([&, n_gpu, n_host]() { challenge_digests_host(dig.data(), blobs + n_gpu * (size_t)kBlobBytes, comm48 + 48 * n_gpu, n_host, mr.be_transcript); });
     // up-front validation of every commitment (main stream) and every proof (validation stream), the rows of the linear combinations behind them
     LWK_HIP(hipMemcpyAsync(vb.comm_in, comm48, n * 48, hipMemcpyHostToDevice, st));
     LWK_HIP(hipMemsetAsync(vb.status_all, 0, n * 4, st));
@@ -223,7 +224,7 @@ static C_KZG_RET verify_prepare_staged(Ctx *c, const uint8_t *blobs, const uint8
                 const size_t lo = hashed * slice, cnt = (landed - hashed) * slice;
                 LWK_HIP(hipEventRecord(c->ev_join[3], sc));
                 LWK_HIP(hipStreamWaitEvent(sh, c->ev_join[3], 0));
-                launch_challenge(d_all + lo * (size_t)kBlobBytes, vb.comm_in + 48 * lo, z + lo, le, cnt, sh);
+                launch_challenge(d_all + lo * (size_t)kBlobBytes, vb.comm_in + 48 * lo, z + lo, fs, cnt, sh);
                 hashed = landed;
             }
         }
@@ -238,17 +239,17 @@ static C_KZG_RET verify_prepare_staged(Ctx *c, const uint8_t *blobs, const uint8
     LWK_HIP(hipStreamWaitEvent(sh, c->ev_join[kMaxSplit - 2], 0));
     hasher.join();
     // the head: redo the challenges of blobs whose commitment bytes were not canonical (exits at once otherwise)
-    if (n_gpu) launch_challenge(d_all, vb.canon_dev, z, le, n_gpu, sh, vb.comm_in);
+    if (n_gpu) launch_challenge(d_all, vb.canon_dev, z, fs, n_gpu, sh, vb.comm_in);
     // the tail: the host's digests, unless a commitment among them was not in its canonical encoding
     if (n_host) {
         if (memcmp(canon_c + 48 * n_gpu, comm48 + 48 * n_gpu, 48 * n_host) == 0) {
             LWK_HIP(hipMemcpyAsync(vb.d_rz + 32 * n_gpu, dig.data(), 32 * n_host, hipMemcpyHostToDevice, sh));
             launch_z_from_bytes(vb.d_rz + 32 * n_gpu, z + n_gpu, nullptr, le, n_host, sh);
         } else {
-            launch_challenge(d_all + n_gpu * (size_t)kBlobBytes, vb.canon_dev + 48 * n_gpu, z + n_gpu, le, n_host, sh);
+            launch_challenge(d_all + n_gpu * (size_t)kBlobBytes, vb.canon_dev + 48 * n_gpu, z + n_gpu, fs, n_host, sh);
         }
     }
-    if (evf) launch_eval_y_from_blobs_evalform(d_all, z, c->tw28_fwd + kBlobElems / 2, vb.d_r, vb.status_all, n, sh);
+    if (evf) launch_eval_y_from_blobs_evalform(d_all, z, c->tw28_fwd + kBlobElems / 2, vb.d_r, vb.status_all, n, sh, le);
     else launch_eval_y_from_blobs_be(d_all, z, vb.d_r, n, sh);
     launch_fr_mont_to_bytes(z, vb.d_rz, le, n, sh);
     LWK_HIP(hipEventRecord(c->ev_join[3], sh));
@@ -266,8 +267,9 @@ static C_KZG_RET verify_prepare_staged(Ctx *c, const uint8_t *blobs, const uint8
 static C_KZG_RET verify_prepare_long(Ctx *c, const uint8_t *blobs, const uint8_t *comm48, const uint8_t *proofs48, size_t n,
                                      int mode, uint8_t *z32, uint8_t *y32, uint8_t *canon_c, uint8_t *canon_p,
                                      VerifyBuffers &vb) {
-    const int le = mode == LWKZG_MODE_CKZG;
-    const int bad = le ? kStatusBadArgs : kStatusError;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le(), fs = mr.hash_rule();   // the byte order of digests and outputs; what the hash kernels are told
+    const int bad = mr.bad_status();
     hipStream_t st = c->stream, sv = c->vstream;
     const bool piped = n >= kMaxChunk;
     const size_t step = piped ? kMaxChunk / 2 : n;
@@ -320,7 +322,8 @@ static C_KZG_RET verify_prepare_long(Ctx *c, const uint8_t *blobs, const uint8_t
         s.dig.resize(32 * m);
         Slot *sp = &s;  // digests assume the caller's commitment bytes are canonical; finish() confirms or refutes that
         uint8_t *d_blobs = w.blobs + s.base * (size_t)kBlobBytes;
-        s.hasher.start([sp]() { challenge_digests_host(sp->dig.data(), sp->hb, sp->hc, sp->m); });
+        const bool be_fields = mr.be_transcript;
+        s.hasher.start([sp, be_fields]() { challenge_digests_host(sp->dig.data(), sp->hb, sp->hc, sp->m, be_fields); });
         LWK_HIP(hipMemcpyAsync(d_blobs, s.hb, m * (size_t)kBlobBytes, hipMemcpyHostToDevice, s.sk));
         // (the parser's verdicts go beside the validation's, as in the device-resident form: both only ever write failure codes)
         coefficients_stage(c, d_blobs, m, mode, vb.status_all + off, s.sk, s.base);
@@ -343,7 +346,7 @@ static C_KZG_RET verify_prepare_long(Ctx *c, const uint8_t *blobs, const uint8_t
             LWK_HIP(hipMemcpyAsync(d_zb, s.dig.data(), m * 32, hipMemcpyHostToDevice, sk));
             launch_z_from_bytes(d_zb, d_z, nullptr, le, m, sk);
         } else {  // a non-canonical (or invalid) encoding in this slice: hash the canonical bytes on the GPU
-            launch_challenge(w.blobs + base * (size_t)kBlobBytes, vb.canon_dev + 48 * off, d_z, le, m, sk);
+            launch_challenge(w.blobs + base * (size_t)kBlobBytes, vb.canon_dev + 48 * off, d_z, fs, m, sk);
         }
         quotient_stage(c, mode, w.scalars + base * (size_t)kBlobElems * 8, d_z, nullptr /* y only */, d_yb, le, m,
                              sk);
@@ -396,8 +399,9 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
     if (!vb.owned) vb.hold = std::unique_lock<std::mutex>(c->verify_mu);
     std::lock_guard<std::mutex> lk(c->mu);
     LWK_HIP(hipSetDevice(c->device));
-    const int le = mode == LWKZG_MODE_CKZG;
-    const int bad = le ? kStatusBadArgs : kStatusError;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le(), fs = mr.hash_rule();   // the byte order of digests and outputs; what the hash kernels are told
+    const int bad = mr.bad_status();
     hipStream_t st = c->stream;
     WsUse wsu(c, st);
     // No exit of this function may leave a validation / multiples kernel running on the side streams against scratch
@@ -438,7 +442,7 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
         const uint8_t *hash_comm = trusted_canon_c ? trusted_canon_c + 48 * off : hc;
         const bool hash_beside = m > 64;  // a few blobs: hashing takes microseconds, a thread and its contention do not pay
         SideTask hasher;  // joined by its destructor on every exit
-        if (hash_beside) hasher.start([&, hash_comm]() { challenge_digests_host(dig.data(), hb, hash_comm, m); });
+        if (hash_beside) hasher.start([&, hash_comm]() { challenge_digests_host(dig.data(), hb, hash_comm, m, mr.be_transcript); });
         LWK_HIP(hipMemcpyAsync(w.comm48, hc, m * 48, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemsetAsync(w.status, 0, m * 4, st));
         // up to 64 blobs: both point sets are validated on the host threads (0.2 ms per point per thread against a 2 ms
@@ -503,7 +507,7 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
             LWK_HIP(hipStreamWaitEvent(st, c->ev_join[1], 0));
         }
         if (hash_beside) hasher.join();
-        else challenge_digests_host(dig.data(), hb, hash_comm, m);
+        else challenge_digests_host(dig.data(), hb, hash_comm, m, mr.be_transcript);
         // device-to-host copies into pageable memory block this thread until the stream has reached them, so the
         // canonical bytes are fetched only after every launch above has been submitted
         if (!trusted_canon_c && !host_validate)
@@ -515,7 +519,7 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
             launch_z_from_bytes(w.zbytes, w.z, nullptr, le, m, st);
         } else {
             if (host_validate) LWK_HIP(hipMemcpyAsync(w.canon48, canon_c + 48 * off, m * 48, hipMemcpyHostToDevice, st));
-            launch_challenge(w.blobs, w.canon48, w.z, le, m, st);
+            launch_challenge(w.blobs, w.canon48, w.z, fs, m, st);
         }
         quotient_stage(c, mode, w.scalars, w.z, nullptr /* a verification wants y = p(z) only */, w.ybytes, le, m, st);
         launch_fr_mont_to_bytes(w.z, w.zbytes, le, m, st);
@@ -546,8 +550,9 @@ C_KZG_RET verify_prepare_host(Ctx *c, const uint8_t *blobs, const uint8_t *comm4
 C_KZG_RET verify_front_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_comm, const uint8_t *d_proofs, size_t n, int mode,
                               VerifyBuffers &vb, hipStream_t caller, bool want_records, bool keep, bool *recorded) {
     *recorded = false;
-    const int le = mode == LWKZG_MODE_CKZG;
-    const int bad = le ? kStatusBadArgs : kStatusError;
+    const ModeRules mr = mode_rules(mode);
+    const int le = mr.le(), fs = mr.hash_rule();   // the byte order of digests and outputs; what the hash kernels are told
+    const int bad = mr.bad_status();
     hipStream_t st = c->stream, sv = c->vstream, sc = c->aux[0];
     if (caller && caller != st) {  // the inputs are whatever the caller's stream has produced by now
         LWK_HIP(hipEventRecord(c->ev_join[3], caller));
@@ -586,7 +591,7 @@ C_KZG_RET verify_front_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_c
     // they would take the whole chip and the hash would wait for them (8192 blobs: the hash 7.6 ms behind 256 exclusive decompression
     // workgroups; profiles/r06_experiments.md section 3). LWKZG_VERIFY_ORDER=1 (experiment) is the other order.
     const bool hash_first = fused ? (apart != (knobs().verify_order != 0)) : knobs().verify_order != 0;
-    if (hash_first) launch_challenge(d_blobs, d_comm, z, le, n, st);
+    if (hash_first) launch_challenge(d_blobs, d_comm, z, fs, n, st);
     if (fused) {   // r06: ONE launch per kernel over both point sets; the rows start as soon as the points are decompressed
         const PointSet set_p{d_proofs, vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p}, set_c{d_comm, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c};
         launch_decompress_points(set_p, &set_c, n, sv, apart);
@@ -612,18 +617,18 @@ C_KZG_RET verify_front_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_c
         LWK_HIP(hipStreamWaitEvent(st, c->ev_join[0], 0));
         LWK_HIP(hipStreamWaitEvent(st, c->ev_join[1], 0));
     }
-    if (!hash_first) launch_challenge(d_blobs, d_comm, z, le, n, st);
+    if (!hash_first) launch_challenge(d_blobs, d_comm, z, fs, n, st);
     LWK_HIP(hipStreamWaitEvent(st, c->ev_join[0], 0));
     LWK_HIP(hipStreamWaitEvent(st, c->ev_join[1], 0));
     drain.armed = false;  // both side streams are joined into the main stream from here on
-    launch_challenge(d_blobs, vb.canon_dev, z, le, n, st, d_comm);  // only the blobs whose commitment bytes were not canonical
+    launch_challenge(d_blobs, vb.canon_dev, z, fs, n, st, d_comm);  // only the blobs whose commitment bytes were not canonical
     // chunk by chunk with no host round trip in between: y and z bytes of ALL blobs collect in the linear combinations' scalar
     // buffers (idle until lincomb3), the parser's verdicts beside the validation's
-    if (mode == LWKZG_MODE_REFERENCE) {   // the blobs are already on the device and a reference-mode parse cannot fail: one launch reads them as they are
+    if (!mr.evaluation_form) {   // the blobs are already on the device and a reference-mode parse cannot fail: one launch reads them as they are
         launch_eval_y_from_blobs_be(d_blobs, z, vb.d_r, n, st);
         launch_fr_mont_to_bytes(z, vb.d_rz, le, n, st);
     } else if (proof_in_evaluation_form(c, mode)) {   // c-kzg on the Lagrange form: the blob's elements ARE the evaluations; range check in the same launch
-        launch_eval_y_from_blobs_evalform(d_blobs, z, c->tw28_fwd + kBlobElems / 2, vb.d_r, vb.status_all, n, st);
+        launch_eval_y_from_blobs_evalform(d_blobs, z, c->tw28_fwd + kBlobElems / 2, vb.d_r, vb.status_all, n, st, le);
         launch_fr_mont_to_bytes(z, vb.d_rz, le, n, st);
     } else {
         for (size_t off = 0; off < n; off += kMaxChunk) {
@@ -681,8 +686,8 @@ C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const ui
     vb.hold = std::unique_lock<std::mutex>(c->verify_mu);
     std::lock_guard<std::mutex> lk(c->mu);
     LWK_HIP(hipSetDevice(c->device));
-    const int le = mode == LWKZG_MODE_CKZG;
-    const int bad = le ? kStatusBadArgs : kStatusError;
+    const ModeRules mr = mode_rules(mode);
+    const int bad = mr.bad_status();
     hipStream_t st = c->stream;
     WsUse wsu(c, st);
     C_KZG_RET rc = vs_reserve(c, n);
@@ -692,7 +697,7 @@ C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const ui
     const PointSet set_p{d_proofs, vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p}, set_c{d_comm, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c};
     launch_decompress_points(set_p, &set_c, n, st);
     launch_subgroup_canon(set_p, &set_c, vb.status_all, bad, n, st);
-    launch_each_openings(d_z, d_y, vb.d_rz, vb.d_r, vb.status_all, bad, le, n, st);
+    launch_each_openings(d_z, d_y, vb.d_rz, vb.d_r, vb.status_all, bad, mr.scalar_rule(), n, st);
     LWK_HIP(hipGetLastError());
     return C_KZG_OK;
 }

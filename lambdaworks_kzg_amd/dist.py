@@ -113,9 +113,10 @@ def _all_gather_bytes(local, counts, item_bytes, device, group=None):
 
 def _empty_batch_verdict(ts):
     """n == 0: False in reference mode (/root/reference/src/lib.rs:538-543), True in c-kzg mode (the reference's own
-    vector verify_blob_kzg_proof_batch_case_a271b78b8e869d69)."""
+    vector verify_blob_kzg_proof_batch_case_a271b78b8e869d69) and in eth mode (the consensus specs' rule). The shards themselves
+    answer in the settings' mode: records, challenge and sums follow it inside the library."""
     mode = ts.get_mode() if ts is not None else capi.get_mode()
-    return mode == capi.MODE_CKZG
+    return mode in (capi.MODE_CKZG, capi.MODE_ETH)
 
 
 def verify_blob_kzg_proof_batch_sharded(blobs, commitments, proofs, n_local, ts, group=None, _shard=None, _finish=None):
