@@ -1,10 +1,29 @@
 // device_api.hip -- the device-resident C ABI: the reserve calls and every lwkzg_*_device compute entry point (device pointers in and out,
 // asynchronous on the caller's stream).
+#include "abi_guard.h"
 #include "async_verifier.h"
 
 #include <string.h>
 
 using namespace lwk;
+
+// The entry points whose call may run on the settings' second context (pick_ctx): the settings' context and mode, the Lagrange form
+// where the mode wants it, the context for this caller stream -- locked, its device selected, the workspace taken on the call's stream
+// (the caller's, or the context's own) -- and body(Ctx *, int mode, hipStream_t) inside the ABI's guard: the proof pipelines size host
+// vectors by their arguments.
+template <class F>
+static C_KZG_RET on_picked_ctx(const char *what, const KZGSettings *s, void *stream, F &&body) {
+    Ctx *c = ctx_of(s);
+    if (!c) return C_KZG_ERROR;
+    const int mode = mode_of(s);
+    ensure_lagrange(c, mode);
+    c = pick_ctx(c, (hipStream_t)stream);
+    std::lock_guard<std::mutex> lk(c->mu);
+    LWK_HIP(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    WsUse wsu(c, st);
+    return guarded(what, [&] { return body(c, mode, st); });
+}
 
 extern "C" {
 
@@ -72,48 +91,27 @@ C_KZG_RET lwkzg_reserve_streams(const KZGSettings *s, size_t max_batch, int call
 
 C_KZG_RET lwkzg_blob_to_kzg_commitment_batch_device(void *out48_dev, const void *blobs_dev, size_t n, const KZGSettings *s,
                                                     void *stream, int32_t *status_dev) {
-    Ctx *c = ctx_of(s);
-    if (!c) return C_KZG_ERROR;
-    const int mode = mode_of(s);
-    ensure_lagrange(c, mode);
-    c = pick_ctx(c, (hipStream_t)stream);
-    std::lock_guard<std::mutex> lk(c->mu);
-    LWK_HIP(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    WsUse wsu(c, st);
-    return commit_batch_device(c, (uint8_t *)out48_dev, (const uint8_t *)blobs_dev, n, mode, st, status_dev);
+    return on_picked_ctx("lwkzg_blob_to_kzg_commitment_batch_device", s, stream, [&](Ctx *c, int mode, hipStream_t st) {
+        return commit_batch_device(c, (uint8_t *)out48_dev, (const uint8_t *)blobs_dev, n, mode, st, status_dev);
+    });
 }
 
 C_KZG_RET lwkzg_compute_blob_kzg_proof_batch_device(void *out48_dev, const void *blobs_dev, const void *commitments48_dev,
                                                     size_t n, const KZGSettings *s, void *stream, int32_t *status_dev) {
-    Ctx *c = ctx_of(s);
-    if (!c) return C_KZG_ERROR;
-    const int mode = mode_of(s);
-    ensure_lagrange(c, mode);
-    c = pick_ctx(c, (hipStream_t)stream);
-    std::lock_guard<std::mutex> lk(c->mu);
-    LWK_HIP(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    WsUse wsu(c, st);
-    return blob_proof_batch_device(c, (uint8_t *)out48_dev, (const uint8_t *)blobs_dev, (const uint8_t *)commitments48_dev,
-                                   n, mode, st, status_dev);
+    return on_picked_ctx("lwkzg_compute_blob_kzg_proof_batch_device", s, stream, [&](Ctx *c, int mode, hipStream_t st) {
+        return blob_proof_batch_device(c, (uint8_t *)out48_dev, (const uint8_t *)blobs_dev, (const uint8_t *)commitments48_dev,
+                                       n, mode, st, status_dev);
+    });
 }
 
 C_KZG_RET lwkzg_commit_and_prove_batch_device(void *commitments48_dev, void *proofs48_dev, const void *blobs_dev, size_t n,
                                               const KZGSettings *s, void *stream, int32_t *status_dev) {
     if (!commitments48_dev || !proofs48_dev || !blobs_dev) return map_rc(C_KZG_BADARGS, mode_of(s));
-    Ctx *c = ctx_of(s);
-    if (!c) return C_KZG_ERROR;
-    if (n == 0) return C_KZG_OK;
-    const int mode = mode_of(s);
-    ensure_lagrange(c, mode);
-    c = pick_ctx(c, (hipStream_t)stream);
-    std::lock_guard<std::mutex> lk(c->mu);
-    LWK_HIP(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    WsUse wsu(c, st);
-    return commit_and_prove_batch_device(c, (uint8_t *)commitments48_dev, (uint8_t *)proofs48_dev, (const uint8_t *)blobs_dev, n,
-                                         mode, st, status_dev);
+    if (n == 0) return ctx_of(s) ? C_KZG_OK : C_KZG_ERROR;   // (settings that are no settings fail an empty call too)
+    return on_picked_ctx("lwkzg_commit_and_prove_batch_device", s, stream, [&](Ctx *c, int mode, hipStream_t st) {
+        return commit_and_prove_batch_device(c, (uint8_t *)commitments48_dev, (uint8_t *)proofs48_dev, (const uint8_t *)blobs_dev, n,
+                                             mode, st, status_dev);
+    });
 }
 
 // z_i = compute_challenge(blob_i, commitment_i) (src/utils.rs:120-154) for device-resident blobs, as 32 bytes in the
@@ -131,10 +129,11 @@ C_KZG_RET lwkzg_compute_challenges_device(void *z32_dev, const void *blobs_dev, 
     WsUse wsu(c, st);
     C_KZG_RET rc = ctx_reserve(c, n);
     if (rc != C_KZG_OK) return rc;
-    if (n > kMaxChunk && (rc = ws_long_reserve(c, n)) != C_KZG_OK) return rc;
+    CallWords cw;
+    if ((rc = call_words(c, n, nullptr, cw)) != C_KZG_OK) return rc;
     const ModeRules mr = mode_rules(mode_of(s));
     const int le = mr.le();
-    Fr *z = n > kMaxChunk ? c->ws.z_long : c->ws.z;
+    Fr *z = cw.z;
     launch_challenge((const uint8_t *)blobs_dev, (const uint8_t *)commitments48_dev, z, mr.hash_rule(), n, st);
     launch_fr_mont_to_bytes(z, (uint8_t *)z32_dev, le, n, st);
     return C_KZG_OK;

@@ -95,15 +95,6 @@ struct Workspace {
     G1Affine29 *val_pts = nullptr;   // cap
     int32_t *val_kind = nullptr;     // cap
     uint32_t *val_verdict = nullptr; // cap
-    // device-resident proof calls longer than one chunk hash / validate ALL their blobs up front (both kernels are
-    // latency chains whose run time does not depend on the batch size); grow-only
-    size_t long_cap = 0;             // blobs
-    Fr *z_long = nullptr;            // long_cap
-    uint8_t *canon_long = nullptr;   // long_cap x 48
-    int32_t *status_long = nullptr;  // long_cap (when the caller passes no status array)
-    G1Affine29 *val_pts_long = nullptr;      // long_cap: the validation's scratch for such a call
-    int32_t *val_kind_long = nullptr;
-    uint32_t *val_verdict_long = nullptr;
 };
 
 // device-side scratch of one batch verification (points kept between its two GPU phases). The memory belongs to the
@@ -215,7 +206,7 @@ struct LoadTiming {
     double total_ms = 0;
 };
 
-// Pinned host staging of the host-assisted Fiat-Shamir step of SMALL device-resident proof calls (engine.hip:
+// Pinned host staging of the host-assisted Fiat-Shamir step of SMALL device-resident proof calls (proof_calls.hip:
 // blob_proof_batch_device): the GPU hash is a 3.2 ms latency chain whatever the batch, a host core with SHA extensions needs
 // 0.07 ms per blob, so up to a few dozen blobs are copied out, hashed and validated on the host threads in stream order
 // (hipLaunchHostFunc) and only the 32-byte digests go back.
@@ -347,6 +338,10 @@ struct Ctx {
     Fr *tw_fwd, *tw_inv;
     Fr28 *tw28_fwd, *tw28_inv;  // the same twiddles in the transform's own arithmetic (fr28.cuh)
     Workspace ws;
+    // device-resident proof calls longer than one chunk hash / validate ALL their blobs up front (both kernels are latency chains whose
+    // run time does not depend on the batch size): their challenges, canonical commitment bytes, status words and validation scratch,
+    // one allocation carved up (cap in blobs; under mu; proof_calls.hip: call_words)
+    GrowBuf long_words;
     SmallProofHost sph;
     DevStage stage;     // under mu
     uint8_t *one_pin = nullptr;    // 4 KiB of pinned memory for a ONE-blob proof call (r06): XYZZ sum 224 | redo flag 4 | digest 32; under mu

@@ -1,5 +1,5 @@
 // engine_internal.h -- what crosses between the engine's own translation units, and nothing else. Included only by engine.hip,
-// verify_front.hip, verify_async.hip, control.hip, load.hip, host_api.hip, tables.hip and device_api.hip; the rest of the library (verify.hip,
+// proof_calls.hip, verify_front.hip, verify_async.hip, control.hip, load.hip, host_api.hip, tables.hip and device_api.hip; the rest of the library (verify.hip,
 // verify_each.hip, cells*_api.hip, cells_verify_each.hip, recover_api.hip, multi.hip) sees the engine through engine.h, the entry points'
 // guard through abi_guard.h, the carver through carve.h and the EIP-7594 compute paths' shared code through cells_common.h.
 #pragma once
@@ -34,7 +34,6 @@ bool twin_off();
 Ctx *pick_ctx(Ctx *c, hipStream_t st);
 bool peer_busy(const Ctx *c);
 void direct_from_env(const KZGSettings *s);
-int last_proof_schedule();
 
 template <class T>
 static void dev_free(T *&p) {
@@ -54,17 +53,13 @@ struct WsLaneUse {
     }
 };
 
-// ---- engine.hip: the pinned staging of the host-assisted proof schedules ---------------------------------------------------------
-size_t small_proof_host_limit();
-size_t mid_proof_host_limit();
-bool sph_reserve(Ctx *c, size_t n, bool at_reserve = false);
-
 // ---- engine.hip: the launch stages (msm_stages and coefficients_to_msm_form are in engine.h) --------------------------------------
 G1Xyzz29 *msm_sums_stage(Ctx *c, const uint32_t *scalars_raw, size_t n, hipStream_t st, size_t base = 0, bool shared_chip = false,
                          bool lagrange = false, G1Xyzz29 *sums_out = nullptr, uint32_t *redo_flag_out = nullptr);
 size_t host_finish_limit();
 void host_finish_compress(uint8_t out[48], const G1Xyzz29 &sum);
 bool proof_in_evaluation_form(const Ctx *c, int mode);
+bool proof_on_lagrange(const Ctx *c, int mode);
 void quotient_stage(Ctx *c, int mode, const uint32_t *in, const Fr *z, uint32_t *quot, uint8_t *y_out, int le, size_t n, hipStream_t st,
                     const uint32_t *only_if = nullptr);
 bool quotient_to_msm_form(Ctx *c, int mode, size_t n, hipStream_t st, size_t base = 0);
@@ -72,11 +67,27 @@ bool coefficients_stage(Ctx *c, const uint8_t *blobs, size_t n, int mode, int32_
                         bool evaluations_ok = false, uint32_t *zero = nullptr, uint32_t zero_words = 0, uint32_t *zero2 = nullptr,
                         uint32_t zero2_words = 0);
 
-// ---- engine.hip: device-resident pipelines and helpers not in engine.h -----------------------------------------------------------
+C_KZG_RET first_status(Ctx *c, const int32_t *d_status, size_t n, hipStream_t st);
+
+// ---- proof_calls.hip: the device-resident proof pipelines not in engine.h, their pinned staging and their per-call scratch --------
 C_KZG_RET commit_and_prove_batch_device(Ctx *c, uint8_t *comm_out48, uint8_t *proof_out48, const uint8_t *blobs, size_t n, int mode,
                                         hipStream_t st, int32_t *status);
-C_KZG_RET ws_long_reserve(Ctx *c, size_t n);
-C_KZG_RET first_status(Ctx *c, const int32_t *d_status, size_t n, hipStream_t st);
+int last_proof_schedule();
+size_t small_proof_host_limit();
+size_t mid_proof_host_limit();
+bool sph_reserve(Ctx *c, size_t n, bool at_reserve = false);
+void sph_free(SmallProofHost &h);
+// Where the per-blob words of a call of n blobs live: the workspace's own arrays up to one chunk (ctx_reserve has run), the context's
+// long block -- reserved here, grow-only, a separate allocation -- beyond. `status` is the caller's array when it passes one. Caller holds c->mu.
+struct CallWords {
+    int32_t *status;
+    Fr *z;
+    uint8_t *canon;
+    G1Affine29 *val_pts;   // the validation's scratch: this, val_kind and val_verdict
+    int32_t *val_kind;
+    uint32_t *val_verdict;
+};
+C_KZG_RET call_words(Ctx *c, size_t n, int32_t *caller_status, CallWords &out);
 
 // ---- engine.hip: context-owned grow-only buffers that several files share (caller holds c->mu) -----------------------------------
 uint8_t *host_res_block(Ctx *c, size_t bytes);

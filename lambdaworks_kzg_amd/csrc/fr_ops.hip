@@ -284,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_quotient(const uint4 *__restr
     __shared__ Fr28 sh_v[kThreads];
     const int t = threadIdx.x;
     const size_t blob = blockIdx.x;
-    if (only_if && !only_if[blob]) return;   // a second pass over the blobs whose challenge changed (engine.hip: blob_proof_batch_device)
+    if (only_if && !only_if[blob]) return;   // a second pass over the blobs whose challenge changed (proof_calls.hip: head_mid_piped)
     const uint4 *cin = coeffs_raw + (blob * kBlobElems + (size_t)t * kChunk) * 2;
     const Fr28 z = fr28_from_mont256(z_mont[blob]);   // z 2^280, normalised, < 2r
 

@@ -27,7 +27,7 @@ constexpr uint32_t kEntryNegBit = 0x80000000u;
 static_assert(kNumWindows * kWindowBits >= 256 + 1, "signed digits need one spare bit");
 
 // ---- schedule selection as a pure function (r06) ------------------------------------------------------------------------------------
-// A device-resident compute_blob_kzg_proof call (engine.hip: blob_proof_batch_device; /root/reference/src/lib.rs:361-404 per blob) has
+// A device-resident compute_blob_kzg_proof call (proof_calls.hip: blob_proof_batch_device; /root/reference/src/lib.rs:361-404 per blob) has
 // five schedules for the part in front of its MSM -- who hashes, who validates, what overlaps -- and r05 chose between them inline, from
 // the batch, the warmth of the host threads, the other context's state, the table forms and six environment reads (Weak 8).
 // The choice is this function now: no HIP, no globals, no clock; tests/plan_table.cpp enumerates it on the CPU and
@@ -88,7 +88,7 @@ constexpr int kStatusBadArgs = 1;
 constexpr int kStatusError = 2;
 
 
-// ---- who hashes which blobs of a long host-pointer verification (r06; engine.hip: verify_prepare_staged) ---------------------------------
+// ---- who hashes which blobs of a long host-pointer verification (r06; verify_front.hip: verify_prepare_staged) ---------------------------
 // The batch is uploaded in slices; the GPU's hash kernel takes the HEAD (whole slices, as they land), the host threads the TAIL (the rest,
 // the ragged end included). Pure: the batch, the two measured rates, the kernel's latency.
 //   * the GPU's kernel is a latency chain of `hash_launch_s` per launch whatever its size, so the head's LAST slice has to land that long

@@ -348,7 +348,7 @@ void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, 
         hipLaunchKernelGGL(k_challenge<false>, grid, dim3(128), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from);
 }
 
-// ---- the challenge in two parts (fused commit-and-prove: engine.hip) ------------------------------------------------
+// ---- the challenge in two parts (fused commit-and-prove: proof_calls.hip) ------------------------------------------------
 // part 1: everything the commitment does not touch (2048 of the 2050 blocks), beside the commitment MSM
 void launch_challenge_midstate(const uint8_t *blobs, uint32_t *midstate, size_t n, hipStream_t st, bool be_fields) {
     if (n == 0) return;

@@ -438,7 +438,7 @@ void host_parallel_for_grain(size_t n, const std::function<void(size_t)> &fn, si
 
 // when did the host threads last finish a job (0: never in this process)? The host-assisted challenge paths of the device-resident
 // proof calls ask: threads that have been idle for long wake slowly (first touches, parked cores), and the first job of a process
-// also creates the pool (engine.hip: host_assist_warm)
+// also creates the pool (proof_calls.hip: host_assist_warm)
 int64_t host_last_active_ns() { return g_host_last_active_ns.load(std::memory_order_acquire); }
 int64_t host_now_ns() { return now_ns(); }
 
@@ -456,7 +456,7 @@ void host_pool_warm() {
 
 // mid[8 i .. 8 i + 7] = the SHA-256 chaining value after the 2048 blocks of the compute_challenge message that do not contain a byte of
 // the commitment (header | blob without its last 32 bytes): what k_challenge_pairs<true> leaves for k_challenge_finish (sha256.hip), computed
-// on the host threads for the one-pass commit-and-prove of mid-size batches (engine.hip)
+// on the host threads for the one-pass commit-and-prove of mid-size batches (proof_calls.hip)
 void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n, bool be_fields) {
     const Compress compress = best_compress();
     host_parallel_for_grain(n, [=](size_t i) {

@@ -2,7 +2,7 @@
 //
 // The synchronous call stops its thread twice: behind the transcript's copy (the host hashes it into r) and behind the copy of the
 // three sums (the host multiplies the generator and runs the pairing). Here both pieces of host work are HOST FUNCTIONS in stream
-// order (hipLaunchHostFunc, as engine.hip's small_proof_host_fn), the one O(n) piece of it -- sum r^i y_i, a serial walk over n powers
+// order (hipLaunchHostFunc, as proof_calls.hip's small_proof_host_fn), the one O(n) piece of it -- sum r^i y_i, a serial walk over n powers
 // on the host -- is a kernel (k_verify_ysum), and the verdict lands in a LwkzgVerifyResult whose state word is stored last:
 //
 //   caller's stream --event--> context stream: per-blob pass, k_verify_records, transcript -> h_rec, status words -> h_status
@@ -130,7 +130,8 @@ C_KZG_RET reserve_for(Ctx *c, size_t n) {
     LWK_HIP(hipSetDevice(c->device));
     C_KZG_RET rc = ctx_reserve(c, n < kMaxChunk ? n : kMaxChunk);
     if (rc != C_KZG_OK) return rc;
-    if (n > kMaxChunk && (rc = ws_long_reserve(c, n)) != C_KZG_OK) return rc;
+    CallWords cw;
+    if ((rc = call_words(c, n, nullptr, cw)) != C_KZG_OK) return rc;
     stream_warm_host_fn(c->stream);
     return C_KZG_OK;
 }

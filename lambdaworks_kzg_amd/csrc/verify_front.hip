@@ -179,7 +179,8 @@ static C_KZG_RET verify_prepare_staged(Ctx *c, const uint8_t *blobs, const uint8
     if (!knobs().host_stage || !(!mr.evaluation_form || evf) || n > ((size_t)1 << 17)) return C_KZG_OK;
     if (grow_reserve(c->vblobs, n, 2 * kMaxChunk, [](size_t cap) { return cap * (size_t)kBlobBytes; }, nullptr) != C_KZG_OK) return C_KZG_OK;
     uint8_t *d_all = c->vblobs.dev;
-    C_KZG_RET rc = ws_long_reserve(c, n);
+    CallWords cw;   // (the long block: only batches of more than a chunk come here)
+    C_KZG_RET rc = call_words(c, n, nullptr, cw);
     if (rc != C_KZG_OK) return rc;
     taken = true;
     const int bad = mr.bad_status();
@@ -189,7 +190,7 @@ static C_KZG_RET verify_prepare_staged(Ctx *c, const uint8_t *blobs, const uint8
     // own -- the runtime keeps a queue per priority level -- and every choice of hash stream then measures the same
     // (profiles/r06_experiments.md section 9). LWKZG_STAGE_STREAMS=c,h (experiment) puts them on side streams instead.
     hipStream_t st = c->stream, sv = c->vstream, sc = upload_stream(c), sh = c->aux[knobs().stage_streams[1]];
-    Fr *z = c->ws.z_long;
+    Fr *z = cw.z;
     // who hashes what, and when the head's launches go out: plan.h: plan_staged_verification (pure; tests/test_plan_cpu.py pins its table)
     const StagedSplit split = plan_staged_verification(n, host_hash_rate());
     const size_t slice = split.slice, n_gpu = split.n_gpu, n_host = split.n_host, every = split.every;
@@ -572,9 +573,10 @@ C_KZG_RET verify_front_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_c
     if (rcv != C_KZG_OK) return rcv;
     C_KZG_RET rc = ctx_reserve(c, n < kMaxChunk ? n : kMaxChunk);
     if (rc != C_KZG_OK) return rc;
-    if (n > kMaxChunk && (rc = ws_long_reserve(c, n)) != C_KZG_OK) return rc;
+    CallWords cw;
+    if ((rc = call_words(c, n, nullptr, cw)) != C_KZG_OK) return rc;
     Workspace &w = c->ws;
-    Fr *z = n > kMaxChunk ? w.z_long : w.z;
+    Fr *z = cw.z;
     LWK_HIP(hipMemsetAsync(vb.status_all, 0, n * 4, st));
     LWK_HIP(hipEventRecord(c->ev_fork, st));
     LWK_HIP(hipStreamWaitEvent(sv, c->ev_fork, 0));

@@ -97,6 +97,45 @@ def test_device_resident_proof_call_longer_than_one_chunk(K, engine_setup, oracl
     assert _host(d_out) == proofs
 
 
+def test_long_calls_scratch_grows_between_calls_and_keeps_the_one_chunk_results(K):
+    """The per-blob words of a call longer than one chunk live in a grow-only block of the settings object's own (proof_calls.hip:
+    call_words): 1030 blobs allocate it for 2048, 2100 make it grow to 4096 after it has been used, 1030 again find it larger than
+    they need -- once with the caller's status array, once with the block's own. Every proof must be the one a call of at most one
+    chunk gives for the same blob (those calls are held to the reference by the oracle tests above). 8 distinct blobs, tiled on
+    the device."""
+    import torch
+    from conftest import SETUP_PATH
+    ts = K.TrustedSetup.from_file(SETUP_PATH)   # a settings object of its own: nothing has grown its block yet
+    base = B.synthetic_batch(60000, 8)
+    comm8, want8 = device_commit_and_prove(K, ts, base, 8)
+    d_base, d_comm8 = _dev(base), _dev(comm8)
+
+    def tiled(n):
+        reps = (n + 7) // 8
+        return d_base.repeat(reps)[:n * B.BYTES_PER_BLOB].contiguous(), d_comm8.repeat(reps)[:48 * n].contiguous()
+
+    def proofs(n, with_status):
+        d_blobs, d_comm = tiled(n)
+        d_out = torch.zeros(48 * n, dtype=torch.uint8, device="cuda")
+        d_st = torch.full((n,), 9, dtype=torch.int32, device="cuda") if with_status else None
+        K.compute_blob_kzg_proof_batch_device(d_out.data_ptr(), d_blobs.data_ptr(), d_comm.data_ptr(), n, ts, None,
+                                              d_st.data_ptr() if with_status else None)
+        torch.cuda.synchronize()
+        if with_status:
+            assert int(d_st.abs().sum()) == 0
+        return _host(d_out)
+
+    def want(n):
+        return (want8 * ((n + 7) // 8))[:48 * n]
+
+    assert proofs(1024, True) == want(1024)      # one full chunk, the schedule the long calls take: the yardstick holds there too
+    assert proofs(1030, True) == want(1030)      # allocates the long block: 2048 blobs
+    assert proofs(2100, True) == want(2100)      # grows it to 4096
+    assert proofs(1030, True) == want(1030)
+    assert proofs(1030, False) == want(1030)
+    ts.free()
+
+
 def test_device_calls_on_two_caller_streams_overlap_safely(K, oracle):
     """Two device-resident calls in flight on two different caller streams: the first runs on the settings' context, the
     second -- arriving while that workspace is busy -- on its twin (own streams and workspace, same tables), so that the
@@ -437,7 +476,7 @@ def test_commit_and_prove_flags_a_non_canonical_blob(K, gpu_setup):
         K.set_mode(K.MODE_REFERENCE)
 
 
-# ---- small device-resident calls: the host-assisted challenge (engine.hip: small_proof_host_fn), VERDICT r03 item 6b -----------------
+# ---- small device-resident calls: the host-assisted challenge (proof_calls.hip: small_proof_host_fn), VERDICT r03 item 6b ------------
 
 @pytest.mark.parametrize("n,first", [(1, 21000), (16, 21000), (64, 21000)])   # (65, 70 above: also the host-assisted path; 256, 1024: the GPU chains)
 @pytest.mark.parametrize("mode_c", [False, True], ids=["reference", "ckzg"])
