@@ -475,6 +475,49 @@ C_KZG_RET lwkzg_verify_blob_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_o
 /* n independent verify_kzg_proof calls (src/lib.rs:407-453): item i is (commitments[i], zs[i], ys[i], proofs[i]); same contract */
 C_KZG_RET lwkzg_verify_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const Bytes48 *commitments, const Bytes32 *zs,
                                       const Bytes32 *ys, const Bytes48 *proofs, size_t n, const KZGSettings *s);
+/* the same for openings already in HBM (device pointers produced on `stream`, NULL = already complete); the verdicts come to the host */
+C_KZG_RET lwkzg_verify_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_out, const void *commitments48_dev, const void *zs32_dev,
+                                             const void *ys32_dev, const void *proofs48_dev, size_t n, const KZGSettings *s, void *stream);
+
+/* Batch verification of n openings (C_i, z_i, y_i, pi_i) with ONE pairing check: the consensus specs' verify_kzg_proof_batch, the inner
+ * function of the reference's blob batch (src/lib.rs:639-692). Verify a batch with this call first and ask lwkzg_verify_kzg_proof_each
+ * only when it answers false. In the mode the settings answer in, resolved at entry:
+ *   validation  item i is valid exactly when verify_kzg_proof on it returns C_KZG_OK: C_i and pi_i by that call's rules for compressed
+ *               G1 points (the infinity encodings it accepts included), z_i and y_i by the mode's scalar rule (reference mode: reduced;
+ *               c-kzg and eth mode: rejected when not below r).
+ *   record      canon(C_i) 48 | z_i 32 | y_i 32 | canon(pi_i) 48 = LWKZG_VERIFY_RECORD_BYTES, the layout lwkzg_verify_shard_begin
+ *               writes: the points in their canonical encoding, z and y canonical in the mode's byte order (reference mode: the
+ *               reduced value).
+ *   challenge   r = lwkzg_batch_challenge_host(records, n, mode); the sums start at r^0.
+ *   verdict     e(sum r^i C_i - [sum r^i y_i]G + sum r^i z_i pi_i, G2) e(-sum r^i pi_i, [tau]G2) == 1.
+ *   codes       C_KZG_BADARGS for ok == NULL; other NULL arguments as verify_blob_kzg_proof_batch answers them. Any invalid item: the
+ *               mode's code (C_KZG_ERROR in reference mode, C_KZG_BADARGS in c-kzg and eth mode) with *ok = false, and
+ *               lwkzg_last_error names the lowest such index. n == 0: the mode's empty-batch verdict, decided before any device work.
+ *               C_KZG_MALLOC / C_KZG_ERROR otherwise only when the device work itself fails.
+ * For n == 1 the answer is verify_kzg_proof's. On the four columns of the records lwkzg_verify_shard_begin returns for a blob batch
+ * the call has that batch's r, the partial of lwkzg_verify_shard_partial(first_index = 0) and verify_blob_kzg_proof_batch's verdict.
+ * The host form uploads 160 bytes per item into the settings' grow-only verify scratch (no allocation once that has grown) and runs
+ * the device path. */
+C_KZG_RET lwkzg_verify_kzg_proof_batch(bool *ok, const Bytes48 *commitments, const Bytes32 *zs, const Bytes32 *ys,
+                                       const Bytes48 *proofs, size_t n, const KZGSettings *s);
+/* the same for openings already in HBM: device pointers, 16-byte aligned (a misaligned pointer is C_KZG_BADARGS, decided on the host),
+ * produced on `stream` (NULL = already complete). Synchronous, *ok is a host bool, as lwkzg_verify_blob_kzg_proof_batch_device; only
+ * the 160-byte records and the three sums cross PCIe. */
+C_KZG_RET lwkzg_verify_kzg_proof_batch_device(bool *ok, const void *commitments48_dev, const void *zs32_dev, const void *ys32_dev,
+                                              const void *proofs48_dev, size_t n, const KZGSettings *s, void *stream);
+/* test hook, by the verdict call's own code path up to the pairing: r canonical big-endian as lwkzg_batch_challenge_host writes it,
+ * partial as lwkzg_verify_shard_partial(first_index = 0) writes it; arguments and codes as the host call; n == 0 writes nothing */
+C_KZG_RET lwkzg_verify_kzg_proof_batch_partial(uint8_t r_out[32], uint8_t partial_out[LWKZG_VERIFY_PARTIAL_BYTES],
+                                               const Bytes48 *commitments, const Bytes32 *zs, const Bytes32 *ys,
+                                               const Bytes48 *proofs, size_t n, const KZGSettings *s);
+/* lwkzg_verify_kzg_proof_batch_device on a verifier (lwkzg_verifier_new above; its max_blobs counts openings for this call), with
+ * lwkzg_verifier_enqueue's contract line by line: it returns once everything is enqueued, waits for nothing and allocates nothing;
+ * state is stored last; rc, ok, first_bad, r and partial are what the synchronous call and the hook above define; a rejected input is
+ * an answer (rc the mode's code, first_bad the lowest such index, the partial zero) and nothing behind r runs on unvalidated points; up
+ * to LWKZG_VERIFIER_DEPTH calls may be in flight; n above the capacity, NULL or misaligned inputs and n == 0 complete on the spot; with
+ * LWKZG_VERIFY_MSM=0 the call completes before it returns. Blob and opening calls may be mixed on one verifier and complete in order. */
+C_KZG_RET lwkzg_verifier_enqueue_openings(LwkzgVerifier *v, LwkzgVerifyResult *result, const void *commitments48_dev,
+                                          const void *zs32_dev, const void *ys32_dev, const void *proofs48_dev, size_t n, void *stream);
 
 /* EIP-7594 (PeerDAS) cells and cell proofs. The blob stands for the polynomial p the settings' mode reads (reference mode: big-endian
  * coefficients reduced mod r; c-kzg mode: little-endian evaluations on the bit-reversed 4096 domain, each < r). With w = 7^((r-1)/8192)

@@ -12,7 +12,8 @@ from .capi import (  # noqa: F401
     compute_kzg_proof, compute_kzg_proof_batch, get_mode, knob_report, lib, set_device, set_mode,
     VerifyShard, verify_shards_finish, Verifier, VerifyResult, VERIFIER_DEPTH, verifier_host_steps, batch_challenge_host,
     verify_blob_kzg_proof, verify_blob_kzg_proof_batch, verify_blob_kzg_proof_batch_device, verify_kzg_proof,
-    verify_blob_kzg_proof_each, verify_blob_kzg_proof_each_device, verify_kzg_proof_each,
+    verify_blob_kzg_proof_each, verify_blob_kzg_proof_each_device, verify_kzg_proof_each, verify_kzg_proof_each_device,
+    verify_kzg_proof_batch, verify_kzg_proof_batch_device, verify_kzg_proof_batch_partial,
     BYTES_PER_CELL, CELLS_PER_EXT_BLOB, FIELD_ELEMENTS_PER_CELL, FIELD_ELEMENTS_PER_EXT_BLOB,
     compute_cells_and_kzg_proofs, compute_cells_and_kzg_proofs_batch, compute_cells_and_kzg_proofs_batch_device,
     verify_cell_kzg_proof_batch, verify_cell_kzg_proof_batch_device, cell_verify_partials, cell_batch_challenge_host,

@@ -94,6 +94,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_verifier_host_steps",
     "lwkzg_cell_verifier_new", "lwkzg_cell_verifier_enqueue", "lwkzg_cell_verifier_pending", "lwkzg_cell_verifier_wait",
     "lwkzg_cell_verifier_free", "lwkzg_cell_verifier_host_steps", "lwkzg_cell_group_device",
+    "lwkzg_verify_kzg_proof_batch", "lwkzg_verify_kzg_proof_batch_device", "lwkzg_verify_kzg_proof_batch_partial",
+    "lwkzg_verifier_enqueue_openings", "lwkzg_verify_kzg_proof_each_device",
 ]
 
 _lib = None
@@ -138,6 +140,10 @@ def lib():
     l.lwkzg_verify_blob_kzg_proof_each.argtypes = [pu8, pi32, C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
     l.lwkzg_verify_blob_kzg_proof_each_device.argtypes = [pu8, pi32, vp, vp, vp, sz, ps, vp]
     l.lwkzg_verify_kzg_proof_each.argtypes = [pu8, pi32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_verify_kzg_proof_each_device.argtypes = [pu8, pi32, vp, vp, vp, vp, sz, ps, vp]
+    l.lwkzg_verify_kzg_proof_batch.argtypes = [C.POINTER(C.c_bool), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_verify_kzg_proof_batch_device.argtypes = [C.POINTER(C.c_bool), vp, vp, vp, vp, sz, ps, vp]
+    l.lwkzg_verify_kzg_proof_batch_partial.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
     l.lwkzg_pairing_line_table.argtypes = [C.c_char_p, C.c_char_p]
     l.lwkzg_compute_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, ps]
     l.lwkzg_compute_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, sz, ps, C.POINTER(sz)]
@@ -176,6 +182,7 @@ def lib():
     l.lwkzg_verify_shards_finish.argtypes = [C.POINTER(C.c_bool), C.c_char_p, sz, sz, ps]
     l.lwkzg_verifier_new.argtypes = [C.POINTER(vp), ps, sz]
     l.lwkzg_verifier_enqueue.argtypes = [vp, C.POINTER(VerifyResult), vp, vp, vp, sz, vp]
+    l.lwkzg_verifier_enqueue_openings.argtypes = [vp, C.POINTER(VerifyResult), vp, vp, vp, vp, sz, vp]
     l.lwkzg_verifier_pending.argtypes = [vp]
     l.lwkzg_verifier_wait.argtypes = [vp]
     l.lwkzg_verifier_free.argtypes = [vp]
@@ -705,6 +712,41 @@ def verify_kzg_proof_each(commitments, zs, ys, proofs, ts):
                  lambda ok, rc: lib().lwkzg_verify_kzg_proof_each(ok, rc, commitments, zs, ys, proofs, n, ts.ref()))
 
 
+def verify_kzg_proof_each_device(comm_ptr, zs_ptr, ys_ptr, proofs_ptr, n, ts, stream=None):
+    """the same on DEVICE pointers (produced on `stream`); the verdicts come to the host, the call is synchronous"""
+    return _each("lwkzg_verify_kzg_proof_each_device", n,
+                 lambda ok, rc: lib().lwkzg_verify_kzg_proof_each_device(ok, rc, comm_ptr, zs_ptr, ys_ptr, proofs_ptr, n, ts.ref(), stream))
+
+
+def verify_kzg_proof_batch(commitments, zs, ys, proofs, ts):
+    """n openings (C_i, z_i, y_i, pi_i) with one pairing check (lwkzg_verify_kzg_proof_batch): the consensus specs'
+    verify_kzg_proof_batch. Inputs: the concatenated commitments, zs, ys and proofs (bytes). Raises KzgError when an item is invalid."""
+    n = len(commitments) // 48
+    assert len(commitments) == 48 * n and len(proofs) == 48 * n and len(zs) == 32 * n and len(ys) == 32 * n
+    ok = C.c_bool(False)
+    _check("lwkzg_verify_kzg_proof_batch", lib().lwkzg_verify_kzg_proof_batch(C.byref(ok), commitments, zs, ys, proofs, n, ts.ref()))
+    return bool(ok.value)
+
+
+def verify_kzg_proof_batch_device(comm_ptr, zs_ptr, ys_ptr, proofs_ptr, n, ts, stream=None):
+    """the same on DEVICE pointers (16-byte aligned, produced on `stream`); the verdict is a host bool, the call synchronous"""
+    ok = C.c_bool(False)
+    _check("lwkzg_verify_kzg_proof_batch_device",
+           lib().lwkzg_verify_kzg_proof_batch_device(C.byref(ok), comm_ptr, zs_ptr, ys_ptr, proofs_ptr, n, ts.ref(), stream))
+    return bool(ok.value)
+
+
+def verify_kzg_proof_batch_partial(commitments, zs, ys, proofs, ts):
+    """test hook: (r, partial) of the batch call up to its pairing -- r as batch_challenge_host writes it, the partial as
+    VerifyShard.partial(records, n, 0) writes it"""
+    n = len(commitments) // 48
+    assert len(commitments) == 48 * n and len(proofs) == 48 * n and len(zs) == 32 * n and len(ys) == 32 * n
+    r, partial = C.create_string_buffer(32), C.create_string_buffer(VERIFY_PARTIAL_BYTES)
+    _check("lwkzg_verify_kzg_proof_batch_partial",
+           lib().lwkzg_verify_kzg_proof_batch_partial(r, partial, commitments, zs, ys, proofs, n, ts.ref()))
+    return r.raw, partial.raw
+
+
 def _cells_split(cells_raw, proofs_raw, n):
     """n x 128 cells / proofs as returned by the library -> [(cells, proofs)] per blob, each a list of 128 bytes objects (or None)"""
     out = []
@@ -971,12 +1013,12 @@ class _AsyncVerifier:
     def _fn(self, name):
         return getattr(lib(), self._PREFIX + name)
 
-    def _enqueue(self, *args):
+    def _enqueue(self, *args, call="enqueue"):
         res = self._RESULT()
         self._results = [r for r in self._results if r.state != 1][-4 * VERIFIER_DEPTH:] + [res]
-        rc = self._fn("enqueue")(self.h, C.byref(res), *args)
+        rc = self._fn(call)(self.h, C.byref(res), *args)
         if rc != C_KZG_OK:
-            err = KzgError(self._PREFIX + "enqueue", rc)
+            err = KzgError(self._PREFIX + call, rc)
             err.result = res
             raise err
         return res
@@ -1011,6 +1053,11 @@ class Verifier(_AsyncVerifier):
     def enqueue(self, blobs_ptr, comm_ptr, proofs_ptr, n, stream=None):
         """returns at once; raises KzgError (its .result is the completed VerifyResult) for what the call itself refuses"""
         return self._enqueue(blobs_ptr, comm_ptr, proofs_ptr, n, stream)
+
+    def enqueue_openings(self, comm_ptr, zs_ptr, ys_ptr, proofs_ptr, n, stream=None):
+        """the same for n openings (lwkzg_verifier_enqueue_openings): verify_kzg_proof_batch_device without the wait; the verifier's
+        capacity counts openings here. Blob and opening calls may be mixed and complete in order."""
+        return self._enqueue(comm_ptr, zs_ptr, ys_ptr, proofs_ptr, n, stream, call="enqueue_openings")
 
 
 def verifier_host_steps(records, n, first_bad, sums3x97, ysum32, settings_ref, mode):

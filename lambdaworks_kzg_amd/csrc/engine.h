@@ -438,8 +438,20 @@ C_KZG_RET verify_front_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d_c
                               VerifyBuffers &vb, hipStream_t caller, bool want_records, bool keep, bool *recorded);
 // the same front for n openings (C, z, y, pi) already on the device (verify_each.hip): both point sets validated, z / y checked and
 // written canonical in the mode's byte order to vb.d_rz / vb.d_r, the status words in vb.status_all; enqueued on c->stream
+// caller: the stream the inputs were produced on (may be null)
 C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const uint8_t *d_proofs, const uint8_t *d_z, const uint8_t *d_y,
-                                         size_t n, int mode, VerifyBuffers &vb);
+                                         size_t n, int mode, VerifyBuffers &vb, hipStream_t caller = nullptr);
+// The front of a BATCH of n openings already on the device, enqueue-only like verify_front_device and under the
+// same locks: both point sets validated on a side stream, the rows of the sums on another as soon as the points are decompressed,
+// then k_opening_records -- z / y checked and written canonical to vb.d_rz / vb.d_r, the transcript assembled, the lowest rejected index
+// behind it -- and the ONE copy into vb.h_rec (*recorded). d_z / d_y are 16-byte aligned and may be vb.d_rz / vb.d_r themselves.
+C_KZG_RET verify_openings_front_device(Ctx *c, const uint8_t *d_comm, const uint8_t *d_proofs, const uint8_t *d_z, const uint8_t *d_y,
+                                       size_t n, int mode, VerifyBuffers &vb, hipStream_t caller, bool *recorded);
+// that front plus the wait: the n records to records_out (host), or the rejected input's status code with the lowest such index in the
+// error text. device_inputs == false: comm .. y are host memory and go up into the scratch first (160 bytes per item, no allocation
+// once the scratch has grown)
+C_KZG_RET verify_openings_prepare(Ctx *c, const uint8_t *comm, const uint8_t *proofs, const uint8_t *z, const uint8_t *y, size_t n, int mode,
+                                  VerifyBuffers &vb, bool device_inputs, hipStream_t caller, uint8_t *records_out);
 C_KZG_RET lincomb3_device_host(Ctx *c, VerifyBuffers &vb, const uint8_t *sc_r, const uint8_t *sc_rz, size_t n,
                                uint8_t sums[3][96], int infs[3]);
 // r06: the same three sums from r alone (vmsm.hip). pw33: r^(2^k), k = 0..31, then r^first, Montgomery form. vmsm_begin only
@@ -468,6 +480,11 @@ C_KZG_RET verify_async_verdict(bool *ok, uint8_t *partial, const uint8_t sums96[
                                const KZGSettings *own);
 C_KZG_RET verify_batch_device_full(bool *ok, uint8_t r_be[32], uint8_t *partial, const uint8_t *d_blobs, const uint8_t *d_comm,
                                    const uint8_t *d_proofs, size_t n, const KZGSettings *s, int mode, hipStream_t caller);
+// the batch of n openings, begin to verdict (verify.hip). Each output is optional: r_be as
+// lwkzg_batch_challenge_host writes it, partial as lwkzg_verify_shard_partial(first_index = 0) writes it, ok from the one pairing check
+// (NULL: no pairing). n > 0 and no NULL input; device_inputs: device pointers, 16-byte aligned, produced on `caller`
+C_KZG_RET verify_openings_batch_full(bool *ok, uint8_t *r_be, uint8_t *partial, const uint8_t *comm, const uint8_t *z, const uint8_t *y,
+                                     const uint8_t *proofs, size_t n, const KZGSettings *s, int mode, bool device_inputs, hipStream_t caller);
 
 // G2 / pairing side (g2_pairing.hip, host only)
 bool g2_fill_values(g2_t *out65, const uint8_t *g2_bytes, size_t n2);

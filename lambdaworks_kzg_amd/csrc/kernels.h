@@ -223,6 +223,13 @@ void launch_verify_records(const uint8_t *canon_c, const uint8_t *z32, const uin
 // reduced) and written canonical in the mode's byte order; a rejected item gets bad_code in status
 void launch_each_openings(const uint8_t *z_in, const uint8_t *y_in, uint8_t *z_out, uint8_t *y_out, int32_t *status, int bad_code,
                           int scalar_rule, size_t n, hipStream_t st);
+// verify_openings.hip: launch_each_openings and launch_verify_records in ONE launch for a batch of openings. z_in / y_in (16-byte aligned)
+// are read by scalar_rule and written canonical to z_out / y_out (where k_vmsm_scalars and k_verify_ysum read them; in place is fine);
+// records[160 i] = canon_c | z_out | y_out | canon_p; a rejected scalar puts bad_code into status[i]; *first_bad (pre-set to 0xffffffff)
+// = the lowest index whose status word is set, by the validation before this launch or by this launch
+void launch_opening_records(const uint8_t *z_in, const uint8_t *y_in, const uint8_t *canon_c, const uint8_t *canon_p, uint8_t *z_out,
+                            uint8_t *y_out, int32_t *status, int bad_code, int scalar_rule, uint8_t *records, uint32_t *first_bad, size_t n,
+                            hipStream_t st);
 void launch_xyzz29_to_affine_be(const G1Xyzz29 *in, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st);
 
 // ---- Fiat-Shamir (sha256.hip, sha256_host.hip)

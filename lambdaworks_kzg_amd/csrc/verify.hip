@@ -527,6 +527,24 @@ C_KZG_RET shard_begin(Shard &sh, const uint8_t *blobs, const uint8_t *comms, con
     return C_KZG_OK;
 }
 
+// the same for n openings (C_i, z_i, y_i, pi_i): nothing is hashed or evaluated per item, the records are the validated inputs
+// themselves (verify_front.hip: verify_openings_prepare). On the context's scratch; device_inputs as above. n > 0
+C_KZG_RET shard_begin_openings(Shard &sh, const uint8_t *comms, const uint8_t *zs, const uint8_t *ys, const uint8_t *proofs, size_t n,
+                               const KZGSettings *s, int mode, bool device_inputs, hipStream_t caller) {
+    sh.ctx = ctx_of(s);
+    if (!sh.ctx) return C_KZG_ERROR;
+    sh.device = sh.ctx->device;
+    sh.ctx_generation = sh.ctx->generation;
+    sh.s = s;
+    sh.n = n;
+    sh.mode = mode;
+    sh.vb.owned = false;
+    sh.records.resize(kRecord * n);
+    const C_KZG_RET rc = verify_openings_prepare(sh.ctx, comms, proofs, zs, ys, n, mode, sh.vb, device_inputs, caller, sh.records.data());
+    if (rc != C_KZG_OK) return mode_rules(mode).bad == C_KZG_ERROR ? C_KZG_ERROR : rc;
+    return C_KZG_OK;
+}
+
 // this shard's records
 void shard_records(const Shard &sh, uint8_t *out) {
     if (sh.n) memcpy(out, sh.records.data(), kRecord * sh.n);
@@ -774,6 +792,43 @@ C_KZG_RET verify_batch_device_full(bool *ok, uint8_t r_be[32], uint8_t *partial,
     uint32_t ys_raw[8];
     hfr_to_raw(ys_raw, ysum);
     return verdict_from_sums(ok, partial, sums, ys_raw, s);
+}
+
+// ---- a batch of openings, begin to verdict (verify_openings.hip, verify_async.hip) -----------------------------------
+// verify_batch_impl's three steps on the records of n openings: one shard, its partial sums with [sum r^i y_i]G on a thread beside
+// them, one pairing. r_be, partial and ok are each optional; the hook (ok == NULL) is this code up to the pairing.
+C_KZG_RET verify_openings_batch_full(bool *ok, uint8_t *r_be, uint8_t *partial, const uint8_t *comm, const uint8_t *z, const uint8_t *y,
+                                     const uint8_t *proofs, size_t n, const KZGSettings *s, int mode, bool device_inputs, hipStream_t caller) {
+    if (ok) *ok = false;
+    Shard sh;
+    C_KZG_RET rc = shard_begin_openings(sh, comm, z, y, proofs, n, s, mode, device_inputs, caller);
+    if (rc != C_KZG_OK) return rc;
+    if (r_be) {   // (the challenge's bytes by the asynchronous step 1's own body; shard_partial takes r from the records itself)
+        Fr pw[33];
+        verify_async_challenge(r_be, pw, sh.records.data(), n, mode);
+    }
+    HostPoint g;
+    if (!setup_generator(g, s)) {
+        set_error("g1_values[0] is not a curve point");
+        return C_KZG_ERROR;
+    }
+    HXyzz ysum_g = HXyzz::infinity();
+    SideTask side;
+    HXyzz sums[3];
+    HFr ysum;
+    rc = shard_partial(sh, sh.records.data(), n, 0, sums, ysum, [&](const HFr &ys) {
+        if (!ok) return;
+        side.start([&, ys]() {
+            uint32_t ys_raw[8];
+            hfr_to_raw(ys_raw, ys);
+            ysum_g = generator_mul(g.a, ys_raw);
+        });
+    });
+    side.join();
+    if (rc != C_KZG_OK) return C_KZG_ERROR;
+    if (partial) partial_to_bytes(partial, sums, ysum);
+    if (!ok) return C_KZG_OK;
+    return batch_verdict(ok, sums, ysum_g, s);
 }
 
 // ---- the host's end of the cell proof batch (cells_verify_api.hip) ------------------------------------------------

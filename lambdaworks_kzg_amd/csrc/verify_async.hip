@@ -13,6 +13,9 @@
 //                              HOST FUNCTION 2: [sum r^i y_i]G, pairing, partial -> *result, state = 1 (release), slot freed
 //   caller's stream <--event-- (work enqueued behind the call sees the verdict)
 //
+// lwkzg_verifier_enqueue_openings is the same call for n openings (C, z, y, pi): verify_openings_front_device in place of the per-blob
+// pass and k_verify_records, everything from host function 1 on unchanged.
+//
 // Calls on one verifier share its VerifyBuffers and run one after the other: on one context by stream order, across the settings' two
 // contexts (pick_ctx) by the verifier's last_done event. The job slots and their hand-over are verifier_ring.h; what this verifier
 // shares with the cells' (cells_verify_async.hip) -- the handle's head, the enqueue around enqueue_on, pending / wait / free -- is
@@ -176,9 +179,11 @@ C_KZG_RET verifier_new_impl(LwkzgVerifier **out, const KZGSettings *s, size_t ma
     return async_verifier_new_end(out, v, rc);
 }
 
-// everything of one call on context c, enqueued; caller holds c->mu. *hf: host functions handed to the runtime so far
-C_KZG_RET enqueue_on(Verifier *v, Ctx *c, AsyncJob *j, const uint8_t *blobs, const uint8_t *comm, const uint8_t *proofs, hipStream_t caller,
-                     int *hf) {
+// everything of one call on context c, enqueued; caller holds c->mu. *hf: host functions handed to the runtime so far.
+// front(c, vb, &recorded): the enqueue-only front of the call's kind -- verify_front_device for blobs, verify_openings_front_device for
+// openings; both leave the transcript on its way to vb.h_rec, the canonical z / y bytes in vb.d_rz / vb.d_r and the rows of both point sets
+template <class Front>
+C_KZG_RET enqueue_on(Verifier *v, Ctx *c, AsyncJob *j, hipStream_t caller, int *hf, Front front) {
     LWK_HIP(hipSetDevice(c->device));
     VerifyBuffers &vb = v->vb;
     const size_t n = j->n;
@@ -189,7 +194,7 @@ C_KZG_RET enqueue_on(Verifier *v, Ctx *c, AsyncJob *j, const uint8_t *blobs, con
     C_KZG_RET rc = async_enqueue_head(v, c);
     if (rc != C_KZG_OK) return rc;
     bool recorded = false;
-    rc = verify_front_device(c, blobs, comm, proofs, n, j->mode, vb, caller, true, false, &recorded);
+    rc = front(c, vb, &recorded);
     if (rc != C_KZG_OK) return rc;
     if (!recorded) {
         set_error("lwkzg_verifier_enqueue: the verifier's scratch has no room for the transcript");
@@ -236,8 +241,44 @@ C_KZG_RET verifier_enqueue_impl(const LwkzgVerifier *handle, LwkzgVerifyResult *
         complete_now(res, rc, ok);
         return C_KZG_OK;
     }
-    return async_enqueue(v, res, n, mode, caller,
-                         [&](Ctx *c, AsyncJob *j, int *hf) { return enqueue_on(v, c, j, blobs, comm, proofs, caller, hf); });
+    return async_enqueue(v, res, n, mode, caller, [&](Ctx *c, AsyncJob *j, int *hf) {
+        return enqueue_on(v, c, j, caller, hf, [&](Ctx *cc, VerifyBuffers &vb, bool *recorded) {
+            return verify_front_device(cc, blobs, comm, proofs, n, mode, vb, caller, true, false, recorded);
+        });
+    });
+}
+
+// lwkzg_verifier_enqueue for n openings: the same checks, the same two host functions and the same launches
+// behind r; only the front differs. The verifier's capacity counts openings here.
+C_KZG_RET verifier_enqueue_openings_impl(const LwkzgVerifier *handle, LwkzgVerifyResult *res, const uint8_t *comm, const uint8_t *zs,
+                                         const uint8_t *ys, const uint8_t *proofs, size_t n, hipStream_t caller) {
+    AsyncVerifier *base;
+    const C_KZG_RET refused = async_enqueue_checks(&base, handle, kVerifierMagic, res, n, "lwkzg_verifier_enqueue_openings", "openings");
+    if (refused != C_KZG_OK) return refused;
+    Verifier *v = static_cast<Verifier *>(base);
+    const int mode = mode_of(v->s);
+    if (n == 0) {
+        complete_now(res, C_KZG_OK, mode_rules(mode).empty_ok);
+        return C_KZG_OK;
+    }
+    if (!comm || !zs || !ys || !proofs) return async_refuse(res, C_KZG_BADARGS);
+    if ((((uintptr_t)comm | (uintptr_t)zs | (uintptr_t)ys | (uintptr_t)proofs) & 15u) != 0) {
+        set_error("lwkzg_verifier_enqueue_openings: the device pointers must be 16-byte aligned");
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    std::lock_guard<std::mutex> enq(v->enq_mu);
+    if (!vmsm_ready(v->vb)) {   // the experiment arm LWKZG_VERIFY_MSM=0: the synchronous call, complete before this returns
+        v->ring.wait();
+        bool ok = false;
+        const C_KZG_RET rc = verify_openings_batch_full(&ok, res->r, res->partial, comm, zs, ys, proofs, n, v->s, mode, true, caller);
+        complete_now(res, rc, ok);
+        return C_KZG_OK;
+    }
+    return async_enqueue(v, res, n, mode, caller, [&](Ctx *c, AsyncJob *j, int *hf) {
+        return enqueue_on(v, c, j, caller, hf, [&](Ctx *cc, VerifyBuffers &vb, bool *recorded) {
+            return verify_openings_front_device(cc, comm, proofs, zs, ys, n, mode, vb, caller, recorded);
+        });
+    });
 }
 
 }  // namespace
@@ -257,6 +298,14 @@ C_KZG_RET lwkzg_verifier_enqueue(LwkzgVerifier *v, LwkzgVerifyResult *result, co
     return guarded("lwkzg_verifier_enqueue", [&] {
         return verifier_enqueue_impl(v, result, (const uint8_t *)blobs_dev, (const uint8_t *)commitments48_dev, (const uint8_t *)proofs48_dev, n,
                                      (hipStream_t)stream);
+    });
+}
+
+C_KZG_RET lwkzg_verifier_enqueue_openings(LwkzgVerifier *v, LwkzgVerifyResult *result, const void *commitments48_dev, const void *zs32_dev,
+                                          const void *ys32_dev, const void *proofs48_dev, size_t n, void *stream) {
+    return guarded("lwkzg_verifier_enqueue_openings", [&] {
+        return verifier_enqueue_openings_impl(v, result, (const uint8_t *)commitments48_dev, (const uint8_t *)zs32_dev, (const uint8_t *)ys32_dev,
+                                              (const uint8_t *)proofs48_dev, n, (hipStream_t)stream);
     });
 }
 

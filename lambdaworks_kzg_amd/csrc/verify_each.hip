@@ -1,5 +1,5 @@
 // verify_each.hip -- n independent verifications in one call, each with its own answer: lwkzg_verify_blob_kzg_proof_each (+ _device)
-// and lwkzg_verify_kzg_proof_each -- n verify_blob_kzg_proof / verify_kzg_proof calls (the reference's src/lib.rs:456-505, 407-453).
+// and lwkzg_verify_kzg_proof_each (+ _device) -- n verify_blob_kzg_proof / verify_kzg_proof calls (the reference's src/lib.rs:456-505, 407-453).
 //
 // Every step runs on the GPU, the pairing included:
 //   front    the batch verification's device front for blobs (verify_prepare_device, keep = true: validation of C_i and pi_i, the
@@ -179,7 +179,7 @@ C_KZG_RET verify_each_device(uint8_t *ok_out, int32_t *rc_out, Ctx *ctx, const K
     VerifyBuffers vb;   // holds the context's verify scratch until the verdicts are back
     C_KZG_RET rc = d_blobs ? verify_prepare_device(ctx, d_blobs, d_comm, d_proofs, n, mode, nullptr, nullptr, nullptr, nullptr, vb, caller,
                                                    nullptr, true)
-                           : verify_openings_prepare_device(ctx, d_comm, d_proofs, d_z, d_y, n, mode, vb);
+                           : verify_openings_prepare_device(ctx, d_comm, d_proofs, d_z, d_y, n, mode, vb, caller);
     if (rc != C_KZG_OK) return rc == C_KZG_MALLOC ? rc : C_KZG_ERROR;
     std::vector<int32_t> status(n);
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -300,6 +300,19 @@ C_KZG_RET lwkzg_verify_kzg_proof_each(uint8_t *ok_out, int32_t *rc_out, const By
         if (!ctx) return C_KZG_ERROR;
         return verify_each_host(ok_out, rc_out, ctx, s, mode_of(s), nullptr, (const uint8_t *)commitments, (const uint8_t *)proofs,
                                 (const uint8_t *)zs, (const uint8_t *)ys, n);
+    });
+}
+
+C_KZG_RET lwkzg_verify_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_out, const void *commitments48_dev, const void *zs32_dev,
+                                             const void *ys32_dev, const void *proofs48_dev, size_t n, const KZGSettings *s, void *stream) {
+    return guarded("lwkzg_verify_kzg_proof_each_device", [&]() -> C_KZG_RET {
+        if (!ok_out || !rc_out || !s) return C_KZG_BADARGS;
+        if (n == 0) return C_KZG_OK;
+        if (!commitments48_dev || !zs32_dev || !ys32_dev || !proofs48_dev) return C_KZG_BADARGS;
+        Ctx *ctx = ctx_of(s);
+        if (!ctx) return C_KZG_ERROR;
+        return verify_each_device(ok_out, rc_out, ctx, s, mode_of(s), nullptr, (const uint8_t *)commitments48_dev, (const uint8_t *)proofs48_dev,
+                                  (const uint8_t *)zs32_dev, (const uint8_t *)ys32_dev, n, (hipStream_t)stream);
     });
 }
 

@@ -684,13 +684,17 @@ C_KZG_RET verify_prepare_device(Ctx *c, const uint8_t *d_blobs, const uint8_t *d
 }
 
 C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const uint8_t *d_proofs, const uint8_t *d_z, const uint8_t *d_y,
-                                         size_t n, int mode, VerifyBuffers &vb) {
+                                         size_t n, int mode, VerifyBuffers &vb, hipStream_t caller) {
     vb.hold = std::unique_lock<std::mutex>(c->verify_mu);
     std::lock_guard<std::mutex> lk(c->mu);
     LWK_HIP(hipSetDevice(c->device));
     const ModeRules mr = mode_rules(mode);
     const int bad = mr.bad_status();
     hipStream_t st = c->stream;
+    if (caller && caller != st) {  // the inputs are whatever the caller's stream has produced by now
+        LWK_HIP(hipEventRecord(c->ev_join[3], caller));
+        LWK_HIP(hipStreamWaitEvent(st, c->ev_join[3], 0));
+    }
     WsUse wsu(c, st);
     C_KZG_RET rc = vs_reserve(c, n);
     if (rc != C_KZG_OK) return rc;
@@ -701,6 +705,113 @@ C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const ui
     launch_subgroup_canon(set_p, &set_c, vb.status_all, bad, n, st);
     launch_each_openings(d_z, d_y, vb.d_rz, vb.d_r, vb.status_all, bad, mr.scalar_rule(), n, st);
     LWK_HIP(hipGetLastError());
+    return C_KZG_OK;
+}
+
+// ---- a batch of openings -------------------------------------------------------------------------------------------
+// verify_front_device without the blob: no hash and no evaluation, so nothing on the main stream until the validation is through, and
+// no hash to keep apart from -- but the subgroup test and the rows, which run beside each other, keep their LDS footprints.
+//
+//   main stream   status words, first-bad word cleared ........ k_opening_records, transcript -> h_rec [ev_join[4]] .. joins the rows
+//   vstream       k_decompress_points (both sets) [ev_join[2]], subgroup test + canonical bytes (both sets) [ev_join[0]]
+//   aux[0]                                         ........... the rows of both sets [ev_join[1]]
+//
+// Enqueue-only; caller holds c->mu (and verify_mu unless vb.owned) and has selected the device. ev_join[4] marks the transcript's arrival,
+// so that a synchronous caller can hash it while the rows are still being built.
+C_KZG_RET verify_openings_front_device(Ctx *c, const uint8_t *d_comm, const uint8_t *d_proofs, const uint8_t *d_z, const uint8_t *d_y,
+                                       size_t n, int mode, VerifyBuffers &vb, hipStream_t caller, bool *recorded) {
+    *recorded = false;
+    const ModeRules mr = mode_rules(mode);
+    const int bad = mr.bad_status();
+    hipStream_t st = c->stream, sv = c->vstream, sc = c->aux[0];
+    if (caller && caller != st) {  // the inputs are whatever the caller's stream has produced by now
+        LWK_HIP(hipEventRecord(c->ev_join[3], caller));
+        LWK_HIP(hipStreamWaitEvent(st, c->ev_join[3], 0));
+    }
+    struct SideDrain {
+        Ctx *c;
+        bool armed = true;
+        ~SideDrain() {
+            if (!armed) return;
+            hipStreamSynchronize(c->vstream);
+            hipStreamSynchronize(c->aux[0]);
+        }
+    } drain{c};
+    const C_KZG_RET rcv = verify_buffers_take(c, vb, n);
+    if (rcv != C_KZG_OK) return rcv;
+    if (!(vb.d_rec && vb.h_rec && vb.rec_cap >= n)) {
+        set_error("openings batch: the verify scratch has no room for a transcript of %zu records", n);
+        return C_KZG_ERROR;
+    }
+    uint32_t *d_flag = (uint32_t *)(vb.d_rec + 160 * n);
+    LWK_HIP(hipMemsetAsync(vb.status_all, 0, n * 4, st));
+    LWK_HIP(hipMemsetAsync(d_flag, 0xff, 4, st));
+    LWK_HIP(hipEventRecord(c->ev_fork, st));
+    LWK_HIP(hipStreamWaitEvent(sv, c->ev_fork, 0));
+    LWK_HIP(hipStreamWaitEvent(sc, c->ev_fork, 0));
+    const PointSet set_p{d_proofs, vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p}, set_c{d_comm, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c};
+    // No hash runs beside these launches, but the subgroup test and the rows run beside EACH OTHER: up to kVerifyApartMax all three keep
+    // the LDS footprints of the blob path, which no two of their workgroups can share a compute unit under (4096 openings:
+    // k_vmsm_multiples 1.63 -> 1.25 ms, the call 3.4 -> 3.0 ms; a footprint on the rows alone changes nothing)
+    const bool apart = n <= kVerifyApartMax;
+    launch_decompress_points(set_p, &set_c, n, sv, apart);
+    LWK_HIP(hipEventRecord(c->ev_join[2], sv));
+    launch_subgroup_canon(set_p, &set_c, vb.status_all, bad, n, sv, apart);
+    LWK_HIP(hipEventRecord(c->ev_join[0], sv));
+    LWK_HIP(hipStreamWaitEvent(sc, c->ev_join[2], 0));
+    launch_verify_rows(vb, n, sc, apart);
+    LWK_HIP(hipEventRecord(c->ev_join[1], sc));
+    LWK_HIP(hipStreamWaitEvent(st, c->ev_join[0], 0));
+    launch_opening_records(d_z, d_y, vb.canon_dev, vb.canon_dev + 48 * n, vb.d_rz, vb.d_r, vb.status_all, bad, mr.scalar_rule(), vb.d_rec, d_flag,
+                           n, st);
+    LWK_HIP(hipMemcpyAsync(vb.h_rec, vb.d_rec, 160 * n + 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipEventRecord(c->ev_join[4], st));
+    LWK_HIP(hipStreamWaitEvent(st, c->ev_join[1], 0));
+    drain.armed = false;  // both side streams are joined into the main stream from here on
+    LWK_HIP(hipGetLastError());
+    *recorded = true;
+    return C_KZG_OK;
+}
+
+C_KZG_RET verify_openings_prepare(Ctx *c, const uint8_t *comm, const uint8_t *proofs, const uint8_t *z, const uint8_t *y, size_t n, int mode,
+                                  VerifyBuffers &vb, bool device_inputs, hipStream_t caller, uint8_t *records_out) {
+    if (!vb.owned) vb.hold = std::unique_lock<std::mutex>(c->verify_mu);
+    std::lock_guard<std::mutex> lk(c->mu);
+    LWK_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (!device_inputs) {
+        // host memory: 160 bytes per item into the scratch the front runs on -- the points where a host-pointer blob batch puts them,
+        // z and y where k_opening_records leaves their canonical bytes (it works in place)
+        const C_KZG_RET rcv = verify_buffers_take(c, vb, n);
+        if (rcv != C_KZG_OK) return rcv;
+        LWK_HIP(hipMemcpyAsync(vb.comm_in, comm, 48 * n, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(vb.proof_in, proofs, 48 * n, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(vb.d_rz, z, 32 * n, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(vb.d_r, y, 32 * n, hipMemcpyHostToDevice, st));
+        comm = vb.comm_in;
+        proofs = vb.proof_in;
+        z = vb.d_rz;
+        y = vb.d_r;
+        caller = nullptr;
+    }
+    bool recorded = false;
+    const C_KZG_RET rc = verify_openings_front_device(c, comm, proofs, z, y, n, mode, vb, caller, &recorded);
+    if (rc != C_KZG_OK) return rc;
+    LWK_HIP(hipEventSynchronize(c->ev_join[4]));   // the transcript has landed; the rows may still be on their way
+    uint32_t first_bad;
+    memcpy(&first_bad, vb.h_rec + 160 * n, 4);
+    if (first_bad != 0xffffffffu) {
+        int32_t code = 0;
+        if (first_bad >= n) {
+            set_error("openings batch: the device reported a rejected index %zu of %zu", (size_t)first_bad, n);
+            return C_KZG_ERROR;
+        }
+        LWK_HIP(hipMemcpyAsync(&code, vb.status_all + first_bad, 4, hipMemcpyDeviceToHost, st));
+        LWK_HIP(hipStreamSynchronize(st));   // (the rows included: nothing of this call is running when it returns)
+        set_error("opening %zu rejected (status %d)", (size_t)first_bad, code);
+        return (C_KZG_RET)code;
+    }
+    memcpy(records_out, vb.h_rec, 160 * n);
     return C_KZG_OK;
 }
 
