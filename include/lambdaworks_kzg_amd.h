@@ -735,6 +735,46 @@ C_KZG_RET lwkzg_verify_cell_kzg_proof_each_device(uint8_t *ok_out, int32_t *rc_o
 C_KZG_RET lwkzg_cell_verify_each_points(uint8_t *out /* n x 97 */, const Bytes48 *commitments, const uint64_t *cell_indices,
                                         const Cell *cells, const Bytes48 *proofs, size_t n, const KZGSettings *s);
 
+/* Per-group cell verification: g lwkzg_verify_cell_kzg_proof_batch calls in one, for a caller whose items come in units it must judge
+ * one by one (the column sidecars of different peers, the blobs of different transactions). Group j is the items
+ * group_offsets[j] .. group_offsets[j + 1] - 1 of the four item arrays (c-kzg-4844 2.x's item layout). For every j, rc_out[j] (a
+ * C_KZG_RET) and ok_out[j] (0/1) are exactly the return code and *ok of the batch call on the items of group j alone, in the mode the
+ * settings answer in and on every engine: the de-duplication and the row numbers, the transcript header's m and n, and r are the
+ * group's own. Inside a group, as in the batch call:
+ *     an index >= 128                                    rc C_KZG_BADARGS in both modes (decided first and on the host), ok 0
+ *     a commitment or a proof that is not a compressed
+ *     point of G1 (infinity allowed), or a cell element
+ *     not below r                                        rc the mode's code (C_KZG_ERROR reference, C_KZG_BADARGS c-kzg), ok 0
+ *     otherwise                                          rc C_KZG_OK, ok the verdict
+ *     an empty group                                     rc C_KZG_OK, ok 1 (the batch call's answer to n == 0)
+ * A bad group is an answer, not a failure, and does not spread: a good group's answer never depends on its neighbours, and nothing
+ * behind r runs on a bad group's unvalidated points or unchecked indices. The call returns C_KZG_OK once every group is decided;
+ * C_KZG_BADARGS, decided before any device work and with nothing written, for s NULL, ok_out / rc_out / group_offsets NULL with g > 0,
+ * an item array NULL with n > 0, group_offsets[0] != 0, group_offsets[g] != n, offsets that do not ascend, and g == 0 with n > 0
+ * (g == 0 with n == 0: C_KZG_OK, nothing written); what the batch call refuses as a whole (no context, g2_values NULL) the same way;
+ * C_KZG_MALLOC / C_KZG_ERROR only when the device work itself fails. Synchronous. Per item the device does two scalar products and
+ * some Fr work, per group one 64-term commitment; the pairing check of each group runs on the host threads.
+ * Verify with lwkzg_verify_cell_kzg_proof_batch first; use this call when the answer must name the sidecar or the transaction, and
+ * lwkzg_verify_cell_kzg_proof_each only for single cells.
+ * Out of scope: a non-blocking (lwkzg_cell_verifier_*) form, lwkzg_multi_* forms, stream capture, and a pairing on the device (one
+ * lane's chain is about 90 ms; the host does a group's check in about 0.40 ms per thread). */
+C_KZG_RET lwkzg_verify_cell_kzg_proof_groups(uint8_t *ok_out, int32_t *rc_out, const Bytes48 *commitments, const uint64_t *cell_indices,
+                                             const Cell *cells, const Bytes48 *proofs, size_t n,
+                                             const uint64_t *group_offsets /* g + 1 */, size_t g, const KZGSettings *s);
+/* the same for item arrays already in HBM (device pointers, 16-byte aligned, produced on `stream`, NULL = already complete). The
+ * offsets stay a HOST array, read before the call returns. The commitments and the indices come down to be grouped; the cells never
+ * leave the device. */
+C_KZG_RET lwkzg_verify_cell_kzg_proof_groups_device(uint8_t *ok_out, int32_t *rc_out, const void *commitments48_dev,
+                                                    const void *cell_indices_dev, const void *cells_dev, const void *proofs48_dev, size_t n,
+                                                    const uint64_t *group_offsets /* HOST, g + 1 */, size_t g, const KZGSettings *s,
+                                                    void *stream);
+/* test hook: per group exactly what lwkzg_cell_verify_partials writes for the group alone (LWKZG_CELL_VERIFY_PARTIAL_BYTES each), by
+ * the grouped call's own code path up to the pairings; all zero for an empty group and for a group whose rc is not C_KZG_OK. Host
+ * arguments and return codes as lwkzg_verify_cell_kzg_proof_groups (out NULL with g > 0: C_KZG_BADARGS). */
+C_KZG_RET lwkzg_cell_verify_groups_partials(uint8_t *out /* g x LWKZG_CELL_VERIFY_PARTIAL_BYTES */, const Bytes48 *commitments,
+                                            const uint64_t *cell_indices, const Cell *cells, const Bytes48 *proofs, size_t n,
+                                            const uint64_t *group_offsets /* g + 1 */, size_t g, const KZGSettings *s);
+
 /* The engine behind the cell proofs of lwkzg_compute_cells_and_kzg_proofs* and lwkzg_recover_cells_and_kzg_proofs* (DESIGN.md section 4h),
  * a per-settings choice. FK20 (Feist-Khovratovich): the 128 proofs of a blob as a Toeplitz product over G1 -- 64 coefficient transforms,
  * 128 MSMs of 64 terms over a per-settings window table of 8192 transformed bases, and two 128-point transforms over G1 -- instead of 128

@@ -18,6 +18,7 @@ from .capi import (  # noqa: F401
     compute_cells_and_kzg_proofs, compute_cells_and_kzg_proofs_batch, compute_cells_and_kzg_proofs_batch_device,
     verify_cell_kzg_proof_batch, verify_cell_kzg_proof_batch_device, cell_verify_partials, cell_batch_challenge_host,
     verify_cell_kzg_proof_each, verify_cell_kzg_proof_each_device, cell_verify_each_points,
+    verify_cell_kzg_proof_groups, verify_cell_kzg_proof_groups_device, cell_verify_groups_partials,
     CellVerifier, CellVerifyResult, cell_verifier_host_steps, cell_group_device,
     recover_cells_and_kzg_proofs, recover_cells_and_kzg_proofs_batch, recover_cells_and_kzg_proofs_batch_device,
     recover_cells_and_kzg_proofs_mixed, recover_cells_and_kzg_proofs_mixed_device,

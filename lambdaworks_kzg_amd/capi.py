@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_verify_cell_kzg_proof_batch", "lwkzg_verify_cell_kzg_proof_batch_device", "lwkzg_cell_verify_partials",
     "lwkzg_cell_batch_challenge_host",
     "lwkzg_verify_cell_kzg_proof_each", "lwkzg_verify_cell_kzg_proof_each_device", "lwkzg_cell_verify_each_points",
+    "lwkzg_verify_cell_kzg_proof_groups", "lwkzg_verify_cell_kzg_proof_groups_device", "lwkzg_cell_verify_groups_partials",
     "lwkzg_recover_cells_and_kzg_proofs", "lwkzg_recover_cells_and_kzg_proofs_batch", "lwkzg_recover_cells_and_kzg_proofs_batch_device",
     "lwkzg_recover_cells_and_kzg_proofs_mixed", "lwkzg_recover_cells_and_kzg_proofs_mixed_device",
     "lwkzg_set_cell_proof_engine", "lwkzg_cell_proof_engine", "lwkzg_fk20_table_bytes", "lwkzg_fk20_chunk_blobs", "lwkzg_fk20_points",
@@ -156,6 +157,9 @@ def lib():
     l.lwkzg_verify_cell_kzg_proof_each.argtypes = [pu8, pi32, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ps]
     l.lwkzg_verify_cell_kzg_proof_each_device.argtypes = [pu8, pi32, vp, vp, vp, vp, sz, ps, vp]
     l.lwkzg_cell_verify_each_points.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_verify_cell_kzg_proof_groups.argtypes = [pu8, pi32, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, pu64, sz, ps]
+    l.lwkzg_verify_cell_kzg_proof_groups_device.argtypes = [pu8, pi32, vp, vp, vp, vp, sz, pu64, sz, ps, vp]
+    l.lwkzg_cell_verify_groups_partials.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, pu64, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, sz, ps, C.POINTER(sz)]
     l.lwkzg_recover_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, pu64, vp, sz, sz, ps, vp, vp]
@@ -934,6 +938,52 @@ def cell_verify_each_points(commitments, cell_indices, cells, proofs, ts):
     out = C.create_string_buffer(CELL_EACH_POINT_BYTES * max(n, 1))
     _check("lwkzg_cell_verify_each_points", lib().lwkzg_cell_verify_each_points(out, cm, idx, ce, pf, n, ts.ref()))
     return [out.raw[CELL_EACH_POINT_BYTES * i:CELL_EACH_POINT_BYTES * (i + 1)] for i in range(n)]
+
+
+def _group_offsets(sizes):
+    """the g + 1 offsets of groups of these sizes, as the C calls take them"""
+    off = [0]
+    for m in sizes:
+        off.append(off[-1] + m)
+    return (C.c_uint64 * len(off))(*off)
+
+
+def _cell_groups(groups):
+    """a list of item lists (an item: (commitment, cell index, cell, proof)) -> the C arguments of the grouped calls"""
+    items = [it for grp in groups for it in grp]
+    cm, idx, ce, pf, n = _cell_items([i[0] for i in items], [i[1] for i in items], [i[2] for i in items], [i[3] for i in items])
+    return cm, idx, ce, pf, n, _group_offsets([len(grp) for grp in groups]), len(groups)
+
+
+def verify_cell_kzg_proof_groups(groups, ts):
+    """one verify_cell_kzg_proof_batch answer per group in one call (lwkzg_verify_cell_kzg_proof_groups): groups is a list of item
+    lists, an item (commitment, cell index, cell, proof); returns a list of (rc, ok), group j exactly what the batch call on its
+    items alone answers. An empty group answers (C_KZG_OK, True)."""
+    cm, idx, ce, pf, n, off, g = _cell_groups(groups)
+    return _each("lwkzg_verify_cell_kzg_proof_groups", g,
+                 lambda ok, rc: lib().lwkzg_verify_cell_kzg_proof_groups(ok, rc, cm, idx, ce, pf, n, off, g, ts.ref()))
+
+
+def verify_cell_kzg_proof_groups_device(comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, group_sizes, ts, stream=None):
+    """the same on DEVICE pointers (48 n commitment bytes, n uint64 indices, 2048 n cell bytes, 48 n proof bytes, produced on
+    `stream`); group_sizes (a host list) cuts the n items into consecutive groups; the answers come to the host, the call is
+    synchronous"""
+    if sum(group_sizes) != n:
+        raise ValueError("group_sizes must add up to n")
+    off, g = _group_offsets(group_sizes), len(group_sizes)
+    return _each("lwkzg_verify_cell_kzg_proof_groups_device", g,
+                 lambda ok, rc: lib().lwkzg_verify_cell_kzg_proof_groups_device(ok, rc, comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n,
+                                                                                off, g, ts.ref(), stream))
+
+
+def cell_verify_groups_partials(groups, ts):
+    """per group what cell_verify_partials writes for the group alone (CELL_VERIFY_PARTIAL_BYTES each), by the grouped verdict call's
+    own code path up to the pairings; all zero for an empty group and for a group the call answers with an error code: a list of g
+    bytes objects"""
+    cm, idx, ce, pf, n, off, g = _cell_groups(groups)
+    out = C.create_string_buffer(CELL_VERIFY_PARTIAL_BYTES * max(g, 1))
+    _check("lwkzg_cell_verify_groups_partials", lib().lwkzg_cell_verify_groups_partials(out, cm, idx, ce, pf, n, off, g, ts.ref()))
+    return [out.raw[CELL_VERIFY_PARTIAL_BYTES * j:CELL_VERIFY_PARTIAL_BYTES * (j + 1)] for j in range(g)]
 
 
 def cell_batch_challenge_host(commitments, cell_indices, cells, proofs, mode):

@@ -177,9 +177,14 @@ void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, F
         hipLaunchKernelGGL(k_cellv_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pw, idx, tw_fwd, a_mont, sc_a, sc_b, (uint32_t)n,
                            skip);
     }
+    launch_cellv_row_weights(a_mont, perm_row, row_off, sc_c, m_dev ? n : m, st, m_dev, skip);
+}
+
+void launch_cellv_row_weights(const Fr *a_mont, const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t rows, hipStream_t st,
+                              const uint32_t *m_dev, const uint32_t *skip) {
+    if (rows == 0) return;
     ProfScope p("k_cellv_row_weights", st);
-    hipLaunchKernelGGL(k_cellv_row_weights, dim3((unsigned)(m_dev ? n : m)), dim3(64), 0, st, (const Fr *)a_mont, perm_row, row_off, sc_c, m_dev,
-                       skip);
+    hipLaunchKernelGGL(k_cellv_row_weights, dim3((unsigned)rows), dim3(64), 0, st, a_mont, perm_row, row_off, sc_c, m_dev, skip);
 }
 
 // ---- the fault words of an asynchronous verifier ------------------------------------------------------------------------------------

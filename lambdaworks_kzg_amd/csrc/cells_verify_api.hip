@@ -12,14 +12,12 @@
 //            variable-base sums (vmsm.hip); four points come down
 //   host     the pairing check against g2_values[64] (pairing.hip keeps its line table beside the others)
 #include "abi_guard.h"
+#include "cell_groups_plan.h"
 #include "cellv_bufs.h"
 #include "knobs.h"
 
 #include <string.h>
 
-#include <chrono>
-#include <string>
-#include <unordered_map>
 #include <vector>
 
 namespace lwk {
@@ -29,39 +27,7 @@ namespace {
 constexpr size_t kItemMsg = 16 + kCellBytes + 48;   // le64(row) | le64(k) | cell | proof
 constexpr size_t kPinTail = 33 * sizeof(Fr) + 3 * 96 + 3 * 4 + 48 + 12;   // powers up; three sums, their flags and RLI down
 
-// what the host derives from the commitments and the indices
-struct Grouping {
-    size_t m = 0;
-    std::vector<uint8_t> distinct;    // 48 m: the distinct commitments as given, in order of first occurrence
-    std::vector<uint32_t> rows;       // n
-    std::vector<uint32_t> perm_row, row_off, perm_col, col_off;   // n, m + 1, n, 129
-};
-
-bool group_items(Grouping &g, const uint8_t *comms, const uint64_t *idx, size_t n) {
-    for (size_t i = 0; i < n; i++)
-        if (idx[i] >= (uint64_t)kCellsPerBlob) return false;
-    g.rows.resize(n);
-    std::unordered_map<std::string, uint32_t> seen;
-    for (size_t i = 0; i < n; i++) {
-        auto it = seen.emplace(std::string((const char *)comms + 48 * i, 48), (uint32_t)g.m);
-        if (it.second) {
-            g.distinct.insert(g.distinct.end(), comms + 48 * i, comms + 48 * i + 48);
-            g.m++;
-        }
-        g.rows[i] = it.first->second;
-    }
-    auto sort_by = [n](std::vector<uint32_t> &perm, std::vector<uint32_t> &off, size_t groups, auto key) {
-        off.assign(groups + 1, 0);
-        for (size_t i = 0; i < n; i++) off[key(i) + 1]++;
-        for (size_t j = 0; j < groups; j++) off[j + 1] += off[j];
-        std::vector<uint32_t> at(off.begin(), off.end() - 1);
-        perm.resize(n);
-        for (size_t i = 0; i < n; i++) perm[at[key(i)]++] = (uint32_t)i;
-    };
-    sort_by(g.perm_row, g.row_off, g.m, [&](size_t i) { return (size_t)g.rows[i]; });
-    sort_by(g.perm_col, g.col_off, kCellsPerBlob, [&](size_t i) { return (size_t)idx[i]; });
-    return true;
-}
+static_assert(kPlanCellsPerBlob == (size_t)kCellsPerBlob, "cell_groups_plan.h groups by the cells of a blob");   // Grouping, group_items: there
 
 typedef CellvBufs Bufs;   // the device side of a batch, carved out of one allocation (cellv_bufs.h)
 
@@ -86,35 +52,6 @@ C_KZG_RET reserve(Ctx *c, size_t n, Bufs &b) {
     }
     cellv_carve(b, c->cellv.dev, c->cellv.cap);
     return C_KZG_OK;
-}
-
-struct PhaseClock {   // LWKZG_TIMING=1: device time between the phases' boundaries on the call's stream, host time beside it
-    static constexpr int kMarks = 7;
-    hipEvent_t ev[kMarks] = {};
-    bool on = false;
-    hipStream_t st = nullptr;
-    void begin(hipStream_t s) {
-        on = knobs().timing;
-        st = s;
-        if (!on) return;
-        for (auto &e : ev)
-            if (hipEventCreate(&e) != hipSuccess) on = false;
-    }
-    void mark(int k) {
-        if (on) hipEventRecord(ev[k], st);
-    }
-    float ms(int a, int b) {
-        float t = 0;
-        return on && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : -1.f;
-    }
-    ~PhaseClock() {
-        for (auto &e : ev)
-            if (e) hipEventDestroy(e);
-    }
-};
-
-double wall_ms(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
 }
 
 // r (canonical limbs), the three sums of vmsm.hip and the compressed RLI of a batch. Host pointers are uploaded into the context's

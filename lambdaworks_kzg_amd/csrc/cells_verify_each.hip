@@ -77,15 +77,8 @@ __global__ __launch_bounds__(64) void k_celleach_commit(const uint4 *__restrict_
     __syncthreads();   // buf is read; the tree may write over it
     const G1Affine q = setup[t];
     G1Xyzz acc = glv_mul_affine(q.x, q.y, beta, coef);
-    // the 64 partial points summed pairwise: lane t takes lane t + d at every level d = 1, 2, .. 32 where t is a multiple of 2 d. Two
-    // lanes may hold equal or opposite points, or the point at infinity: the complete addition
-#pragma unroll 1
-    for (uint32_t d = 1; d < (uint32_t)kCellElems; d <<= 1) {
-        if ((t & (2 * d - 1)) == d) sh[t] = acc;
-        __syncthreads();
-        if ((t & (2 * d - 1)) == 0) acc = xyzz_add(acc, sh[t + d]);
-        __syncthreads();
-    }
+    // the 64 partial points summed pairwise by the complete addition (cell_each.cuh)
+    cell_each_tree_sum(acc, sh, t);
     if (t == 0) isum[i] = acc;
 }
 

@@ -3,6 +3,9 @@
 #pragma once
 #include "carve.h"
 #include "cells_common.h"
+#include "knobs.h"
+
+#include <chrono>
 
 namespace lwk {
 
@@ -57,6 +60,36 @@ inline size_t cellv_carve(CellvBufs &b, uint8_t *base, size_t cap, bool staging 
     cv.take(b.pw, kCellvPwSlots * sizeof(Fr));
     cv.take(b.colcoef, (size_t)kCellsPerBlob * kCellElems * sizeof(Fr));
     return cv.bytes();
+}
+
+// ---- what the synchronous calls over these buffers share (cells_verify_api.hip, cells_verify_groups.hip) --------------------------------
+struct PhaseClock {   // LWKZG_TIMING=1: device time between the phases' boundaries on the call's stream, host time beside it
+    static constexpr int kMarks = 8;
+    hipEvent_t ev[kMarks] = {};
+    bool on = false;
+    hipStream_t st = nullptr;
+    void begin(hipStream_t s) {
+        on = knobs().timing;
+        st = s;
+        if (!on) return;
+        for (auto &e : ev)
+            if (hipEventCreate(&e) != hipSuccess) on = false;
+    }
+    void mark(int k) {
+        if (on) hipEventRecord(ev[k], st);
+    }
+    float ms(int a, int b) {
+        float t = 0;
+        return on && hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? t : -1.f;
+    }
+    ~PhaseClock() {
+        for (auto &e : ev)
+            if (e) hipEventDestroy(e);
+    }
+};
+
+inline double wall_ms(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double, std::milli>(b - a).count();
 }
 
 }  // namespace lwk

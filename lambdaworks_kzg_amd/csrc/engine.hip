@@ -287,6 +287,8 @@ void ctx_destroy(Ctx *c) {
     dev_free(c->recover_tab);
     grow_free(c->recover_sets);
     fk20_free(c);
+    grow_free(c->cellg);
+    if (c->cellg_pin) hipHostFree(c->cellg_pin);
     if (c->cellv_pin) hipHostFree(c->cellv_pin);
     if (c->cellv_ev) hipEventDestroy(c->cellv_ev);
     if (c->prio_copy) hipStreamDestroy(c->prio_copy);

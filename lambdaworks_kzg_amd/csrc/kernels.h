@@ -324,6 +324,9 @@ void launch_cellv_digests(const uint8_t *cells, const uint8_t *proofs48, const u
 void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b,
                           const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t n, size_t m, hipStream_t st,
                           const uint32_t *m_dev = nullptr, const uint32_t *skip = nullptr);
+// the weights alone, one workgroup per row of `rows` rows (the grouped call's concatenated rows: cells_verify_groups.hip)
+void launch_cellv_row_weights(const Fr *a_mont, const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t rows, hipStream_t st,
+                              const uint32_t *m_dev = nullptr, const uint32_t *skip = nullptr);
 // slot_raw: 4096 canonical scalars, the first 64 the coefficients of sum_i r^i I_i(X), the rest zero. perm_col / col_off (129 words): the
 // items by column; colcoef: 128 x 64 Fr of scratch. Under skip slot_raw is 4096 zero scalars (the MSM behind it takes no skip word)
 void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off, const Fr *tw_inv,
