@@ -671,7 +671,8 @@ C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *comm
  *                                FOR THE OLDEST. Context lock, two verifiers on two streams, lwkzg_reserve_streams first: as above.
  *   lwkzg_cell_verifier_pending / _wait / _free   as lwkzg_verifier_pending / _wait / _free; free_trusted_setup waits for the calls in
  *                                flight of the settings' cell verifiers too.
- * Not covered: host-pointer batches, the per-item form, stream capture. */
+ * Not covered: host-pointer batches, the per-item form, stream capture. The per-group form is lwkzg_cell_verifier_enqueue_groups
+ * below, which gives the fields of LwkzgCellVerifyResult meanings of its own. */
 typedef struct {
     int32_t  state;      /* 0 = pending, 1 = complete; written LAST, with release order */
     int32_t  rc;         /* the C_KZG_RET the synchronous device call would have returned */
@@ -705,6 +706,77 @@ C_KZG_RET lwkzg_cell_group_device(uint32_t *rows, uint32_t *m_out, uint8_t *dist
                                   uint32_t *row_off, uint32_t *perm_col, uint32_t *col_off, uint32_t *bad_index,
                                   const void *commitments48_dev, const void *cell_indices_dev, size_t n, uint64_t seed, uint32_t hash_mask,
                                   void *stream);
+
+/* PER-GROUP answers without a parked host thread: lwkzg_verify_cell_kzg_proof_groups_device (below) on a cell verifier (DESIGN.md
+ * section 4r). The commitments and the indices never come to the host: the groups' de-duplication, rows, lists and slices are made by
+ * kernels.
+ *   lwkzg_cell_verifier_new_groups  everything lwkzg_cell_verifier_new allocates, plus what a grouped call of up to max_cells items in up
+ *                                to max_groups groups needs (the segmented grouping's counters and lists, g power tables, the slice
+ *                                table, 16 MiB for the interpolants, LWKZG_VERIFIER_DEPTH copies of the offsets), and the settings'
+ *                                workspace for min(max_groups, 1024) MSM slots on both of the settings' contexts. The only call that
+ *                                may allocate or synchronise the device. C_KZG_BADARGS also for max_groups == 0 or above 2^30. The
+ *                                verifier takes lwkzg_cell_verifier_enqueue exactly as one from lwkzg_cell_verifier_new does; batch and
+ *                                grouped calls may alternate, share its ring and its depth and complete in order; pending / wait /
+ *                                free are unchanged, and free_trusted_setup waits for grouped calls in flight too. A verifier from
+ *                                lwkzg_cell_verifier_new has max_groups == 0 and refuses a grouped call on the spot.
+ *   lwkzg_cell_verifier_enqueue_groups  device item arrays (16-byte aligned, produced on `stream`; NULL = already complete) and HOST
+ *                                group_offsets (g + 1 values, read -- copied into storage of the call's own job slot -- before the call
+ *                                returns). For every j, (rc_out[j], ok_out[j]) is exactly what lwkzg_verify_cell_kzg_proof_groups_device
+ *                                writes for the same inputs, in every mode and on both MSM engines: its definition, its precedence
+ *                                inside a group, empty groups, and groups that do not spread to their neighbours. partials_out, if not
+ *                                NULL, takes exactly what lwkzg_cell_verify_groups_partials writes. Nothing behind r runs on a bad
+ *                                group's unvalidated points or unchecked indices. In *result:
+ *                                    rc         the call's return code: C_KZG_OK once every group is decided
+ *                                    ok         1 only if every group answered (C_KZG_OK, 1)
+ *                                    first_bad  the lowest GROUP whose answer is anything else, 0xffffffff when there is none
+ *                                    m          the total of the groups' distinct commitments
+ *                                    partials   zero
+ *                                ok_out, rc_out and partials_out (HOST arrays of g, g and g x LWKZG_CELL_VERIFY_PARTIAL_BYTES) are written
+ *                                before result->state, which is stored last with release order: they stay the caller's -- not to be
+ *                                read, reused or freed -- until it reads 1 there. The call returns once everything is enqueued: no wait
+ *                                for a stream or an event, no allocation. Completed on the spot, as the call's return value:
+ *                                C_KZG_BADARGS for group_offsets NULL, not starting at 0, not ending at n or not ascending, g == 0 with
+ *                                n > 0, an item array NULL with n > 0, ok_out or rc_out NULL with g > 0, n above max_cells, g above
+ *                                max_groups, a verifier from lwkzg_cell_verifier_new, and what lwkzg_cell_verifier_enqueue refuses
+ *                                (nothing but *result is written); C_KZG_OK with ok = 1 for g == 0 with n == 0 (nothing else written)
+ *                                and for n == 0 with g > 0 (every group is empty: (C_KZG_OK, 1) and zero partials for each, written
+ *                                before the call returns). A failing enqueue: C_KZG_ERROR, as lwkzg_cell_verifier_enqueue. The stream
+ *                                stands still while the host threads check the g pairings (about 0.4 ms per group and thread).
+ * Not covered: host-pointer inputs, lwkzg_multi_* forms, stream capture, a pairing on the device. */
+C_KZG_RET lwkzg_cell_verifier_new_groups(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_cells, size_t max_groups);
+C_KZG_RET lwkzg_cell_verifier_enqueue_groups(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, uint8_t *ok_out /* HOST, g */,
+                                             int32_t *rc_out /* HOST, g */,
+                                             uint8_t *partials_out /* HOST, g x LWKZG_CELL_VERIFY_PARTIAL_BYTES, or NULL */,
+                                             const void *commitments48_dev, const void *cell_indices_dev, const void *cells_dev,
+                                             const void *proofs48_dev, size_t n, const uint64_t *group_offsets /* HOST, g + 1 */, size_t g,
+                                             void *stream);
+/* Test hook: lwkzg_cell_group_device for a call of g groups -- the segmented grouping kernels alone on device inputs and HOST offsets
+ * (valid, n > 0, g > 0), every output brought to host arrays: rows n (GROUP-LOCAL; 0 for the items of a group with a bad index),
+ * *m_out (M, the total of the groups' distinct commitments), distinct48 48 n (the groups' distinct commitments one after the other in
+ * order of first occurrence, then infinity encodings), first_item n (M used), perm_row n / row_off n + 1 (M + 1 used) over the
+ * concatenated rows, perm_col n / col_off 128 g + 1 (list 128 j + k), row_base g + 1, bad_words g (non-zero: an index of the group is
+ * not below 128 -- it has no rows, columns or slices and its items are in no list). With slice_off_out (3 g + 1 words) and slices_out
+ * (4 words -- group, sum, first, count -- for each of 3 (n / 64 + g) slices) not NULL the slice table too, cut with the groups flagged
+ * by gflag (HOST, g words) or, where that is NULL, by the bad words. The order inside a list of perm_row / perm_col is not defined;
+ * places of the two that no item took read 0xffffffff. seed, hash_mask, return codes: as lwkzg_cell_group_device. */
+C_KZG_RET lwkzg_cell_group_segmented_device(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, uint32_t *first_item, uint32_t *perm_row,
+                                            uint32_t *row_off, uint32_t *perm_col, uint32_t *col_off, uint32_t *row_base, uint32_t *bad_words,
+                                            uint32_t *slices_out, uint32_t *slice_off_out, const uint32_t *gflag,
+                                            const void *commitments48_dev, const void *cell_indices_dev, size_t n,
+                                            const uint64_t *group_offsets /* HOST, g + 1 */, size_t g, uint64_t seed, uint32_t hash_mask,
+                                            void *stream);
+/* Host-only test hook: the two host steps of a grouped enqueue back to back on caller-supplied blocks, as
+ * lwkzg_cell_verifier_host_steps; no GPU, no context. The blocks are what the device sends down for a call of n items in g groups:
+ * group_offsets g + 1, row_base g + 1, bad_words g, status 2 n fault words ([i] item i's own, [n + q] concatenated row q's), first_item
+ * (row_base[g] words), digests32 32 n, distinct48 (48 row_base[g] bytes), sums3x97 g x 3 x 97 and rli48 g x 48 (group j's at j). Per
+ * group the answer into rc_out / ok_out and, where not NULL, partials_out; *out as lwkzg_cell_verifier_enqueue_groups completes it. A
+ * rejected or empty group reads nothing behind what decides it: with a bad word set neither status nor digests, with a fault word set
+ * neither digests nor sums; the blocks that only honest groups read may be NULL when there is none. */
+C_KZG_RET lwkzg_cell_verifier_groups_host_steps(LwkzgCellVerifyResult *out, uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_out,
+                                                const uint64_t *group_offsets, size_t g, size_t n, const uint32_t *row_base,
+                                                const uint32_t *bad_words, const int32_t *status, const uint32_t *first_item,
+                                                const uint8_t *digests32, const uint8_t *distinct48, const uint8_t *sums3x97,
+                                                const uint8_t *rli48, const KZGSettings *s, int mode);
 
 /* Per-item cell verification: n independent lwkzg_verify_cell_kzg_proof_batch calls of ONE item each, in one. For every i, ok_out[i]
  * (0/1) and rc_out[i] (a C_KZG_RET) are exactly the (*ok, return code) of the batch call on item i alone, in the mode the settings
@@ -756,8 +828,9 @@ C_KZG_RET lwkzg_cell_verify_each_points(uint8_t *out /* n x 97 */, const Bytes48
  * some Fr work, per group one 64-term commitment; the pairing check of each group runs on the host threads.
  * Verify with lwkzg_verify_cell_kzg_proof_batch first; use this call when the answer must name the sidecar or the transaction, and
  * lwkzg_verify_cell_kzg_proof_each only for single cells.
- * Out of scope: a non-blocking (lwkzg_cell_verifier_*) form, lwkzg_multi_* forms, stream capture, and a pairing on the device (one
- * lane's chain is about 90 ms; the host does a group's check in about 0.40 ms per thread). */
+ * The form that does not block is lwkzg_cell_verifier_enqueue_groups above.
+ * Out of scope: lwkzg_multi_* forms, stream capture, and a pairing on the device (one lane's chain is about 90 ms; the host does a
+ * group's check in about 0.40 ms per thread). */
 C_KZG_RET lwkzg_verify_cell_kzg_proof_groups(uint8_t *ok_out, int32_t *rc_out, const Bytes48 *commitments, const uint64_t *cell_indices,
                                              const Cell *cells, const Bytes48 *proofs, size_t n,
                                              const uint64_t *group_offsets /* g + 1 */, size_t g, const KZGSettings *s);

@@ -20,6 +20,7 @@ from .capi import (  # noqa: F401
     verify_cell_kzg_proof_each, verify_cell_kzg_proof_each_device, cell_verify_each_points,
     verify_cell_kzg_proof_groups, verify_cell_kzg_proof_groups_device, cell_verify_groups_partials,
     CellVerifier, CellVerifyResult, cell_verifier_host_steps, cell_group_device,
+    GroupedCellAnswers, cell_group_segmented_device, cell_verifier_groups_host_steps,
     recover_cells_and_kzg_proofs, recover_cells_and_kzg_proofs_batch, recover_cells_and_kzg_proofs_batch_device,
     recover_cells_and_kzg_proofs_mixed, recover_cells_and_kzg_proofs_mixed_device,
     CELL_PROOFS_FK20, CELL_PROOFS_MSM, fk20_chunk_blobs,

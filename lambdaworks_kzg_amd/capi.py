@@ -95,6 +95,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_verifier_host_steps",
     "lwkzg_cell_verifier_new", "lwkzg_cell_verifier_enqueue", "lwkzg_cell_verifier_pending", "lwkzg_cell_verifier_wait",
     "lwkzg_cell_verifier_free", "lwkzg_cell_verifier_host_steps", "lwkzg_cell_group_device",
+    "lwkzg_cell_verifier_new_groups", "lwkzg_cell_verifier_enqueue_groups", "lwkzg_cell_group_segmented_device",
+    "lwkzg_cell_verifier_groups_host_steps",
     "lwkzg_verify_kzg_proof_batch", "lwkzg_verify_kzg_proof_batch_device", "lwkzg_verify_kzg_proof_batch_partial",
     "lwkzg_verifier_enqueue_openings", "lwkzg_verify_kzg_proof_each_device",
 ]
@@ -202,6 +204,12 @@ def lib():
     l.lwkzg_cell_verifier_host_steps.argtypes = [C.POINTER(CellVerifyResult), C.c_char_p, sz, C.c_char_p, sz, C.c_uint32, pi32, pu32,
                                                  C.c_char_p, C.c_char_p, ps, ci]
     l.lwkzg_cell_group_device.argtypes = [pu32, pu32, C.c_char_p, pu32, pu32, pu32, pu32, pu32, pu32, vp, vp, sz, C.c_uint64, C.c_uint32, vp]
+    l.lwkzg_cell_verifier_new_groups.argtypes = [C.POINTER(vp), ps, sz, sz]
+    l.lwkzg_cell_verifier_enqueue_groups.argtypes = [vp, C.POINTER(CellVerifyResult), pu8, pi32, C.c_char_p, vp, vp, vp, vp, sz, pu64, sz, vp]
+    l.lwkzg_cell_group_segmented_device.argtypes = [pu32, pu32, C.c_char_p, pu32, pu32, pu32, pu32, pu32, pu32, pu32, pu32, pu32, pu32, vp, vp,
+                                                    sz, pu64, sz, C.c_uint64, C.c_uint32, vp]
+    l.lwkzg_cell_verifier_groups_host_steps.argtypes = [C.POINTER(CellVerifyResult), pu8, pi32, C.c_char_p, pu64, sz, sz, pu32, pu32, pi32,
+                                                        pu32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, ps, C.c_int]
     l.lwkzg_release_context.argtypes = [ps]
     l.lwkzg_reserve.argtypes = [ps, sz]
     l.lwkzg_reserve_streams.argtypes = [ps, sz, ci]
@@ -1063,8 +1071,9 @@ class _AsyncVerifier:
     def _fn(self, name):
         return getattr(lib(), self._PREFIX + name)
 
-    def _enqueue(self, *args, call="enqueue"):
+    def _enqueue(self, *args, call="enqueue", keep=None):
         res = self._RESULT()
+        res._keep = keep   # what else the call writes lives as long as its result
         self._results = [r for r in self._results if r.state != 1][-4 * VERIFIER_DEPTH:] + [res]
         rc = self._fn(call)(self.h, C.byref(res), *args)
         if rc != C_KZG_OK:
@@ -1124,12 +1133,49 @@ class CellVerifier(_AsyncVerifier):
     out alive."""
     _PREFIX, _RESULT = "lwkzg_cell_verifier_", CellVerifyResult
 
-    def __init__(self, ts, max_cells):
-        super().__init__(ts, max_cells)
+    def __init__(self, ts, max_cells, max_groups=0):
+        """max_groups > 0: lwkzg_cell_verifier_new_groups -- the verifier also takes enqueue_groups"""
+        if not max_groups:
+            super().__init__(ts, max_cells)
+            return
+        self.ts = ts
+        self.h = C.c_void_p()
+        self._results = []
+        _check(self._PREFIX + "new_groups", self._fn("new_groups")(C.byref(self.h), ts.ref(), max_cells, max_groups))
 
     def enqueue(self, comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream=None):
         """returns at once; raises KzgError (its .result is the completed CellVerifyResult) for what the call itself refuses"""
         return self._enqueue(comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream)
+
+    def enqueue_groups(self, comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, group_sizes, stream=None, partials=True):
+        """one answer per group (lwkzg_cell_verifier_enqueue_groups): group_sizes (a host list) cuts the n device-resident items into
+        consecutive groups. Returns at once with a GroupedCellAnswers, whose arrays stay the library's until its result.state reads 1;
+        raises KzgError (its .result is the completed CellVerifyResult) for what the call itself refuses"""
+        ans = GroupedCellAnswers(len(group_sizes), partials)
+        off = _group_offsets(group_sizes)
+        ans.result = self._enqueue(ans._ok, ans._rc, ans._partials, comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, off, len(group_sizes),
+                                   stream, call="enqueue_groups", keep=ans)
+        return ans
+
+
+class GroupedCellAnswers:
+    """where CellVerifier.enqueue_groups answers: result (a CellVerifyResult) and, once result.state == 1, answers() / partials()"""
+
+    def __init__(self, g, partials=True):
+        self.g = g
+        self._ok, self._rc = (C.c_uint8 * max(g, 1))(*([0xee] * max(g, 1))), (C.c_int32 * max(g, 1))(*([-1] * max(g, 1)))
+        self._partials = C.create_string_buffer(b"\xee" * (CELL_VERIFY_PARTIAL_BYTES * max(g, 1))) if partials else None
+        self.result = None
+
+    def answers(self):
+        """[(rc, ok)] per group, as verify_cell_kzg_proof_groups returns them"""
+        assert self.result is not None and self.result.state == 1
+        return [(self._rc[j], bool(self._ok[j])) for j in range(self.g)]
+
+    def partials(self):
+        assert self.result is not None and self.result.state == 1 and self._partials is not None
+        raw = self._partials.raw
+        return [raw[CELL_VERIFY_PARTIAL_BYTES * j:CELL_VERIFY_PARTIAL_BYTES * (j + 1)] for j in range(self.g)]
 
 
 def cell_verifier_host_steps(distinct48, m, digests32, n, bad_index, status, first_item, sums3x97, rli48, settings_ref, mode):
@@ -1157,6 +1203,47 @@ def cell_group_device(comm_ptr, indices_ptr, n, seed, hash_mask=0xffffffff, stre
                                          indices_ptr, n, seed, hash_mask, stream))
     return {"rows": list(rows), "m": m.value, "distinct": distinct.raw, "first_item": list(first)[:m.value], "perm_row": list(perm_row),
             "row_off": list(row_off)[:m.value + 1], "perm_col": list(perm_col), "col_off": list(col_off), "bad_index": bad.value}
+
+
+def cell_group_segmented_device(comm_ptr, indices_ptr, n, group_sizes, seed, hash_mask=0xffffffff, stream=None, gflag=None, slices=True):
+    """test hook: the segmented grouping kernels of a grouped cell verifier on DEVICE inputs, and the slice table cut with the groups
+    flagged by gflag (a list of g words; None: the groups with a bad index). Returns a dict: rows (group-local), m (the total), distinct
+    (48 n bytes), first_item (m), perm_row, row_off (m + 1), perm_col, col_off (128 g + 1), row_base (g + 1), bad_words (g), slice_off
+    (3 g + 1), slices ((group, sum, first, count) each). The order inside a list of perm_row / perm_col is not defined."""
+    u32, g = C.c_uint32, len(group_sizes)
+    rows, first, perm_row, row_off, perm_col = (u32 * n)(), (u32 * n)(), (u32 * n)(), (u32 * (n + 1))(), (u32 * n)()
+    col_off, row_base, bad, m = (u32 * (128 * g + 1))(), (u32 * (g + 1))(), (u32 * max(g, 1))(), u32(0)
+    max_slices = 3 * (n // 64 + g)
+    sl, sl_off = ((u32 * (4 * max_slices))(), (u32 * (3 * g + 1))()) if slices else (None, None)
+    flags = (u32 * g)(*gflag) if gflag is not None else None
+    distinct = C.create_string_buffer(48 * max(n, 1))
+    _check("lwkzg_cell_group_segmented_device",
+           lib().lwkzg_cell_group_segmented_device(rows, C.byref(m), distinct, first, perm_row, row_off, perm_col, col_off, row_base, bad, sl,
+                                                   sl_off, flags, comm_ptr, indices_ptr, n, _group_offsets(group_sizes), g, seed, hash_mask,
+                                                   stream))
+    out = {"rows": list(rows), "m": m.value, "distinct": distinct.raw[:48 * n], "first_item": list(first)[:m.value],
+           "perm_row": list(perm_row), "row_off": list(row_off)[:m.value + 1], "perm_col": list(perm_col), "col_off": list(col_off),
+           "row_base": list(row_base), "bad_words": list(bad)[:g]}
+    if slices:
+        out["slice_off"] = list(sl_off)
+        out["slices"] = [tuple(sl[4 * k:4 * k + 4]) for k in range(sl_off[3 * g])]
+    return out
+
+
+def cell_verifier_groups_host_steps(group_sizes, row_base, bad_words, status, first_item, digests32, distinct48, sums3x97, rli48,
+                                    settings_ref, mode, partials=True):
+    """test hook (host only): the two host steps of CellVerifier.enqueue_groups on caller-supplied blocks (None where a block is not to
+    be read). Returns (the completed CellVerifyResult, [(rc, ok)] per group, the partials per group or None)"""
+    g, n = len(group_sizes), sum(group_sizes)
+    res, ans = CellVerifyResult(), GroupedCellAnswers(g, partials)
+    st = (C.c_int32 * len(status))(*status) if status is not None else None
+    fi = (C.c_uint32 * max(len(first_item), 1))(*first_item) if first_item is not None else None
+    _check("lwkzg_cell_verifier_groups_host_steps",
+           lib().lwkzg_cell_verifier_groups_host_steps(C.byref(res), ans._ok, ans._rc, ans._partials, _group_offsets(group_sizes), g, n,
+                                                       (C.c_uint32 * (g + 1))(*row_base), (C.c_uint32 * g)(*bad_words), st, fi, digests32,
+                                                       distinct48, sums3x97, rli48, settings_ref, mode))
+    ans.result = res
+    return res, ans.answers(), ans.partials() if partials else None
 
 
 def verify_shards_finish(partials, n_shards, n_total, ts):

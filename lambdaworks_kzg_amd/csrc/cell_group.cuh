@@ -77,6 +77,13 @@ LWK_GROUP_HD uint32_t group_slot_hash(const uint64_t w[6], uint64_t seed, uint32
     return (uint32_t)(h ^ (h >> 32)) & hash_mask;
 }
 
+// the slot hash of a SEGMENTED grouping (a call of g groups: the key is (group, 48 bytes)): the same keyed hash
+// with the group mixed into both halves of the key, so that one commitment in two groups starts two unrelated probe chains
+LWK_GROUP_HD uint32_t group_slot_hash_seg(const uint64_t w[6], uint32_t group, uint64_t seed, uint32_t hash_mask) {
+    const uint64_t g = ((uint64_t)group + 1) * 0xd6e8feb86659fd93ull;
+    return group_slot_hash(w, seed ^ g ^ (g >> 29), hash_mask);
+}
+
 LWK_GROUP_HD bool group_equal48(const uint64_t a[6], const uint8_t *other48) {
     const uint64_t *p = (const uint64_t *)other48;
     uint64_t d = 0;

@@ -18,9 +18,12 @@
 //                     The order inside a group is whatever the atomics gave: every consumer sums field elements exactly.
 // An index >= 128 is never a bin or a subscript here: such an item is left out of the column list, and the verifier's skip word keeps
 // everything that reads idx[] as a subscript from running.
+// The second half of the file is the same for a call of g groups (k_seg_*: the segmented grouping and the slice table of a cell
+// verifier's grouped calls; lwkzg_cell_group_segmented_device is its test hook).
 #include "abi_guard.h"
 #include "carve.h"
 #include "cell_group.cuh"
+#include "cell_groups_plan.h"
 #include "kernels.h"
 
 #include <vector>
@@ -233,6 +236,274 @@ void launch_cell_group(const uint8_t *comms48, const uint64_t *idx, size_t n, si
                        (const uint32_t *)g.col_off, g.row_cnt, g.col_cnt, g.perm_row, g.perm_col, n32);
 }
 
+// ---- the segmented grouping: a call of g groups ---------------------------------------------------------------------
+// What plan_groups (cell_groups_plan.h) makes on the host, for a verifier that never brings the commitments down. The key of an item is
+// (its group, its 48 bytes): the same commitment in two groups is two rows. Groups are contiguous item ranges, so ONE scan of the
+// first-occurrence flags over all items in index order numbers the CONCATENATED rows directly, and a group's rows start at the count of
+// flags in front of its first item.
+//   k_seg_mark        one lane per item: its group (a binary search of the offsets), and the group's bad word where its index is >= 128
+//   k_seg_insert      k_group_insert with the group in the slot hash and in the equality test. Whether the item found in a slot is of
+//                     the same group is read off the OFFSETS (immutable), not off another lane's store. The items of a group with a
+//                     bad word take no slot.
+//   k_seg_scan        one workgroup: the flags' exclusive scan pre[i] (pre[n] = M); a first occurrence writes slot_row, first_item, distinct
+//   k_seg_rows        the concatenated row of every item (kept in slot_of), its group-local row, both histograms (in HBM: the bins are
+//                     (group, column) pairs), row_base[j] = pre[item_off[j]] -- right for an empty group and for groups at the very
+//                     end, whose offset is n -- and the infinity encodings behind the M-th distinct commitment
+//   k_seg_offsets     two workgroups: the exclusive scans row_off[M + 1] and col_off[128 g + 1]
+//   k_seg_scatter     perm_row / perm_col, places counted down from the counters as in k_group_scatter
+// An index >= 128 is never a bin or a subscript: its whole group has no slot, row, column or place in a list.
+namespace {
+
+// the group of item i: item_off[j] <= i < item_off[j + 1] (offsets valid, i < n: item_off[0] = 0 <= i < n = item_off[g])
+__device__ __forceinline__ uint32_t seg_group_of(const uint32_t *__restrict__ item_off, uint32_t g, uint32_t i) {
+    uint32_t lo = 0, hi = g;
+#pragma unroll 1
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (item_off[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kGroupLanes) void k_seg_mark(const uint64_t *__restrict__ idx, const uint32_t *__restrict__ item_off,
+                                                          uint32_t *__restrict__ item_group, uint32_t *__restrict__ gbad, uint32_t n,
+                                                          uint32_t g) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = seg_group_of(item_off, g, i);
+    item_group[i] = j;
+    if (idx[i] >= (uint64_t)kGroupColumns) atomicOr(&gbad[j], 1u);
+}
+
+__global__ __launch_bounds__(kGroupLanes) void k_seg_insert(const uint8_t *__restrict__ comms, const uint32_t *__restrict__ item_off,
+                                                            const uint32_t *__restrict__ item_group, const uint32_t *__restrict__ gbad,
+                                                            uint32_t *__restrict__ table, uint32_t *__restrict__ slot_of,
+                                                            uint32_t *__restrict__ head, uint32_t n, uint32_t slot_mask, uint64_t seed,
+                                                            uint32_t hash_mask) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = item_group[i];
+    if (gbad[j]) {   // (k_seg_mark is complete: the word is final)
+        slot_of[i] = kGroupEmpty;
+        return;
+    }
+    const uint32_t lo = item_off[j], hi = item_off[j + 1];
+    uint64_t key[6];
+    group_load48(key, comms + 48 * (size_t)i);
+    uint32_t s = group_slot_hash_seg(key, j, seed, hash_mask) & slot_mask;
+    uint32_t found = kGroupEmpty;
+#pragma unroll 1
+    for (uint32_t probe = 0; probe <= slot_mask; probe++, s = (s + 1) & slot_mask) {
+        const uint32_t c = atomicCAS(&table[s], kGroupEmpty, i);
+        if (c == kGroupEmpty) {   // claimed
+            found = s;
+            break;
+        }
+        if (c >= n) break;        // (no lane writes such a word: the table is not this launch's)
+        if (c >= lo && c < hi && group_equal48(key, comms + 48 * (size_t)c)) {
+            atomicMin(&table[s], i);
+            found = s;
+            break;
+        }
+    }
+    if (found == kGroupEmpty) atomicOr(&head[kGroupHeadErr], 1u);   // (the item is in no row; host function 1 fails the call)
+    slot_of[i] = found;
+}
+
+__global__ __launch_bounds__(kScanLanes) void k_seg_scan(const uint8_t *__restrict__ comms, const uint32_t *__restrict__ table,
+                                                         const uint32_t *__restrict__ slot_of, uint32_t *__restrict__ slot_row,
+                                                         uint32_t *__restrict__ first_item, uint8_t *__restrict__ distinct,
+                                                         uint32_t *__restrict__ pre, uint32_t *__restrict__ head, uint32_t n) {
+    __shared__ uint32_t wave_tot[kScanWaves];
+    uint32_t run = 0;
+#pragma unroll 1
+    for (uint32_t base = 0; base < n; base += kScanLanes) {   // (n is the same for every lane: they all meet the barriers)
+        const uint32_t i = base + threadIdx.x;
+        uint32_t s = kGroupEmpty, flag = 0;
+        if (i < n) {
+            s = slot_of[i];
+            flag = s != kGroupEmpty && table[s] == i ? 1u : 0u;
+        }
+        uint32_t total;
+        const uint32_t before = block_exclusive_scan(flag, wave_tot, &total);
+        if (i < n) pre[i] = run + before;
+        if (flag) {
+            const uint32_t row = run + before;   // < n: at most one flag per item
+            slot_row[s] = row;
+            first_item[row] = i;
+            const uint64_t *src = (const uint64_t *)(comms + 48 * (size_t)i);
+            uint64_t *dst = (uint64_t *)(distinct + 48 * (size_t)row);
+#pragma unroll
+            for (int k = 0; k < 6; k++) dst[k] = src[k];
+        }
+        run += total;
+    }
+    if (threadIdx.x == 0) head[kGroupHeadM] = pre[n] = run;
+}
+
+// lanes 0 .. max(n, g + 1) - 1
+__global__ __launch_bounds__(kGroupLanes) void k_seg_rows(const uint64_t *__restrict__ idx, const uint32_t *__restrict__ item_off,
+                                                          const uint32_t *__restrict__ item_group, uint32_t *__restrict__ slot_of,
+                                                          const uint32_t *__restrict__ slot_row, const uint32_t *__restrict__ pre,
+                                                          uint32_t *__restrict__ rows, uint32_t *__restrict__ row_base,
+                                                          uint32_t *__restrict__ row_cnt, uint32_t *__restrict__ col_cnt,
+                                                          uint8_t *__restrict__ distinct, uint32_t *__restrict__ head, uint32_t n, uint32_t g) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= g) {
+        const uint32_t at = item_off[i];
+        row_base[i] = pre[at <= n ? at : n];
+    }
+    if (i >= n) return;
+    const uint32_t s = slot_of[i];
+    uint32_t crow = kGroupEmpty, local = 0;
+    if (s != kGroupEmpty) {
+        const uint32_t j = item_group[i], first = pre[item_off[j]];
+        crow = slot_row[s];
+        if (crow >= n || crow < first) {   // only behind a failed insertion elsewhere: keep every subscript in range, report
+            atomicOr(&head[kGroupHeadErr], 2u);
+            crow = kGroupEmpty;
+        } else {
+            local = crow - first;
+            atomicAdd(&row_cnt[crow], 1u);
+            const uint64_t k = idx[i];
+            if (k < (uint64_t)kGroupColumns) atomicAdd(&col_cnt[(size_t)kGroupColumns * j + (uint32_t)k], 1u);
+        }
+    }
+    slot_of[i] = crow;   // from here on the item's CONCATENATED row (only lane i reads slot_of[i] in this launch)
+    rows[i] = local;
+    if (i >= head[kGroupHeadM]) {   // the padding the two-set launches take: infinity
+        uint64_t *dst = (uint64_t *)(distinct + 48 * (size_t)i);
+        dst[0] = 0xc0ull;   // (little-endian: byte 0)
+#pragma unroll
+        for (int q = 1; q < 6; q++) dst[q] = 0;
+    }
+}
+
+// workgroup 0: row_off[0 .. M] from row_cnt; workgroup 1: col_off[0 .. cols] from col_cnt (cols = 128 g)
+__global__ __launch_bounds__(kScanLanes) void k_seg_offsets(const uint32_t *__restrict__ row_cnt, const uint32_t *__restrict__ col_cnt,
+                                                            uint32_t *__restrict__ row_off, uint32_t *__restrict__ col_off,
+                                                            const uint32_t *__restrict__ head, uint32_t n, uint32_t cols) {
+    __shared__ uint32_t wave_tot[kScanWaves];
+    const bool by_col = blockIdx.x != 0;
+    const uint32_t *cnt = by_col ? col_cnt : row_cnt;
+    uint32_t *off = by_col ? col_off : row_off;
+    uint32_t len = by_col ? cols : head[kGroupHeadM];
+    if (len > n && !by_col) len = n;
+    uint32_t run = 0;
+#pragma unroll 1
+    for (uint32_t base = 0; base < len; base += kScanLanes) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < len ? cnt[i] : 0u;
+        uint32_t total;
+        const uint32_t before = block_exclusive_scan(v, wave_tot, &total);
+        if (i < len) off[i] = run + before;
+        run += total;
+    }
+    if (threadIdx.x == 0) off[len] = run;
+}
+
+__global__ __launch_bounds__(kGroupLanes) void k_seg_scatter(const uint64_t *__restrict__ idx, const uint32_t *__restrict__ item_group,
+                                                             const uint32_t *__restrict__ crow_of, const uint32_t *__restrict__ row_off,
+                                                             const uint32_t *__restrict__ col_off, uint32_t *__restrict__ row_cnt,
+                                                             uint32_t *__restrict__ col_cnt, uint32_t *__restrict__ perm_row,
+                                                             uint32_t *__restrict__ perm_col, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t crow = crow_of[i];
+    if (crow >= n) return;   // an item of a group with a bad word (or behind a failed insertion): in neither list
+    uint32_t at = row_off[crow] + atomicSub(&row_cnt[crow], 1u) - 1u;
+    if (at < n) perm_row[at] = i;
+    const uint64_t k = idx[i];
+    if (k >= (uint64_t)kGroupColumns) return;
+    const size_t bin = (size_t)kGroupColumns * item_group[i] + (uint32_t)k;
+    at = col_off[bin] + atomicSub(&col_cnt[bin], 1u) - 1u;
+    if (at < n) perm_col[at] = i;
+}
+
+// ---- the slice table of a call of g groups, on the device -------------------------------------------------------------------------------------
+// One workgroup over the 3 g sums in order: sum 3 j + s of a group without a flag has plan_slice_count(terms) slices -- terms the
+// group's items (s < 2) or its distinct commitments (s == 2) -- an exclusive scan of the counts is slice_off, and the sum's lane writes
+// its slices by plan_slice: the rule plan_groups cuts by (cell_groups_plan.h). A flagged group has none. slice_off[3 g]: the live count.
+__global__ __launch_bounds__(kScanLanes) void k_seg_slice_table(const uint32_t *__restrict__ item_off, const uint32_t *__restrict__ row_base,
+                                                                const uint32_t *__restrict__ gflag, GroupSlice *__restrict__ slices,
+                                                                uint32_t *__restrict__ slice_off, uint32_t sums, uint32_t max_slices) {
+    __shared__ uint32_t wave_tot[kScanWaves];
+    uint32_t run = 0;
+#pragma unroll 1
+    for (uint32_t base = 0; base < sums; base += kScanLanes) {
+        const uint32_t q = base + threadIdx.x, j = q / 3, s = q - 3 * j;
+        uint32_t first = 0, terms = 0;
+        if (q < sums && !gflag[j]) {
+            const uint32_t *off = s < 2 ? item_off : row_base;
+            first = off[j];
+            terms = off[j + 1] - first;
+        }
+        const uint32_t cnt = plan_slice_count(terms);
+        uint32_t total;
+        const uint32_t before = block_exclusive_scan(cnt, wave_tot, &total);
+        if (q < sums) {
+            slice_off[q] = run + before;
+#pragma unroll 1
+            for (uint32_t k = 0; k < cnt; k++) {
+                const uint32_t at = run + before + k;
+                if (at < max_slices) slices[at] = plan_slice(j, s, first, terms, k);
+            }
+        }
+        run += total;
+    }
+    if (threadIdx.x == 0) slice_off[sums] = run < max_slices ? run : max_slices;
+}
+
+void launch_cell_group_seg(const uint8_t *comms48, const uint64_t *idx, size_t n, size_t g, size_t slots, uint64_t seed, uint32_t hash_mask,
+                           const CellGroupSegBufs &s, hipStream_t st) {
+    const uint32_t n32 = (uint32_t)n, g32 = (uint32_t)g;
+    const dim3 per_item((unsigned)((n + kGroupLanes - 1) / kGroupLanes));
+    const size_t lanes = n > g + 1 ? n : g + 1;
+    hipMemsetAsync(s.table, 0xff, slots * 4, st);
+    hipMemsetAsync(s.row_cnt, 0, n * 4, st);
+    hipMemsetAsync(s.head, 0, (kGroupHeadWords + kGroupColumns * g) * 4, st);   // (col_cnt behind it: one piece)
+    hipMemsetAsync(s.gbad, 0, g * 4, st);
+    {
+        ProfScope p("k_seg_mark", st);
+        hipLaunchKernelGGL(k_seg_mark, per_item, dim3(kGroupLanes), 0, st, idx, (const uint32_t *)s.item_off, s.item_group, s.gbad, n32, g32);
+    }
+    {
+        ProfScope p("k_seg_insert", st);
+        hipLaunchKernelGGL(k_seg_insert, per_item, dim3(kGroupLanes), 0, st, comms48, (const uint32_t *)s.item_off,
+                           (const uint32_t *)s.item_group, (const uint32_t *)s.gbad, s.table, s.slot_of, s.head, n32, (uint32_t)(slots - 1), seed,
+                           hash_mask);
+    }
+    {
+        ProfScope p("k_seg_scan", st);
+        hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(kScanLanes), 0, st, comms48, (const uint32_t *)s.table, (const uint32_t *)s.slot_of,
+                           s.slot_row, s.first_item, s.distinct, s.pre, s.head, n32);
+    }
+    {
+        ProfScope p("k_seg_rows", st);
+        hipLaunchKernelGGL(k_seg_rows, dim3((unsigned)((lanes + kGroupLanes - 1) / kGroupLanes)), dim3(kGroupLanes), 0, st, idx,
+                           (const uint32_t *)s.item_off, (const uint32_t *)s.item_group, s.slot_of, (const uint32_t *)s.slot_row,
+                           (const uint32_t *)s.pre, s.rows, s.row_base, s.row_cnt, s.col_cnt, s.distinct, s.head, n32, g32);
+    }
+    {
+        ProfScope p("k_seg_offsets", st);
+        hipLaunchKernelGGL(k_seg_offsets, dim3(2), dim3(kScanLanes), 0, st, (const uint32_t *)s.row_cnt, (const uint32_t *)s.col_cnt, s.row_off,
+                           s.col_off, (const uint32_t *)s.head, n32, (uint32_t)(kGroupColumns * g));
+    }
+    ProfScope p("k_seg_scatter", st);
+    hipLaunchKernelGGL(k_seg_scatter, per_item, dim3(kGroupLanes), 0, st, idx, (const uint32_t *)s.item_group, (const uint32_t *)s.slot_of,
+                       (const uint32_t *)s.row_off, (const uint32_t *)s.col_off, s.row_cnt, s.col_cnt, s.perm_row, s.perm_col, n32);
+}
+
+void launch_cell_group_slice_table(const uint32_t *item_off, const uint32_t *row_base, const uint32_t *gflag, GroupSlice *slices,
+                                   uint32_t *slice_off, size_t g, size_t max_slices, hipStream_t st) {
+    ProfScope p("k_seg_slice_table", st);
+    hipLaunchKernelGGL(k_seg_slice_table, dim3(1), dim3(kScanLanes), 0, st, item_off, row_base, gflag, slices, slice_off, (uint32_t)(3 * g),
+                       (uint32_t)max_slices);
+}
+
 namespace {
 
 size_t hook_carve(CellGroupBufs &g, uint8_t *base, size_t n, size_t slots) {
@@ -287,11 +558,91 @@ C_KZG_RET cell_group_hook(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, 
     return C_KZG_OK;
 }
 
+struct SegHookOut {
+    uint32_t *rows, *m_out, *first_item, *perm_row, *row_off, *perm_col, *col_off, *row_base, *bad_words, *slices, *slice_off;
+    uint8_t *distinct48;
+};
+
+C_KZG_RET cell_group_seg_hook(const SegHookOut &o, const uint32_t *gflag, const uint8_t *comms, const uint64_t *idx, size_t n,
+                              const uint64_t *offsets, size_t g, uint64_t seed, uint32_t hash_mask, hipStream_t st) {
+    if (n == 0 || g == 0 || n >= 0x7fffffffu || g > 0x40000000u || !o.rows || !o.m_out || !o.distinct48 || !o.first_item || !o.perm_row ||
+        !o.row_off || !o.perm_col || !o.col_off || !o.row_base || !o.bad_words || !comms || !idx || !group_offsets_valid(offsets, g, n) ||
+        (o.slices != nullptr) != (o.slice_off != nullptr))
+        return C_KZG_BADARGS;
+    const size_t slots = group_table_slots(n), max_slices = plan_max_slices(n, g);
+    CellGroupBufs gb;
+    CellGroupSegBufs sb;
+    uint32_t *d_gflag, *d_slice_off;
+    GroupSlice *d_slices;
+    auto carve = [&](uint8_t *base) {
+        const size_t used = hook_carve(gb, base, n, slots);
+        Carver cv(base ? base + used : nullptr);
+        cell_group_seg_carve(sb, gb, cv, n, g);
+        cv.take(d_gflag, g * 4);
+        cv.take(d_slice_off, (3 * g + 1) * 4);
+        cv.take(d_slices, max_slices * sizeof(GroupSlice));
+        return used + cv.bytes();
+    };
+    const size_t bytes = carve(nullptr);
+    uint8_t *dev = nullptr;
+    if (hipMalloc((void **)&dev, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("lwkzg_cell_group_segmented_device: no device memory for %zu bytes", bytes);
+        return C_KZG_MALLOC;
+    }
+    DevBlock block{dev};
+    carve(dev);
+    std::vector<uint32_t> off32(g + 1);
+    for (size_t j = 0; j <= g; j++) off32[j] = (uint32_t)offsets[j];
+    LWK_HIP(hipMemcpyAsync(sb.item_off, off32.data(), (g + 1) * 4, hipMemcpyHostToDevice, st));
+    LWK_HIP(hipMemsetAsync(sb.perm_row, 0xff, n * 4, st));   // (a place no lane wrote shows as such)
+    LWK_HIP(hipMemsetAsync(sb.perm_col, 0xff, n * 4, st));
+    launch_cell_group_seg(comms, idx, n, g, slots, seed, hash_mask, sb, st);
+    if (o.slices) {
+        if (gflag) LWK_HIP(hipMemcpyAsync(d_gflag, gflag, g * 4, hipMemcpyHostToDevice, st));
+        launch_cell_group_slice_table(sb.item_off, sb.row_base, gflag ? d_gflag : sb.gbad, d_slices, d_slice_off, g, max_slices, st);
+        LWK_HIP(hipMemcpyAsync(o.slices, d_slices, max_slices * sizeof(GroupSlice), hipMemcpyDeviceToHost, st));
+        LWK_HIP(hipMemcpyAsync(o.slice_off, d_slice_off, (3 * g + 1) * 4, hipMemcpyDeviceToHost, st));
+    }
+    LWK_HIP(hipGetLastError());
+    uint32_t head[kGroupHeadWords];
+    LWK_HIP(hipMemcpyAsync(head, sb.head, sizeof head, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.rows, sb.rows, n * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.distinct48, sb.distinct, n * 48, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.first_item, sb.first_item, n * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.perm_row, sb.perm_row, n * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.row_off, sb.row_off, (n + 1) * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.perm_col, sb.perm_col, n * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.col_off, sb.col_off, (kGroupColumns * g + 1) * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.row_base, sb.row_base, (g + 1) * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(o.bad_words, sb.gbad, g * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipStreamSynchronize(st));
+    *o.m_out = head[kGroupHeadM];
+    if (head[kGroupHeadErr] || head[kGroupHeadM] > n) {
+        set_error("lwkzg_cell_group_segmented_device: the grouping failed (error word %u, M = %u)", head[kGroupHeadErr], head[kGroupHeadM]);
+        return C_KZG_ERROR;
+    }
+    return C_KZG_OK;
+}
+
 }  // namespace
 
 }  // namespace lwk
 
 using namespace lwk;
+
+extern "C" C_KZG_RET lwkzg_cell_group_segmented_device(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, uint32_t *first_item,
+                                                       uint32_t *perm_row, uint32_t *row_off, uint32_t *perm_col, uint32_t *col_off,
+                                                       uint32_t *row_base, uint32_t *bad_words, uint32_t *slices_out, uint32_t *slice_off_out,
+                                                       const uint32_t *gflag, const void *commitments48_dev, const void *cell_indices_dev,
+                                                       size_t n, const uint64_t *group_offsets, size_t g, uint64_t seed, uint32_t hash_mask,
+                                                       void *stream) {
+    return guarded("lwkzg_cell_group_segmented_device", [&] {
+        const SegHookOut o{rows, m_out, first_item, perm_row, row_off, perm_col, col_off, row_base, bad_words, slices_out, slice_off_out, distinct48};
+        return cell_group_seg_hook(o, gflag, (const uint8_t *)commitments48_dev, (const uint64_t *)cell_indices_dev, n, group_offsets, g, seed,
+                                   hash_mask, (hipStream_t)stream);
+    });
+}
 
 extern "C" C_KZG_RET lwkzg_cell_group_device(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, uint32_t *first_item, uint32_t *perm_row,
                                              uint32_t *row_off, uint32_t *perm_col, uint32_t *col_off, uint32_t *bad_index,

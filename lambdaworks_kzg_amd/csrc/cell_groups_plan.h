@@ -1,6 +1,8 @@
 // cell_groups_plan.h -- the host's plan of a cell proof verification: the grouping of one batch (group_items: cells_verify_api.hip and,
 // per range, the grouped call) and the plan of a call of g groups (cells_verify_groups.hip). Host only and free
-// of HIP: tests/cell_groups_plan_check.cpp compiles it as it stands.
+// of HIP: tests/cell_groups_plan_check.cpp compiles it as it stands. The slice rule (plan_slice_count, plan_slice) is also the device's:
+// a cell verifier's grouped call cuts its slice table by it in a kernel (cell_group.hip: k_seg_slice_table; section 4r), and
+// tests/cell_groups_slice_rule_check.cpp holds the two against each other.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -56,6 +58,19 @@ struct GroupSlice {
     uint32_t group, sum, first, count;
 };
 
+// The rule both sides cut by (plan_groups below; k_seg_slice_table of cell_group.hip on the device): a sum of `count` terms from term
+// `first` on is plan_slice_count(count) slices, slice s of them plan_slice(.., s) -- kPlanSliceTerms terms each but the last.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define LWK_PLAN_HD __host__ __device__ __forceinline__
+#else
+#define LWK_PLAN_HD inline
+#endif
+LWK_PLAN_HD uint32_t plan_slice_count(uint32_t count) { return count / kPlanSliceTerms + (count % kPlanSliceTerms ? 1u : 0u); }
+LWK_PLAN_HD GroupSlice plan_slice(uint32_t group, uint32_t sum, uint32_t first, uint32_t count, uint32_t s) {
+    const uint32_t at = s * kPlanSliceTerms;
+    return GroupSlice{group, sum, first + at, count - at < kPlanSliceTerms ? count - at : kPlanSliceTerms};
+}
+
 struct GroupsPlan {
     size_t g = 0, n = 0, m_total = 0;
     std::vector<uint32_t> item_off;     // g + 1: the call's offsets
@@ -97,8 +112,7 @@ inline void plan_groups(GroupsPlan &p, const uint8_t *comms, const uint64_t *idx
     p.col_off.reserve(kPlanCellsPerBlob * g + 1);
     p.slice_off.assign(1, 0);
     auto cut = [&p](uint32_t group, uint32_t sum, uint32_t first, uint32_t count) {
-        for (uint32_t at = 0; at < count; at += kPlanSliceTerms)
-            p.slices.push_back({group, sum, first + at, count - at < kPlanSliceTerms ? count - at : kPlanSliceTerms});
+        for (uint32_t k = 0, slices = plan_slice_count(count); k < slices; k++) p.slices.push_back(plan_slice(group, sum, first, count, k));
         p.slice_off.push_back((uint32_t)p.slices.size());
     };
     for (size_t j = 0; j < g; j++) {

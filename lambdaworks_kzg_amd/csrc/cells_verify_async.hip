@@ -20,24 +20,59 @@
 // the settings' two contexts (pick_ctx) by the verifier's last_done event. The job slots and the protocol of a failing enqueue are
 // verifier_ring.h; the handle's head, the enqueue around enqueue_on, pending / wait / free and the host functions' rules are
 // async_verifier.h, shared with verify_async.hip.
+//
+// A verifier made by lwkzg_cell_verifier_new_groups also takes GROUPED calls (lwkzg_cell_verifier_enqueue_groups):
+// lwkzg_verify_cell_kzg_proof_groups_device's answers, one per group, through the same shell -- the segmented grouping and the slice
+// table of cell_group.hip, the launches behind r of cells_verify_groups.h, two host functions of their own (enqueue_groups_on below).
 #include "abi_guard.h"
 #include "async_verifier.h"
 #include "cell_group.cuh"
+#include "cells_verify_groups.h"
 #include "cellv_bufs.h"
 
 #include <chrono>
 #include <new>
 #include <random>
+#include <vector>
 
 namespace lwk {
+
+void host_parallel_for(size_t n, const std::function<void(size_t)> &fn);  // sha256_host.hip: persistent workers
 
 namespace {
 
 constexpr uint64_t kCellVerifierMagic = 0x4c574b5a43564659ull;  // "LWKZCVFY"
 constexpr size_t kPinPowers = 33 * sizeof(Fr) + 4;   // the powers and, behind them, the skip word: one copy up
 constexpr size_t kPinSums = 3 * 96 + 3 * 4 + 48;     // the three sums, their flags, RLI: 348 bytes down
+constexpr size_t kGroupUpBytes = kPwWords * sizeof(Fr) + 4;   // per group of a grouped call: its powers and its flag word
+
+// what a GROUPED call keeps beside its job slot (section 4r): where its answers go, and its own copy of the offsets
+struct GroupCall {
+    uint8_t *ok_out = nullptr, *partials_out = nullptr;
+    int32_t *rc_out = nullptr;
+    size_t g = 0;
+    uint32_t *h_off = nullptr;   // pinned, gcap + 1 words of this slot alone: the upload reads it after the enqueue has returned
+};
 
 struct CellVerifier : AsyncVerifier {
+    // ---- grouped calls (lwkzg_cell_verifier_new_groups; gcap == 0: none) ----
+    size_t gcap = 0, max_slices = 0;
+    CellGroupSegBufs sg;
+    uint8_t *pw_g = nullptr;          // g x 33 powers and, right behind them, g flag words: one copy up
+    uint32_t *slice_off = nullptr;
+    GroupSlice *slices = nullptr;
+    G1Xyzz *part = nullptr;
+    uint8_t *out96_g = nullptr, *rli_g = nullptr;
+    int32_t *inf_g = nullptr;
+    Fr *colcoef_g = nullptr;
+    uint32_t *h_rowbase = nullptr, *h_gbad = nullptr, *h_offs = nullptr;
+    uint8_t *h_up_g = nullptr, *h_sums_g = nullptr, *h_rli_g = nullptr;
+    int32_t *h_inf_g = nullptr;
+    GroupCall gcall[LWKZG_VERIFIER_DEPTH];
+    // between the two host functions of ONE call (calls of a verifier run one after the other): every group's code and r
+    std::vector<int32_t> g_rc;
+    std::vector<uint32_t> g_r;
+    // ---- every call ----
     size_t slots = 0;
     uint64_t seed = 0;                // of the slot hash, drawn once
     uint8_t *dev = nullptr;           // one block: CellvBufs, the grouping's scratch, the fault words
@@ -72,6 +107,18 @@ size_t carve_device(CellVerifier *v, uint8_t *base) {
     v->g.perm_col = v->b.perm_col;
     v->g.col_off = v->b.col_off;
     v->g.distinct = v->b.comm_in;
+    if (v->gcap) {
+        const size_t gc = v->gcap;
+        cell_group_seg_carve(v->sg, v->g, cv, v->cap, gc);
+        cv.take(v->pw_g, gc * kGroupUpBytes);
+        cv.take(v->slice_off, (3 * gc + 1) * 4);
+        cv.take(v->slices, v->max_slices * sizeof(GroupSlice));
+        cv.take(v->part, v->max_slices * sizeof(G1Xyzz));
+        cv.take(v->out96_g, gc * 3 * 96);
+        cv.take(v->inf_g, gc * 3 * 4);
+        cv.take(v->rli_g, gc * 48);
+        cv.take(v->colcoef_g, cellg_colcoef_bytes());
+    }
     return used + cv.bytes();
 }
 
@@ -84,11 +131,24 @@ size_t carve_pinned(CellVerifier *v, uint8_t *base) {
     cv.take(v->h_comm, v->cap * 48);
     cv.take(v->h_up, kPinPowers);
     cv.take(v->h_sums, kPinSums);
+    if (v->gcap) {
+        const size_t gc = v->gcap;
+        cv.take(v->h_rowbase, (gc + 1) * 4);
+        cv.take(v->h_gbad, gc * 4);
+        cv.take(v->h_up_g, gc * kGroupUpBytes);
+        cv.take(v->h_sums_g, gc * 3 * 96);
+        cv.take(v->h_inf_g, gc * 3 * 4);
+        cv.take(v->h_rli_g, gc * 48);
+        cv.take(v->h_offs, LWKZG_VERIFIER_DEPTH * (gc + 1) * 4);
+        for (int k = 0; k < LWKZG_VERIFIER_DEPTH; k++) v->gcall[k].h_off = v->h_offs + (size_t)k * (gc + 1);
+    }
     return cv.bytes();
 }
 
-// the lowest item at fault: an item's own word (a cell element, its proof), or a distinct commitment's at the item it was first seen at
-uint32_t first_fault(const int32_t *fault, const uint32_t *first_item, size_t n, size_t m) {
+// the lowest item at fault: an item's own word (a cell element, its proof), or a distinct commitment's at the item it was first seen at.
+// fault: the n items' words; fault_c: the m distinct commitments' (fault + n in a batch call; a group of a grouped call has its slices
+// of the call's two runs of words, and first_item then counts in the call's items)
+uint32_t first_fault(const int32_t *fault, const int32_t *fault_c, const uint32_t *first_item, size_t n, size_t m) {
     uint32_t bad = kNoneBad;
     for (size_t i = 0; i < n; i++)
         if (fault[i] != 0) {
@@ -96,20 +156,20 @@ uint32_t first_fault(const int32_t *fault, const uint32_t *first_item, size_t n,
             break;
         }
     for (size_t j = 0; j < m; j++)
-        if (fault[n + j] != 0 && first_item[j] < bad) bad = first_item[j];
+        if (fault_c[j] != 0 && first_item[j] < bad) bad = first_item[j];
     return bad;
 }
 
 // Host function 1's work on plain blocks (also lwkzg_cell_verifier_host_steps'): the code and first_bad of a rejected batch, or r into
 // r_raw and true. bad_index: the lowest i with an index >= 128 (kNoneBad: none), decided first, whatever else is wrong
 bool decide_or_challenge(uint32_t r_raw[8], uint32_t *first_bad, int32_t *rc, const uint8_t *distinct48, size_t m, const uint8_t *digests32,
-                         size_t n, uint32_t bad_index, const int32_t *fault, const uint32_t *first_item, int mode) {
+                         size_t n, uint32_t bad_index, const int32_t *fault, const int32_t *fault_c, const uint32_t *first_item, int mode) {
     if (bad_index != kNoneBad) {
         *first_bad = bad_index;
         *rc = C_KZG_BADARGS;
         return false;
     }
-    *first_bad = first_fault(fault, first_item, n, m);
+    *first_bad = first_fault(fault, fault_c, first_item, n, m);
     if (*first_bad != kNoneBad) {
         *rc = bad_input(mode);
         return false;
@@ -142,7 +202,8 @@ void cell_verifier_host_fn1(void *p) {
             j->failed = true;
         } else {
             uint32_t r_raw[8];
-            if (decide_or_challenge(r_raw, &j->first_bad, &j->code, v->h_comm, m, v->h_dig, j->n, bad_index, v->h_fault, v->h_first, j->mode)) {
+            if (decide_or_challenge(r_raw, &j->first_bad, &j->code, v->h_comm, m, v->h_dig, j->n, bad_index, v->h_fault, v->h_fault + j->n, v->h_first,
+                                    j->mode)) {
                 cell_batch_powers((Fr *)v->h_up, r_raw);
                 r_bytes(((LwkzgCellVerifyResult *)j->res)->partials, r_raw, j->mode);
                 skip = 0;
@@ -183,11 +244,124 @@ void cell_verifier_host_fn2(void *p) {
     v->ring.release(j);   // (the verifier may be gone as soon as this returns)
 }
 
-// the workspace a call on context c takes: one MSM slot
-C_KZG_RET reserve_for(Ctx *c) {
+// ---- a grouped call's two host steps, on plain blocks (the host functions below and lwkzg_cell_verifier_groups_host_steps) -----------------
+inline const uint8_t *at_byte(const uint8_t *p, size_t off) { return p ? p + off : nullptr; }
+
+// Step 1. Per group decide_or_challenge on the group's own slices of the call's arrays, then its powers: rc[j] the group's code so far,
+// r_raw[8 j] its r, pw[33 j] its power table, flags[j] = 1 for a group nothing behind r is to run for (empty, a bad index, a fault).
+// off: the call's g + 1 offsets; fault: 2 n words (items, then concatenated rows); first_item, distinct48: by concatenated row
+void groups_decide(int32_t *rc, uint32_t *r_raw, Fr *pw, uint32_t *flags, const uint32_t *off, size_t g, size_t n, const uint32_t *row_base,
+                   const uint32_t *gbad, const int32_t *fault, const uint32_t *first_item, const uint8_t *digests32, const uint8_t *distinct48,
+                   int mode) {
+    host_parallel_for(g, [&](size_t j) {
+        const uint32_t lo = off[j], cnt = off[j + 1] - lo;
+        flags[j] = 1;
+        rc[j] = (int32_t)C_KZG_OK;
+        if (cnt == 0) return;   // the batch call's answer to n == 0
+        const bool dead = gbad[j] != 0;
+        const uint32_t rb = dead ? 0 : row_base[j], m = dead ? 0 : row_base[j + 1] - rb;
+        if (!dead && (m == 0 || m > cnt)) {   // (the grouping left no such group)
+            rc[j] = (int32_t)C_KZG_ERROR;
+            return;
+        }
+        uint32_t first_bad;
+        if (!decide_or_challenge(r_raw + 8 * j, &first_bad, &rc[j], at_byte(distinct48, 48 * (size_t)rb), m, at_byte(digests32, 32 * (size_t)lo),
+                                 cnt, dead ? 0u : kNoneBad, fault ? fault + lo : nullptr, fault ? fault + n + rb : nullptr,
+                                 first_item ? first_item + rb : nullptr, mode))
+            return;
+        cell_batch_powers(pw + kPwWords * j, r_raw + 8 * j);
+        flags[j] = 0;
+    });
+}
+
+// Step 2. The pairing of every group without a flag, then the outputs, then the result's fields, then state. sums_of(j, sums, infs,
+// rli48): group j's three sums and RLI where the caller keeps them; false: not well formed. failed: step 1 could not do its work
+template <class SumsOf>
+void groups_finish(LwkzgCellVerifyResult *res, uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_out, const int32_t *rc, const uint32_t *r_raw,
+                   const uint32_t *flags, const uint32_t *off, size_t g, uint32_t m_total, const KZGSettings *own, int mode, bool failed,
+                   const SumsOf &sums_of) {
+    constexpr size_t kPart = LWKZG_CELL_VERIFY_PARTIAL_BYTES;
+    if (partials_out) memset(partials_out, 0, g * kPart);
+    if (failed) {
+        for (size_t j = 0; j < g; j++) rc_out[j] = (int32_t)C_KZG_ERROR, ok_out[j] = 0;
+    } else {
+        host_parallel_for(g, [&](size_t j) {
+            rc_out[j] = rc[j];
+            ok_out[j] = rc[j] == (int32_t)C_KZG_OK && off[j + 1] == off[j] ? 1 : 0;
+            if (flags[j]) return;
+            uint8_t *part = partials_out ? partials_out + kPart * j : nullptr;
+            C_KZG_RET f = C_KZG_ERROR;
+            bool ok = false;
+            try {
+                uint8_t sums[3][96], rli48[48];
+                int infs[3];
+                if (part) r_bytes(part, r_raw + 8 * j, mode);
+                f = sums_of(j, sums, infs, rli48) ? cell_batch_finish(&ok, part ? part + 32 : nullptr, sums, infs, rli48, own) : C_KZG_BADARGS;
+            } catch (...) {
+                f = C_KZG_ERROR;
+            }
+            if (f != C_KZG_OK && part) memset(part, 0, kPart);
+            rc_out[j] = (int32_t)f;
+            ok_out[j] = f == C_KZG_OK && ok ? 1 : 0;
+        });
+    }
+    uint32_t first_bad = kNoneBad;
+    for (size_t j = 0; j < g && first_bad == kNoneBad; j++)
+        if (rc_out[j] != (int32_t)C_KZG_OK || ok_out[j] != 1) first_bad = (uint32_t)j;
+    res->first_bad = first_bad;
+    res->m = m_total;
+    complete_now(res, failed ? C_KZG_ERROR : C_KZG_OK, !failed && first_bad == kNoneBad);
+}
+
+// ---- the two host functions of a grouped call (rules: async_verifier.h; host_parallel_for's pool is taken in turns and no job of it
+// ever waits for the GPU) ----
+// behind the copies of the head, row_base, the bad words, the fault words, first_item, the digests and the concatenated commitments
+void cell_verifier_groups_fn1(void *p) {
+    AsyncJob *j = (AsyncJob *)p;
+    CellVerifier *v = static_cast<CellVerifier *>(j->v);
+    const GroupCall &gc = v->gcall[j - v->ring.slots];
+    uint32_t *flags = (uint32_t *)(v->h_up_g + gc.g * kPwWords * sizeof(Fr));
+    try {
+        const uint32_t m = v->h_head[kGroupHeadM];
+        j->m = m;
+        if (v->h_head[kGroupHeadErr] != 0 || m > j->n || v->h_rowbase[gc.g] != m) j->failed = true;
+        else
+            groups_decide(v->g_rc.data(), v->g_r.data(), (Fr *)v->h_up_g, flags, gc.h_off, gc.g, j->n, v->h_rowbase, v->h_gbad, v->h_fault,
+                          v->h_first, v->h_dig, v->h_comm, j->mode);
+    } catch (...) {
+        j->failed = true;
+    }
+    if (j->failed)
+        for (size_t k = 0; k < gc.g; k++) flags[k] = 1;
+}
+
+// behind the copies of the sums, their flags and the RLIs
+void cell_verifier_groups_fn2(void *p) {
+    AsyncJob *j = (AsyncJob *)p;
+    CellVerifier *v = static_cast<CellVerifier *>(j->v);
+    const GroupCall &gc = v->gcall[j - v->ring.slots];
+    LwkzgCellVerifyResult *res = (LwkzgCellVerifyResult *)j->res;
+    const uint32_t *flags = (const uint32_t *)(v->h_up_g + gc.g * kPwWords * sizeof(Fr));
+    bool failed = j->failed;
+    try {
+        groups_finish(res, gc.ok_out, gc.rc_out, gc.partials_out, v->g_rc.data(), v->g_r.data(), flags, gc.h_off, gc.g, j->m, &v->own, j->mode,
+                      failed, [&](size_t k, uint8_t sums[3][96], int infs[3], uint8_t rli48[48]) {
+                          sums_from_pinned(sums, infs, v->h_sums_g + 3 * 96 * k, (const uint8_t *)(v->h_inf_g + 3 * k));
+                          memcpy(rli48, v->h_rli_g + 48 * k, 48);
+                          return true;
+                      });
+    } catch (...) {   // (the pool could not take the job: nothing of the result is final yet)
+        res->first_bad = 0;
+        complete_now(res, C_KZG_ERROR, false);
+    }
+    v->ring.release(j);   // (the verifier may be gone as soon as this returns)
+}
+
+// the workspace a call on context c takes: one MSM slot, or a grouped call's launch set
+C_KZG_RET reserve_for(Ctx *c, size_t msm_slots) {
     std::lock_guard<std::mutex> lk(c->mu);
     LWK_HIP(hipSetDevice(c->device));
-    C_KZG_RET rc = ctx_reserve(c, 1);
+    C_KZG_RET rc = ctx_reserve(c, msm_slots);
     if (rc != C_KZG_OK) return rc;
     stream_warm_host_fn(c->stream);
     return C_KZG_OK;
@@ -203,10 +377,11 @@ uint64_t draw_seed(const void *salt) {
     return s;
 }
 
-C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_cells) {
+// max_groups == 0: a verifier of batch calls alone (lwkzg_cell_verifier_new)
+C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_cells, size_t max_groups) {
     if (!out) return C_KZG_BADARGS;
     *out = nullptr;
-    if (!s || max_cells == 0 || max_cells >= 0x40000000u) return C_KZG_BADARGS;
+    if (!s || max_cells == 0 || max_cells >= 0x40000000u || max_groups > 0x40000000u) return C_KZG_BADARGS;
     Ctx *c = ctx_of(s);
     if (!c) return C_KZG_ERROR;
     if (!s->g2_values) {
@@ -217,6 +392,8 @@ C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, 
     CellVerifier *v = new (std::nothrow) CellVerifier(c, s, max_cells);
     if (!v) return C_KZG_MALLOC;
     v->slots = group_table_slots(max_cells);
+    v->gcap = max_groups;
+    v->max_slices = max_groups ? plan_max_slices(max_cells, max_groups) : 0;
     v->seed = draw_seed(v);
     memset(v->g2, 0, sizeof v->g2);
     v->g2[0] = s->g2_values[0];
@@ -224,9 +401,17 @@ C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, 
     v->own.fs = nullptr;
     v->own.g1_values = nullptr;
     v->own.g2_values = v->g2;
-    C_KZG_RET rc = reserve_for(c);
+    const size_t msm_slots = max_groups ? min_sz(max_groups, kMaxChunk) : 1;
+    C_KZG_RET rc = C_KZG_OK;
+    try {
+        v->g_rc.resize(max_groups);
+        v->g_r.resize(8 * max_groups);
+    } catch (...) {
+        rc = C_KZG_MALLOC;
+    }
+    if (rc == C_KZG_OK) rc = reserve_for(c, msm_slots);
     if (rc == C_KZG_OK)
-        if (Ctx *t = c->twin.load(std::memory_order_acquire)) rc = reserve_for(t);
+        if (Ctx *t = c->twin.load(std::memory_order_acquire)) rc = reserve_for(t, msm_slots);
     if (rc == C_KZG_OK) {
         std::lock_guard<std::mutex> lk(c->mu);
         const size_t dev_bytes = carve_device(v, nullptr), pin_bytes = carve_pinned(v, nullptr);
@@ -321,6 +506,109 @@ C_KZG_RET cell_verifier_enqueue_impl(const LwkzgCellVerifier *handle, LwkzgCellV
                          [&](Ctx *c, AsyncJob *j, int *hf) { return enqueue_on(v, c, j, comms, idx, cells, proofs, caller, hf); });
 }
 
+// ---- a grouped call --------------------------------------------------------------------------------------------------
+//   context stream: the offsets up; the segmented grouping (cell_group.hip); digests with the group-local rows; two-set validation over
+//                   the items and the concatenated distinct commitments; fault words
+//                   head, row_base, bad words, fault words, first_item, digests, concatenated commitments -> pinned
+//                   HOST FUNCTION 1: per group the code, or r and its 33 powers; one flag word per group -> pinned
+//                   powers + flags -> device (one copy); the slice table; k_cellg_scalars, row weights (n workgroups, M from memory),
+//                   the interpolants and their MSMs a launch set at a time, k_cellg_slices on plan_max_slices(n, g) workgroups (the
+//                   live count from memory), k_cellg_fold; sums, flags and RLIs -> pinned, one copy each
+//                   HOST FUNCTION 2: the g pairings on the host threads -- the stream stands still for them --, the outputs, the
+//                   result, state = 1 (release), slot freed
+C_KZG_RET enqueue_groups_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t *comms, const uint64_t *idx, const uint8_t *cells,
+                            const uint8_t *proofs, hipStream_t caller, int *hf) {
+    LWK_HIP(hipSetDevice(c->device));
+    C_KZG_RET rc = ctx_reserve(c, min_sz(v->gcap, kMaxChunk));   // (at once unless this context was made after the verifier)
+    if (rc != C_KZG_OK) return rc;
+    CellvBufs &b = v->b;
+    const CellGroupSegBufs &sg = v->sg;
+    const GroupCall &gc = v->gcall[j - v->ring.slots];
+    const size_t n = j->n, g = gc.g;
+    const int le = mode_rules(j->mode).le(), bad = (int)bad_input(j->mode);
+    hipStream_t st = c->stream;
+    const Fr *d_pw = (const Fr *)v->pw_g;
+    const uint32_t *d_gflag = (const uint32_t *)(v->pw_g + g * kPwWords * sizeof(Fr));
+    if ((rc = async_enqueue_head(v, c)) != C_KZG_OK) return rc;
+    if (caller && caller != st) {   // the inputs were produced on the caller's stream
+        LWK_HIP(hipEventRecord(v->ev_in, caller));
+        LWK_HIP(hipStreamWaitEvent(st, v->ev_in, 0));
+    }
+    WsUse wsu(c, st);
+    LWK_HIP(hipMemsetAsync(v->fault, 0, 4 * n, st));
+    LWK_HIP(hipMemsetAsync(b.status, 0, 4 * n, st));
+    LWK_HIP(hipMemcpyAsync(sg.item_off, gc.h_off, (g + 1) * 4, hipMemcpyHostToDevice, st));
+    launch_cell_group_seg(comms, idx, n, g, v->slots, v->seed, 0xffffffffu, sg, st);
+    launch_cellv_digests(cells, proofs, sg.rows, idx, b.digests, v->fault, bad, le, n, st);
+    const PointSet set_p{proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
+    launch_decompress_points(set_p, &set_c, n, st);
+    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st);
+    launch_cellv_fault_words(v->fault, b.kind_p, b.kind_c, bad, n, st);
+    LWK_HIP(hipMemcpyAsync(v->h_head, sg.head, kGroupHeadWords * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->h_rowbase, sg.row_base, (g + 1) * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->h_gbad, sg.gbad, g * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->h_fault, v->fault, 8 * n, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->h_first, sg.first_item, 4 * n, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->h_dig, b.digests, 32 * n, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->h_comm, b.comm_in, 48 * n, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipLaunchHostFunc(st, cell_verifier_groups_fn1, j));
+    *hf = 1;
+    LWK_HIP(hipMemcpyAsync(v->pw_g, v->h_up_g, g * kGroupUpBytes, hipMemcpyHostToDevice, st));
+    const size_t workgroups = plan_max_slices(n, g);   // (at most v->max_slices: n and g are within the verifier's capacities)
+    launch_cell_group_slice_table(sg.item_off, sg.row_base, d_gflag, v->slices, v->slice_off, g, workgroups, st);
+    LWK_HIP(hipMemsetAsync(b.a_mont, 0, n * sizeof(Fr), st));   // (the row weights read whole rows: a flagged group's stay defined)
+    launch_cellg_scalars(d_pw, idx, c->tw_fwd, sg.item_group, sg.item_off, d_gflag, b.a_mont, b.sc_a, b.sc_b, n, st);
+    launch_cellv_row_weights(b.a_mont, sg.perm_row, sg.row_off, b.sc_c, n, st, sg.head + kGroupHeadM);
+    launch_cellg_interpolants(c, j->mode, cells, b.a_mont, sg.perm_col, sg.col_off, d_gflag, v->colcoef_g, v->rli_g, le, g, st);
+    launch_cellg_sums(v->slices, v->slice_off, d_gflag, b.sc_a, b.sc_b, b.sc_c, b.pts_p, b.kind_p, b.pts_c, b.kind_c, v->part, v->out96_g,
+                      v->inf_g, workgroups, v->slice_off + 3 * g, g, st);
+    LWK_HIP(hipMemcpyAsync(v->h_sums_g, v->out96_g, 3 * 96 * g, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->h_inf_g, v->inf_g, 3 * 4 * g, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->h_rli_g, v->rli_g, 48 * g, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipGetLastError());
+    LWK_HIP(hipLaunchHostFunc(st, cell_verifier_groups_fn2, j));
+    *hf = 2;
+    return async_enqueue_tail(v, c, caller);
+}
+
+C_KZG_RET cell_verifier_enqueue_groups_impl(const LwkzgCellVerifier *handle, LwkzgCellVerifyResult *res, uint8_t *ok_out, int32_t *rc_out,
+                                            uint8_t *partials_out, const uint8_t *comms, const uint64_t *idx, const uint8_t *cells,
+                                            const uint8_t *proofs, size_t n, const uint64_t *offsets, size_t g, hipStream_t caller) {
+    const char *fn = "lwkzg_cell_verifier_enqueue_groups";
+    AsyncVerifier *base;
+    const C_KZG_RET refused = async_enqueue_checks(&base, handle, kCellVerifierMagic, res, n, fn, "cells");
+    if (refused != C_KZG_OK) return refused;
+    CellVerifier *v = static_cast<CellVerifier *>(base);
+    if (v->gcap == 0 || g > v->gcap) {
+        set_error(v->gcap ? "%s: %zu groups, the verifier was created for %zu" : "%s: the verifier was not created by lwkzg_cell_verifier_new_groups",
+                  fn, g, v->gcap);
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    if ((g > 0 && (!ok_out || !rc_out || !offsets)) || (n > 0 && (!comms || !idx || !cells || !proofs))) {
+        set_error("%s: NULL argument", fn);
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    if (!group_offsets_valid(offsets, g, n)) {
+        set_error("%s: group_offsets must be %zu ascending values from 0 to %zu", fn, g + 1, n);
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    if (n == 0) {   // no group, or empty groups alone: the batch call's answer to n == 0 for each
+        for (size_t j = 0; j < g; j++) rc_out[j] = (int32_t)C_KZG_OK, ok_out[j] = 1;
+        if (partials_out) memset(partials_out, 0, g * (size_t)LWKZG_CELL_VERIFY_PARTIAL_BYTES);
+        complete_now(res, C_KZG_OK, true);
+        return C_KZG_OK;
+    }
+    const int mode = mode_of(v->s);
+    ensure_lagrange(v->ctx, mode);   // (a load unless the mode changed to c-kzg after the verifier was made)
+    std::lock_guard<std::mutex> enq(v->enq_mu);
+    return async_enqueue(v, res, n, mode, caller, [&](Ctx *c, AsyncJob *j, int *hf) {
+        GroupCall &gc = v->gcall[j - v->ring.slots];   // the slot's own: no call in flight reads it
+        gc.ok_out = ok_out, gc.rc_out = rc_out, gc.partials_out = partials_out, gc.g = g;
+        for (size_t k = 0; k <= g; k++) gc.h_off[k] = (uint32_t)offsets[k];
+        return enqueue_groups_on(v, c, j, comms, idx, cells, proofs, caller, hf);
+    });
+}
+
 }  // namespace
 
 }  // namespace lwk
@@ -330,7 +618,28 @@ using namespace lwk;
 extern "C" {
 
 C_KZG_RET lwkzg_cell_verifier_new(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_cells) {
-    return guarded("lwkzg_cell_verifier_new", [&] { return cell_verifier_new_impl(out, s, max_cells); });
+    return guarded("lwkzg_cell_verifier_new", [&] { return cell_verifier_new_impl(out, s, max_cells, 0); });
+}
+
+C_KZG_RET lwkzg_cell_verifier_new_groups(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_cells, size_t max_groups) {
+    return guarded("lwkzg_cell_verifier_new_groups", [&] {
+        if (max_groups == 0) {
+            if (out) *out = nullptr;
+            return C_KZG_BADARGS;
+        }
+        return cell_verifier_new_impl(out, s, max_cells, max_groups);
+    });
+}
+
+C_KZG_RET lwkzg_cell_verifier_enqueue_groups(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, uint8_t *ok_out, int32_t *rc_out,
+                                             uint8_t *partials_out, const void *commitments48_dev, const void *cell_indices_dev,
+                                             const void *cells_dev, const void *proofs48_dev, size_t n, const uint64_t *group_offsets, size_t g,
+                                             void *stream) {
+    return guarded("lwkzg_cell_verifier_enqueue_groups", [&] {
+        return cell_verifier_enqueue_groups_impl(v, result, ok_out, rc_out, partials_out, (const uint8_t *)commitments48_dev,
+                                                 (const uint64_t *)cell_indices_dev, (const uint8_t *)cells_dev, (const uint8_t *)proofs48_dev, n,
+                                                 group_offsets, g, (hipStream_t)stream);
+    });
 }
 
 C_KZG_RET lwkzg_cell_verifier_enqueue(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, const void *commitments48_dev,
@@ -357,14 +666,15 @@ C_KZG_RET lwkzg_cell_verifier_host_steps(LwkzgCellVerifyResult *out, const uint8
     if (n == 0 || m == 0 || m > n) return refuse();
     // what each outcome reads: a bad index nothing; a fault word the words and first_item; an honest batch everything
     if (bad_index == kNoneBad && (!status || !first_item)) return refuse();
-    const bool rejected = bad_index != kNoneBad || first_fault(status, first_item, n, m) != kNoneBad;
+    const bool rejected = bad_index != kNoneBad || first_fault(status, status + n, first_item, n, m) != kNoneBad;
     if (!rejected && (!distinct48 || !digests32 || !sums3x97 || !rli48 || !s || !s->g2_values)) return refuse();
     C_KZG_RET rc = C_KZG_ERROR;
     bool ok = false;
     try {
         uint32_t r_raw[8];
         int32_t code = 0;
-        if (!decide_or_challenge(r_raw, &out->first_bad, &code, distinct48, m, digests32, n, bad_index, status, first_item, mode)) {
+        if (!decide_or_challenge(r_raw, &out->first_bad, &code, distinct48, m, digests32, n, bad_index, status, status ? status + n : nullptr,
+                                 first_item, mode)) {
             complete_now(out, (C_KZG_RET)code, false);   // a rejected batch: the code, and nothing behind r is read
             return C_KZG_OK;
         }
@@ -380,6 +690,43 @@ C_KZG_RET lwkzg_cell_verifier_host_steps(LwkzgCellVerifyResult *out, const uint8
     if (rc != C_KZG_OK) memset(out->partials, 0, sizeof out->partials);
     complete_now(out, rc, ok && rc == C_KZG_OK);
     return C_KZG_OK;
+}
+
+C_KZG_RET lwkzg_cell_verifier_groups_host_steps(LwkzgCellVerifyResult *out, uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_out,
+                                                const uint64_t *group_offsets, size_t g, size_t n, const uint32_t *row_base,
+                                                const uint32_t *bad_words, const int32_t *status, const uint32_t *first_item,
+                                                const uint8_t *digests32, const uint8_t *distinct48, const uint8_t *sums3x97,
+                                                const uint8_t *rli48, const KZGSettings *s, int mode) {
+    if (!out) return C_KZG_BADARGS;
+    memset(out, 0, sizeof *out);
+    out->first_bad = kNoneBad;
+    auto refuse = [&] { return async_refuse(out, C_KZG_BADARGS); };
+    if (!mode_known(mode) || g == 0 || n == 0 || n > 0x7fffffffu || g > 0x40000000u) return refuse();
+    if (!ok_out || !rc_out || !row_base || !bad_words || !group_offsets_valid(group_offsets, g, n)) return refuse();
+    return guarded("lwkzg_cell_verifier_groups_host_steps", [&] {
+        std::vector<uint32_t> off(g + 1), r_raw(8 * g), flags(g);
+        std::vector<int32_t> rc(g);
+        std::vector<Fr> pw(kPwWords * g);
+        for (size_t j = 0; j <= g; j++) off[j] = (uint32_t)group_offsets[j];
+        // what each outcome reads: a bad word nothing; a fault word the words and first_item; an honest group everything
+        bool honest = false;
+        for (size_t j = 0; j < g; j++) {
+            if (off[j] == off[j + 1] || bad_words[j]) continue;
+            if (!status || !first_item) return refuse();
+            const uint32_t rb = row_base[j], m = row_base[j + 1] - rb;
+            if (row_base[j + 1] < rb || row_base[j + 1] > n || m > off[j + 1] - off[j]) return refuse();
+            honest = honest || first_fault(status + off[j], status + n + rb, first_item + rb, off[j + 1] - off[j], m) == kNoneBad;
+        }
+        if (honest && (!digests32 || !distinct48 || !sums3x97 || !rli48 || !s || !s->g2_values)) return refuse();
+        groups_decide(rc.data(), r_raw.data(), pw.data(), flags.data(), off.data(), g, n, row_base, bad_words, status, first_item, digests32,
+                      distinct48, mode);
+        groups_finish(out, ok_out, rc_out, partials_out, rc.data(), r_raw.data(), flags.data(), off.data(), g, row_base[g], s, mode, false,
+                      [&](size_t j, uint8_t sums[3][96], int infs[3], uint8_t rli[48]) {
+                          memcpy(rli, rli48 + 48 * j, 48);
+                          return sums_from_97(sums, infs, sums3x97 + 3 * 97 * j);
+                      });
+        return C_KZG_OK;
+    });
 }
 
 }  // extern "C"

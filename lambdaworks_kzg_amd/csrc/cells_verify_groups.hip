@@ -15,7 +15,7 @@
 //   host     cell_batch_finish per live group on the host threads (the pairing does not re-enter them: it forks by SideTask)
 // A dead (bad index) or faulty group is flagged before the second device visit and nothing there reads its points or its indices.
 #include "abi_guard.h"
-#include "cell_groups_plan.h"
+#include "cells_verify_groups.h"
 #include "cellv_bufs.h"
 #include "cell_interp.cuh"
 #include "cell_each.cuh"
@@ -40,7 +40,6 @@ static_assert(sizeof(GroupSlice) == 16, "four words per slice on the device");
 // groups per pass of the interpolant kernels: their scratch is kInterpChunk x 128 columns x 64 coefficients = 16 MiB, whatever g
 constexpr size_t kInterpChunk = 64;
 constexpr size_t kInterpGroupBytes = (size_t)kCellsPerBlob * kCellElems * sizeof(Fr);   // 256 KiB
-constexpr size_t kPwWords = 33;                                                        // Fr slots of a group's power table
 
 // ---- behind r: a_i = r_j^(i - off_j), b_i = a_i c_(k_i) for the items of the live groups -------------------------------------------------
 // pw: group j's table at 33 j (r_j^(2^k), k < 32, then 1). One lane per item and no barrier: a lane of a flagged group leaves alone, before
@@ -141,9 +140,11 @@ __global__ __launch_bounds__(64) void k_cellg_slices(const GroupSlice *__restric
                                                      const uint32_t *__restrict__ sc_a, const uint32_t *__restrict__ sc_b,
                                                      const uint32_t *__restrict__ sc_c, const G1Affine29 *__restrict__ pts_p,
                                                      const int32_t *__restrict__ kind_p, const G1Affine29 *__restrict__ pts_c,
-                                                     const int32_t *__restrict__ kind_c, Fp beta, G1Xyzz *__restrict__ part) {
+                                                     const int32_t *__restrict__ kind_c, Fp beta, G1Xyzz *__restrict__ part,
+                                                     const uint32_t *__restrict__ live) {
     __shared__ G1Xyzz sh[kCellElems];   // 12 KiB: the tree's points
     const uint32_t t = threadIdx.x;
+    if (live && blockIdx.x >= *live) return;   // (a verifier's launch covers the most slices its call can have: section 4r)
     const GroupSlice sl = slices[blockIdx.x];
     if (gflag[sl.group]) return;
     // a lane without a term -- the slice is short, or the term's point is the point at infinity -- multiplies by zero: the product is
@@ -193,6 +194,57 @@ __global__ __launch_bounds__(64) void k_cellg_fold(const G1Xyzz *__restrict__ pa
     fe_to_raw<FpParams>(raw, a.y);
     raw_to_be<12>(o + 48, raw);
 }
+
+}  // namespace
+
+// ---- the launches (cells_verify_groups.h) ----------------------------------------------------------------------------------------------------
+size_t cellg_colcoef_bytes() { return kInterpChunk * kInterpGroupBytes; }
+
+void launch_cellg_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, const uint32_t *item_group, const uint32_t *item_off,
+                          const uint32_t *gflag, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b, size_t n, hipStream_t st) {
+    ProfScope p("k_cellg_scalars", st);
+    hipLaunchKernelGGL(k_cellg_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pw, idx, tw_fwd, item_group, item_off, gflag, a_mont,
+                       sc_a, sc_b, (uint32_t)n);
+}
+
+void launch_cellg_interpolants(Ctx *c, int mode, const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off,
+                               const uint32_t *gflag, Fr *colcoef, uint8_t *rli48, int le, size_t g, hipStream_t st) {
+    for (size_t base = 0; base < g; base += kMaxChunk) {   // a launch set of MSM slots at a time
+        const size_t set = min_sz(g - base, kMaxChunk);
+        for (size_t off = 0; off < set; off += kInterpChunk) {
+            const size_t m = min_sz(set - off, kInterpChunk);
+            const uint32_t first = (uint32_t)(base + off);
+            {
+                ProfScope p("k_cellg_columns", st);
+                hipLaunchKernelGGL(k_cellg_columns, dim3(kCellsPerBlob, (unsigned)m), dim3(256), 0, st, (const uint4 *)cells, a_mont, perm_col,
+                                   col_off, gflag, (const Fr *)c->tw_inv, colcoef, le, first);
+            }
+            ProfScope p("k_cellg_coeffs", st);
+            hipLaunchKernelGGL(k_cellg_coeffs, dim3(kBlobElems / 256, (unsigned)m), dim3(256), 0, st, (const Fr *)colcoef, gflag,
+                               (Fr *)c->ws.scalars2 + (size_t)kBlobElems * off, first);
+        }
+        const bool lg = coefficients_to_msm_form(c, mode, set, st);
+        msm_stages(c, c->ws.scalars2, rli48 + 48 * base, set, st, 0, false, lg);
+    }
+}
+
+void launch_cellg_sums(const GroupSlice *slices, const uint32_t *slice_off, const uint32_t *gflag, const uint32_t *sc_a, const uint32_t *sc_b,
+                       const uint32_t *sc_c, const G1Affine29 *pts_p, const int32_t *kind_p, const G1Affine29 *pts_c, const int32_t *kind_c,
+                       G1Xyzz *part, uint8_t *out96, int32_t *inf, size_t workgroups, const uint32_t *live, size_t g, hipStream_t st) {
+    uint32_t braw[12];
+    g1_beta_raw(braw);
+    const Fp beta = fe_from_raw<FpParams>(braw);
+    if (workgroups) {
+        ProfScope p("k_cellg_slices", st);
+        hipLaunchKernelGGL(k_cellg_slices, dim3((unsigned)workgroups), dim3(kCellElems), 0, st, slices, gflag, sc_a, sc_b, sc_c, pts_p, kind_p,
+                           pts_c, kind_c, beta, part, live);
+    }
+    ProfScope p("k_cellg_fold", st);
+    hipLaunchKernelGGL(k_cellg_fold, dim3((unsigned)((3 * g + 63) / 64)), dim3(64), 0, st, (const G1Xyzz *)part, slice_off, gflag, out96, inf,
+                       (uint32_t)(3 * g));
+}
+
+namespace {
 
 // ---- the device side of a call, carved out of one allocation ---------------------------------------------------------------------------------
 // cap counts units: a call of n items in g groups needs max(n, g) of them
@@ -447,48 +499,13 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
     LWK_HIP(hipMemcpyAsync(b.gflag, pin.gflag, 4 * g, hipMemcpyHostToDevice, st));
     LWK_HIP(hipMemsetAsync(b.a_mont, 0, n * sizeof(Fr), st));   // (the row weights read whole rows: a flagged group's stay defined)
     clk.mark(3);
-    {
-        ProfScope p("k_cellg_scalars", st);
-        hipLaunchKernelGGL(k_cellg_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const Fr *)b.pw, d_idx, (const Fr *)c->tw_fwd,
-                           (const uint32_t *)b.item_group, (const uint32_t *)b.item_off, (const uint32_t *)b.gflag, b.a_mont, b.sc_a, b.sc_b,
-                           (uint32_t)n);
-    }
+    launch_cellg_scalars(b.pw, d_idx, c->tw_fwd, b.item_group, b.item_off, b.gflag, b.a_mont, b.sc_a, b.sc_b, n, st);
     launch_cellv_row_weights(b.a_mont, b.perm_row, b.row_off, b.sc_c, plan.m_total, st);
     clk.mark(4);
-    for (size_t base = 0; base < g; base += kMaxChunk) {   // a launch set of MSM slots at a time
-        const size_t set = min_sz(g - base, kMaxChunk);
-        for (size_t off = 0; off < set; off += kInterpChunk) {
-            const size_t m = min_sz(set - off, kInterpChunk);
-            const uint32_t first = (uint32_t)(base + off);
-            {
-                ProfScope p("k_cellg_columns", st);
-                hipLaunchKernelGGL(k_cellg_columns, dim3(kCellsPerBlob, (unsigned)m), dim3(256), 0, st, (const uint4 *)d_cells, (const Fr *)b.a_mont,
-                                   (const uint32_t *)b.perm_col, (const uint32_t *)b.col_off, (const uint32_t *)b.gflag, (const Fr *)c->tw_inv,
-                                   b.colcoef, le, first);
-            }
-            ProfScope p("k_cellg_coeffs", st);
-            hipLaunchKernelGGL(k_cellg_coeffs, dim3(kBlobElems / 256, (unsigned)m), dim3(256), 0, st, (const Fr *)b.colcoef,
-                               (const uint32_t *)b.gflag, (Fr *)c->ws.scalars2 + (size_t)kBlobElems * off, first);
-        }
-        const bool lg = coefficients_to_msm_form(c, mode, set, st);
-        msm_stages(c, c->ws.scalars2, b.rli48 + 48 * base, set, st, 0, false, lg);
-    }
+    launch_cellg_interpolants(c, mode, d_cells, b.a_mont, b.perm_col, b.col_off, b.gflag, b.colcoef, b.rli48, le, g, st);
     clk.mark(5);
-    uint32_t braw[12];
-    g1_beta_raw(braw);
-    const Fp beta = fe_from_raw<FpParams>(braw);
-    if (!plan.slices.empty()) {
-        ProfScope p("k_cellg_slices", st);
-        hipLaunchKernelGGL(k_cellg_slices, dim3((unsigned)plan.slices.size()), dim3(kCellElems), 0, st, (const GroupSlice *)b.slices,
-                           (const uint32_t *)b.gflag, (const uint32_t *)b.sc_a, (const uint32_t *)b.sc_b, (const uint32_t *)b.sc_c,
-                           (const G1Affine29 *)b.pts_p, (const int32_t *)b.kind_p, (const G1Affine29 *)b.pts_c, (const int32_t *)b.kind_c, beta,
-                           b.part);
-    }
-    {
-        ProfScope p("k_cellg_fold", st);
-        hipLaunchKernelGGL(k_cellg_fold, dim3((unsigned)((3 * g + 63) / 64)), dim3(64), 0, st, (const G1Xyzz *)b.part,
-                           (const uint32_t *)b.slice_off, (const uint32_t *)b.gflag, b.out96, b.inf, (uint32_t)(3 * g));
-    }
+    launch_cellg_sums(b.slices, b.slice_off, b.gflag, b.sc_a, b.sc_b, b.sc_c, b.pts_p, b.kind_p, b.pts_c, b.kind_c, b.part, b.out96, b.inf,
+                      plan.slices.size(), nullptr, g, st);
     clk.mark(6);
     LWK_HIP(hipMemcpyAsync(pin.sums, b.out96, 3 * 96 * g, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(pin.inf, b.inf, 3 * 4 * g, hipMemcpyDeviceToHost, st));

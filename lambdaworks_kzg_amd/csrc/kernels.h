@@ -366,4 +366,42 @@ inline void cell_group_carve(CellGroupBufs &g, Carver_ &cv, size_t cap, size_t s
 void launch_cell_group(const uint8_t *comms48, const uint64_t *idx, size_t n, size_t slots, uint64_t seed, uint32_t hash_mask,
                        const CellGroupBufs &g, hipStream_t st);
 
+// ---- the same for a call of g groups (cell_group.hip): what plan_groups (cell_groups_plan.h) makes on the host.
+// The key of an item is (its group, its 48 bytes); the groups are the contiguous item ranges item_off[j] .. item_off[j + 1] - 1.
+// Capacities for n items in g groups: table slots words, slot_of n, slot_row slots, row_cnt n, pre n + 1, head kGroupHeadWords and
+// behind it col_cnt 128 g (ONE piece, one fill); item_off g + 1 (in), item_group n, gbad g, rows n (GROUP-LOCAL), row_base g + 1,
+// first_item n, distinct 48 n (the groups' distinct commitments one after the other, then infinity encodings), perm_row n / row_off
+// n + 1 over the M = row_base[g] concatenated rows, perm_col n / col_off 128 g + 1 (list 128 j + k).
+// head[kGroupHeadM] = M; head[kGroupHeadErr] as above; gbad[j] != 0: an index of group j is not below 128 -- the group has no rows
+// and no columns, its items' rows are 0 and they are in neither list.
+struct CellGroupSegBufs {
+    uint32_t *table, *slot_of, *slot_row, *row_cnt, *pre;
+    uint32_t *head, *col_cnt;
+    uint32_t *item_off, *item_group, *gbad, *rows, *row_base, *first_item, *perm_row, *row_off, *perm_col, *col_off;
+    uint8_t *distinct;
+};
+// what a segmented grouping needs beyond a CellGroupBufs of the same capacity, whose scratch and outputs it shares (a verifier runs
+// one grouping or the other, never both at once)
+template <class Carver_>
+inline void cell_group_seg_carve(CellGroupSegBufs &s, const CellGroupBufs &g, Carver_ &cv, size_t cap, size_t gcap) {
+    s.table = g.table, s.slot_of = g.slot_of, s.slot_row = g.slot_row, s.row_cnt = g.row_cnt, s.first_item = g.first_item;
+    s.rows = g.rows, s.perm_row = g.perm_row, s.row_off = g.row_off, s.perm_col = g.perm_col, s.distinct = g.distinct;
+    cv.take(s.pre, (cap + 1) * 4);
+    cv.take(s.head, (kGroupHeadWords + 128 * gcap) * 4);
+    s.col_cnt = (uint32_t *)((uintptr_t)s.head + kGroupHeadWords * 4);
+    cv.take(s.item_off, (gcap + 1) * 4);
+    cv.take(s.item_group, cap * 4);
+    cv.take(s.gbad, gcap * 4);
+    cv.take(s.row_base, (gcap + 1) * 4);
+    cv.take(s.col_off, (128 * gcap + 1) * 4);
+}
+// s.item_off holds the call's g + 1 offsets (valid: group_offsets_valid). Seven launches and four fills on st; nothing is read back
+void launch_cell_group_seg(const uint8_t *comms48, const uint64_t *idx, size_t n, size_t g, size_t slots, uint64_t seed, uint32_t hash_mask,
+                           const CellGroupSegBufs &s, hipStream_t st);
+// the slice table of the call (cell_groups_plan.h: plan_slice_count / plan_slice): slice_off[3 g + 1], slices[slice_off[3 g]]; a
+// group with gflag[j] != 0 has no slices. One workgroup. slice_off[3 g] -- the live slice count -- never exceeds max_slices
+struct GroupSlice;
+void launch_cell_group_slice_table(const uint32_t *item_off, const uint32_t *row_base, const uint32_t *gflag, GroupSlice *slices,
+                                   uint32_t *slice_off, size_t g, size_t max_slices, hipStream_t st);
+
 }  // namespace lwk
