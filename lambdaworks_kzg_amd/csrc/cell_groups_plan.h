@@ -15,6 +15,7 @@ namespace lwk {
 
 constexpr size_t kPlanCellsPerBlob = 128;   // kernels.h: kCellsPerBlob (cells_verify_api.hip holds the two against each other)
 constexpr uint32_t kPlanSliceTerms = 64;    // terms of one slice of one sum: one lane each of a 64-lane workgroup
+constexpr size_t kPwWords = 33;             // field-element slots of a group's power table: r^(2^k), k < 32, then 1
 
 // what the host derives from the commitments and the indices of one batch
 struct Grouping {
@@ -75,7 +76,7 @@ struct GroupsPlan {
     size_t g = 0, n = 0, m_total = 0;
     std::vector<uint32_t> item_off;     // g + 1: the call's offsets
     std::vector<uint32_t> row_base;     // g + 1: group j's rows are row_base[j] .. row_base[j + 1] - 1 of the concatenated rows
-    std::vector<uint8_t> dead;          // g: an index of the group is not below 128; it has no rows, no columns and no slices
+    std::vector<uint32_t> dead;         // g: an index of the group is not below 128; it has no rows, no columns and no slices
     std::vector<uint32_t> item_group;   // n
     std::vector<uint32_t> rows;         // n: GROUP-LOCAL rows, as the group's own transcript numbers them (0 for a dead group's items)
     std::vector<uint8_t> distinct;      // 48 n: the groups' distinct commitments one after the other, then infinity encodings

@@ -204,6 +204,20 @@ void launch_cellv_fault_words(int32_t *fault, const int32_t *kind_p, const int32
     hipLaunchKernelGGL(k_cellv_fault_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fault, kind_p, kind_c, bad_code, (uint32_t)n);
 }
 
+hipError_t launch_cellv_first_visit(const uint8_t *cells, const uint64_t *idx, const uint32_t *rows, const PointSet &set_p, const PointSet &set_c,
+                                    uint8_t *digests32, int32_t *fault, int32_t *status, int bad_code, int le, size_t n, hipStream_t st,
+                                    hipEvent_t digests_done) {
+    hipError_t e = hipMemsetAsync(fault, 0, 4 * n, st);   // (the digests write a word only where an element is out of range)
+    if (e == hipSuccess) e = hipMemsetAsync(status, 0, 4 * n, st);
+    if (e != hipSuccess) return e;
+    launch_cellv_digests(cells, set_p.in48, rows, idx, digests32, fault, bad_code, le, n, st);
+    if (digests_done) e = hipEventRecord(digests_done, st);
+    launch_decompress_points(set_p, &set_c, n, st);
+    launch_subgroup_canon(set_p, &set_c, status, bad_code, n, st);
+    launch_cellv_fault_words(fault, set_p.kind, set_c.kind, bad_code, n, st);
+    return e;
+}
+
 // ---- behind r: the column sums, their interpolation, and the 64 coefficients of I(X) ------------------------------------------------
 // One workgroup per column k, four waves: wave v sums every fourth item of the column (lane t = element t of the cell; a wave reads
 // a cell's 2 KiB in one pass), the four partial sums meet in LDS, and 32 lanes run the six stages of the 64-point decimation-in-time

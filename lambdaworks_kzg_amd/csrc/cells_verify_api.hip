@@ -11,8 +11,11 @@
 //   device   scalars, row weights, column sums + interpolation, the 64-term MSM on the engine's own launch set, the three
 //            variable-base sums (vmsm.hip); four points come down
 //   host     the pairing check against g2_values[64] (pairing.hip keeps its line table beside the others)
+// This call reports no first_bad and keeps its single status word and its own launch sequence; of the host unit that the calls with
+// attribution share (cells_verify_host.h) it takes cell_r_bytes, and sums_from_pinned of async_verifier.h.
 #include "abi_guard.h"
 #include "cell_groups_plan.h"
+#include "cells_verify_host.h"
 #include "cellv_bufs.h"
 #include "knobs.h"
 
@@ -161,12 +164,7 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
     LWK_HIP(hipMemcpyAsync(res + 3 * 96 + 12, b.rli48, 48, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipGetLastError());
     LWK_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < 3; k++) {
-        memcpy(sums[k], res + 96 * k, 96);
-        int32_t f;
-        memcpy(&f, res + 3 * 96 + 4 * k, 4);
-        infs[k] = f;
-    }
+    sums_from_pinned(sums, infs, res, res + 3 * 96);
     memcpy(rli48, res + 3 * 96 + 12, 48);
     if (clk.on)
         fprintf(stderr, "[lambdaworks_kzg_amd] verify cells n=%zu m=%zu: host grouping %.3f ms | device: digests %.3f, validation %.3f, "
@@ -196,10 +194,7 @@ C_KZG_RET cell_batch_impl(bool *ok, uint8_t *partials, const void *comms, const 
     C_KZG_RET rc = cell_batch_sums(r_raw, sums, infs, rli48, (const uint8_t *)comms, (const uint64_t *)idx, (const uint8_t *)cells,
                                    (const uint8_t *)proofs, n, s, mode, device_inputs, caller);
     if (rc != C_KZG_OK) return rc;
-    if (partials) {
-        if (mode_rules(mode).little_endian) raw_to_le<8>(partials, r_raw);
-        else raw_to_be<8>(partials, r_raw);
-    }
+    if (partials) cell_r_bytes(partials, r_raw, mode);
     const auto t0 = std::chrono::steady_clock::now();
     rc = cell_batch_finish(ok, partials ? partials + 32 : nullptr, sums, infs, rli48, s);
     if (knobs().timing && ok)
@@ -258,8 +253,7 @@ C_KZG_RET lwkzg_cell_batch_challenge_host(uint8_t r_out[32], const Bytes48 *comm
         }
         uint32_t r_raw[8];
         cell_batch_challenge(r_raw, g.distinct.data(), g.m, digests.data(), n, mode_rules(mode).little_endian);
-        if (mode_rules(mode).little_endian) raw_to_le<8>(r_out, r_raw);
-        else raw_to_be<8>(r_out, r_raw);
+        cell_r_bytes(r_out, r_raw, mode);
         return C_KZG_OK;
     });
 }

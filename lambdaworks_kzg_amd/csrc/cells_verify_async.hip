@@ -19,15 +19,19 @@
 // Calls on one verifier share its device block and pinned block and run one after the other: on one context by stream order, across
 // the settings' two contexts (pick_ctx) by the verifier's last_done event. The job slots and the protocol of a failing enqueue are
 // verifier_ring.h; the handle's head, the enqueue around enqueue_on, pending / wait / free and the host functions' rules are
-// async_verifier.h, shared with verify_async.hip.
+// async_verifier.h, shared with verify_async.hip. What the host functions DECIDE -- the first fault, the code or r, a grouped call's
+// two steps -- is cells_verify_host.h and the first visit cells_verify.hip's launch_cellv_first_visit, both shared with the synchronous
+// grouped call (cells_verify_groups.hip); this file keeps the host functions themselves, the enqueue code and the *_host_steps hooks.
 //
 // A verifier made by lwkzg_cell_verifier_new_groups also takes GROUPED calls (lwkzg_cell_verifier_enqueue_groups):
 // lwkzg_verify_cell_kzg_proof_groups_device's answers, one per group, through the same shell -- the segmented grouping and the slice
-// table of cell_group.hip, the launches behind r of cells_verify_groups.h, two host functions of their own (enqueue_groups_on below).
+// table of cell_group.hip, the launches and the buffers behind r of cells_verify_groups.h (CellgBufs, CellgPin), two host functions
+// of their own around groups_decide and groups_answers (enqueue_groups_on below).
 #include "abi_guard.h"
 #include "async_verifier.h"
 #include "cell_group.cuh"
 #include "cells_verify_groups.h"
+#include "cells_verify_host.h"
 #include "cellv_bufs.h"
 
 #include <chrono>
@@ -37,14 +41,11 @@
 
 namespace lwk {
 
-void host_parallel_for(size_t n, const std::function<void(size_t)> &fn);  // sha256_host.hip: persistent workers
-
 namespace {
 
 constexpr uint64_t kCellVerifierMagic = 0x4c574b5a43564659ull;  // "LWKZCVFY"
 constexpr size_t kPinPowers = 33 * sizeof(Fr) + 4;   // the powers and, behind them, the skip word: one copy up
 constexpr size_t kPinSums = 3 * 96 + 3 * 4 + 48;     // the three sums, their flags, RLI: 348 bytes down
-constexpr size_t kGroupUpBytes = kPwWords * sizeof(Fr) + 4;   // per group of a grouped call: its powers and its flag word
 
 // what a GROUPED call keeps beside its job slot (section 4r): where its answers go, and its own copy of the offsets
 struct GroupCall {
@@ -58,16 +59,9 @@ struct CellVerifier : AsyncVerifier {
     // ---- grouped calls (lwkzg_cell_verifier_new_groups; gcap == 0: none) ----
     size_t gcap = 0, max_slices = 0;
     CellGroupSegBufs sg;
-    uint8_t *pw_g = nullptr;          // g x 33 powers and, right behind them, g flag words: one copy up
-    uint32_t *slice_off = nullptr;
-    GroupSlice *slices = nullptr;
-    G1Xyzz *part = nullptr;
-    uint8_t *out96_g = nullptr, *rli_g = nullptr;
-    int32_t *inf_g = nullptr;
-    Fr *colcoef_g = nullptr;
+    CellgBufs gb = {};                // behind r (cells_verify_groups.h)
+    CellgPin gp = {};
     uint32_t *h_rowbase = nullptr, *h_gbad = nullptr, *h_offs = nullptr;
-    uint8_t *h_up_g = nullptr, *h_sums_g = nullptr, *h_rli_g = nullptr;
-    int32_t *h_inf_g = nullptr;
     GroupCall gcall[LWKZG_VERIFIER_DEPTH];
     // between the two host functions of ONE call (calls of a verifier run one after the other): every group's code and r
     std::vector<int32_t> g_rc;
@@ -97,8 +91,8 @@ struct CellVerifier : AsyncVerifier {
 };
 
 size_t carve_device(CellVerifier *v, uint8_t *base) {
-    const size_t used = cellv_carve(v->b, base, v->cap, false);
-    Carver cv(base ? base + used : nullptr);
+    Carver cv(base);
+    cellv_carve(v->b, cv, v->cap, false);
     cell_group_carve(v->g, cv, v->cap, v->slots);
     cv.take(v->fault, 2 * v->cap * 4);
     v->g.rows = v->b.rows;
@@ -110,16 +104,9 @@ size_t carve_device(CellVerifier *v, uint8_t *base) {
     if (v->gcap) {
         const size_t gc = v->gcap;
         cell_group_seg_carve(v->sg, v->g, cv, v->cap, gc);
-        cv.take(v->pw_g, gc * kGroupUpBytes);
-        cv.take(v->slice_off, (3 * gc + 1) * 4);
-        cv.take(v->slices, v->max_slices * sizeof(GroupSlice));
-        cv.take(v->part, v->max_slices * sizeof(G1Xyzz));
-        cv.take(v->out96_g, gc * 3 * 96);
-        cv.take(v->inf_g, gc * 3 * 4);
-        cv.take(v->rli_g, gc * 48);
-        cv.take(v->colcoef_g, cellg_colcoef_bytes());
+        cellg_carve(v->gb, cv, gc, v->max_slices);
     }
-    return used + cv.bytes();
+    return cv.bytes();
 }
 
 size_t carve_pinned(CellVerifier *v, uint8_t *base) {
@@ -135,52 +122,11 @@ size_t carve_pinned(CellVerifier *v, uint8_t *base) {
         const size_t gc = v->gcap;
         cv.take(v->h_rowbase, (gc + 1) * 4);
         cv.take(v->h_gbad, gc * 4);
-        cv.take(v->h_up_g, gc * kGroupUpBytes);
-        cv.take(v->h_sums_g, gc * 3 * 96);
-        cv.take(v->h_inf_g, gc * 3 * 4);
-        cv.take(v->h_rli_g, gc * 48);
+        cellg_carve_pin(v->gp, cv, gc);
         cv.take(v->h_offs, LWKZG_VERIFIER_DEPTH * (gc + 1) * 4);
         for (int k = 0; k < LWKZG_VERIFIER_DEPTH; k++) v->gcall[k].h_off = v->h_offs + (size_t)k * (gc + 1);
     }
     return cv.bytes();
-}
-
-// the lowest item at fault: an item's own word (a cell element, its proof), or a distinct commitment's at the item it was first seen at.
-// fault: the n items' words; fault_c: the m distinct commitments' (fault + n in a batch call; a group of a grouped call has its slices
-// of the call's two runs of words, and first_item then counts in the call's items)
-uint32_t first_fault(const int32_t *fault, const int32_t *fault_c, const uint32_t *first_item, size_t n, size_t m) {
-    uint32_t bad = kNoneBad;
-    for (size_t i = 0; i < n; i++)
-        if (fault[i] != 0) {
-            bad = (uint32_t)i;
-            break;
-        }
-    for (size_t j = 0; j < m; j++)
-        if (fault_c[j] != 0 && first_item[j] < bad) bad = first_item[j];
-    return bad;
-}
-
-// Host function 1's work on plain blocks (also lwkzg_cell_verifier_host_steps'): the code and first_bad of a rejected batch, or r into
-// r_raw and true. bad_index: the lowest i with an index >= 128 (kNoneBad: none), decided first, whatever else is wrong
-bool decide_or_challenge(uint32_t r_raw[8], uint32_t *first_bad, int32_t *rc, const uint8_t *distinct48, size_t m, const uint8_t *digests32,
-                         size_t n, uint32_t bad_index, const int32_t *fault, const int32_t *fault_c, const uint32_t *first_item, int mode) {
-    if (bad_index != kNoneBad) {
-        *first_bad = bad_index;
-        *rc = C_KZG_BADARGS;
-        return false;
-    }
-    *first_bad = first_fault(fault, fault_c, first_item, n, m);
-    if (*first_bad != kNoneBad) {
-        *rc = bad_input(mode);
-        return false;
-    }
-    cell_batch_challenge(r_raw, distinct48, m, digests32, n, mode_rules(mode).little_endian);
-    return true;
-}
-
-void r_bytes(uint8_t out32[32], const uint32_t r_raw[8], int mode) {
-    if (mode_rules(mode).little_endian) raw_to_le<8>(out32, r_raw);
-    else raw_to_be<8>(out32, r_raw);
 }
 
 // ---- the two host functions ------------------------------------------------------------------------------------------------------
@@ -190,7 +136,7 @@ void r_bytes(uint8_t out32[32], const uint32_t r_raw[8], int mode) {
 // that is no point) cannot happen with a verifier's own copy of the G2 points and the engine's own compressed output, and would only
 // write the runtime thread's own error text.
 
-// behind the copies of the head, the fault words, the digests and the padded commitments
+// behind the copies of the head, the fault words, the digests and the padded commitments: decide_or_challenge (cells_verify_host.h)
 void cell_verifier_host_fn1(void *p) {
     AsyncJob *j = (AsyncJob *)p;
     CellVerifier *v = static_cast<CellVerifier *>(j->v);
@@ -205,7 +151,7 @@ void cell_verifier_host_fn1(void *p) {
             if (decide_or_challenge(r_raw, &j->first_bad, &j->code, v->h_comm, m, v->h_dig, j->n, bad_index, v->h_fault, v->h_fault + j->n, v->h_first,
                                     j->mode)) {
                 cell_batch_powers((Fr *)v->h_up, r_raw);
-                r_bytes(((LwkzgCellVerifyResult *)j->res)->partials, r_raw, j->mode);
+                cell_r_bytes(((LwkzgCellVerifyResult *)j->res)->partials, r_raw, j->mode);
                 skip = 0;
             }
         }
@@ -244,66 +190,17 @@ void cell_verifier_host_fn2(void *p) {
     v->ring.release(j);   // (the verifier may be gone as soon as this returns)
 }
 
-// ---- a grouped call's two host steps, on plain blocks (the host functions below and lwkzg_cell_verifier_groups_host_steps) -----------------
-inline const uint8_t *at_byte(const uint8_t *p, size_t off) { return p ? p + off : nullptr; }
-
-// Step 1. Per group decide_or_challenge on the group's own slices of the call's arrays, then its powers: rc[j] the group's code so far,
-// r_raw[8 j] its r, pw[33 j] its power table, flags[j] = 1 for a group nothing behind r is to run for (empty, a bad index, a fault).
-// off: the call's g + 1 offsets; fault: 2 n words (items, then concatenated rows); first_item, distinct48: by concatenated row
-void groups_decide(int32_t *rc, uint32_t *r_raw, Fr *pw, uint32_t *flags, const uint32_t *off, size_t g, size_t n, const uint32_t *row_base,
-                   const uint32_t *gbad, const int32_t *fault, const uint32_t *first_item, const uint8_t *digests32, const uint8_t *distinct48,
-                   int mode) {
-    host_parallel_for(g, [&](size_t j) {
-        const uint32_t lo = off[j], cnt = off[j + 1] - lo;
-        flags[j] = 1;
-        rc[j] = (int32_t)C_KZG_OK;
-        if (cnt == 0) return;   // the batch call's answer to n == 0
-        const bool dead = gbad[j] != 0;
-        const uint32_t rb = dead ? 0 : row_base[j], m = dead ? 0 : row_base[j + 1] - rb;
-        if (!dead && (m == 0 || m > cnt)) {   // (the grouping left no such group)
-            rc[j] = (int32_t)C_KZG_ERROR;
-            return;
-        }
-        uint32_t first_bad;
-        if (!decide_or_challenge(r_raw + 8 * j, &first_bad, &rc[j], at_byte(distinct48, 48 * (size_t)rb), m, at_byte(digests32, 32 * (size_t)lo),
-                                 cnt, dead ? 0u : kNoneBad, fault ? fault + lo : nullptr, fault ? fault + n + rb : nullptr,
-                                 first_item ? first_item + rb : nullptr, mode))
-            return;
-        cell_batch_powers(pw + kPwWords * j, r_raw + 8 * j);
-        flags[j] = 0;
-    });
-}
-
-// Step 2. The pairing of every group without a flag, then the outputs, then the result's fields, then state. sums_of(j, sums, infs,
-// rli48): group j's three sums and RLI where the caller keeps them; false: not well formed. failed: step 1 could not do its work
+// ---- a grouped call's result, behind its two host steps (cells_verify_host.h: groups_decide, groups_answers) ----------------------------------
+// The groups' answers and partials, then the result's fields, then state. failed: step 1 could not do its work
 template <class SumsOf>
-void groups_finish(LwkzgCellVerifyResult *res, uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_out, const int32_t *rc, const uint32_t *r_raw,
+void groups_finish(LwkzgCellVerifyResult *res, uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_out, int32_t *rc, const uint32_t *r_raw,
                    const uint32_t *flags, const uint32_t *off, size_t g, uint32_t m_total, const KZGSettings *own, int mode, bool failed,
                    const SumsOf &sums_of) {
-    constexpr size_t kPart = LWKZG_CELL_VERIFY_PARTIAL_BYTES;
-    if (partials_out) memset(partials_out, 0, g * kPart);
     if (failed) {
+        if (partials_out) memset(partials_out, 0, g * (size_t)LWKZG_CELL_VERIFY_PARTIAL_BYTES);
         for (size_t j = 0; j < g; j++) rc_out[j] = (int32_t)C_KZG_ERROR, ok_out[j] = 0;
     } else {
-        host_parallel_for(g, [&](size_t j) {
-            rc_out[j] = rc[j];
-            ok_out[j] = rc[j] == (int32_t)C_KZG_OK && off[j + 1] == off[j] ? 1 : 0;
-            if (flags[j]) return;
-            uint8_t *part = partials_out ? partials_out + kPart * j : nullptr;
-            C_KZG_RET f = C_KZG_ERROR;
-            bool ok = false;
-            try {
-                uint8_t sums[3][96], rli48[48];
-                int infs[3];
-                if (part) r_bytes(part, r_raw + 8 * j, mode);
-                f = sums_of(j, sums, infs, rli48) ? cell_batch_finish(&ok, part ? part + 32 : nullptr, sums, infs, rli48, own) : C_KZG_BADARGS;
-            } catch (...) {
-                f = C_KZG_ERROR;
-            }
-            if (f != C_KZG_OK && part) memset(part, 0, kPart);
-            rc_out[j] = (int32_t)f;
-            ok_out[j] = f == C_KZG_OK && ok ? 1 : 0;
-        });
+        groups_answers(ok_out, rc_out, partials_out, rc, r_raw, flags, off, g, own, mode, sums_of);
     }
     uint32_t first_bad = kNoneBad;
     for (size_t j = 0; j < g && first_bad == kNoneBad; j++)
@@ -320,13 +217,13 @@ void cell_verifier_groups_fn1(void *p) {
     AsyncJob *j = (AsyncJob *)p;
     CellVerifier *v = static_cast<CellVerifier *>(j->v);
     const GroupCall &gc = v->gcall[j - v->ring.slots];
-    uint32_t *flags = (uint32_t *)(v->h_up_g + gc.g * kPwWords * sizeof(Fr));
+    uint32_t *flags = v->gp.gflag(gc.g);
     try {
         const uint32_t m = v->h_head[kGroupHeadM];
         j->m = m;
         if (v->h_head[kGroupHeadErr] != 0 || m > j->n || v->h_rowbase[gc.g] != m) j->failed = true;
         else
-            groups_decide(v->g_rc.data(), v->g_r.data(), (Fr *)v->h_up_g, flags, gc.h_off, gc.g, j->n, v->h_rowbase, v->h_gbad, v->h_fault,
+            groups_decide(v->g_rc.data(), v->g_r.data(), v->gp.pw(), flags, gc.h_off, gc.g, j->n, v->h_rowbase, v->h_gbad, v->h_fault,
                           v->h_first, v->h_dig, v->h_comm, j->mode);
     } catch (...) {
         j->failed = true;
@@ -341,13 +238,13 @@ void cell_verifier_groups_fn2(void *p) {
     CellVerifier *v = static_cast<CellVerifier *>(j->v);
     const GroupCall &gc = v->gcall[j - v->ring.slots];
     LwkzgCellVerifyResult *res = (LwkzgCellVerifyResult *)j->res;
-    const uint32_t *flags = (const uint32_t *)(v->h_up_g + gc.g * kPwWords * sizeof(Fr));
+    const uint32_t *flags = v->gp.gflag(gc.g);
     bool failed = j->failed;
     try {
         groups_finish(res, gc.ok_out, gc.rc_out, gc.partials_out, v->g_rc.data(), v->g_r.data(), flags, gc.h_off, gc.g, j->m, &v->own, j->mode,
                       failed, [&](size_t k, uint8_t sums[3][96], int infs[3], uint8_t rli48[48]) {
-                          sums_from_pinned(sums, infs, v->h_sums_g + 3 * 96 * k, (const uint8_t *)(v->h_inf_g + 3 * k));
-                          memcpy(rli48, v->h_rli_g + 48 * k, 48);
+                          sums_from_pinned(sums, infs, v->gp.sums + 3 * 96 * k, (const uint8_t *)(v->gp.inf + 3 * k));
+                          memcpy(rli48, v->gp.rli48 + 48 * k, 48);
                           return true;
                       });
     } catch (...) {   // (the pool could not take the job: nothing of the result is final yet)
@@ -451,15 +348,10 @@ C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t *comms,
         LWK_HIP(hipStreamWaitEvent(st, v->ev_in, 0));
     }
     WsUse wsu(c, st);
-    LWK_HIP(hipMemsetAsync(v->fault, 0, 4 * n, st));
-    LWK_HIP(hipMemsetAsync(b.status, 0, 4 * n, st));
     LWK_HIP(hipMemsetAsync(b.sc_c, 0, 32 * n, st));
     launch_cell_group(comms, idx, n, v->slots, v->seed, 0xffffffffu, v->g, st);
-    launch_cellv_digests(cells, proofs, b.rows, idx, b.digests, v->fault, bad, le, n, st);
     const PointSet set_p{proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
-    launch_decompress_points(set_p, &set_c, n, st);
-    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st);
-    launch_cellv_fault_words(v->fault, b.kind_p, b.kind_c, bad, n, st);
+    LWK_HIP(launch_cellv_first_visit(cells, idx, b.rows, set_p, set_c, b.digests, v->fault, b.status, bad, le, n, st));
     LWK_HIP(hipEventRecord(v->ev_fork, st));
     LWK_HIP(hipStreamWaitEvent(side, v->ev_fork, 0));
     launch_vmsm_multiples2(b.pts_p, b.kind_p, b.tab_p, b.pts_c, b.kind_c, b.tab_c, b.vm_tmp, b.vm_pre, n, side);   // beside the copies and the hash
@@ -527,23 +419,19 @@ C_KZG_RET enqueue_groups_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t 
     const size_t n = j->n, g = gc.g;
     const int le = mode_rules(j->mode).le(), bad = (int)bad_input(j->mode);
     hipStream_t st = c->stream;
-    const Fr *d_pw = (const Fr *)v->pw_g;
-    const uint32_t *d_gflag = (const uint32_t *)(v->pw_g + g * kPwWords * sizeof(Fr));
+    const CellgBufs &gb = v->gb;
+    const Fr *d_pw = gb.pw();
+    const uint32_t *d_gflag = gb.gflag(g);
     if ((rc = async_enqueue_head(v, c)) != C_KZG_OK) return rc;
     if (caller && caller != st) {   // the inputs were produced on the caller's stream
         LWK_HIP(hipEventRecord(v->ev_in, caller));
         LWK_HIP(hipStreamWaitEvent(st, v->ev_in, 0));
     }
     WsUse wsu(c, st);
-    LWK_HIP(hipMemsetAsync(v->fault, 0, 4 * n, st));
-    LWK_HIP(hipMemsetAsync(b.status, 0, 4 * n, st));
     LWK_HIP(hipMemcpyAsync(sg.item_off, gc.h_off, (g + 1) * 4, hipMemcpyHostToDevice, st));
     launch_cell_group_seg(comms, idx, n, g, v->slots, v->seed, 0xffffffffu, sg, st);
-    launch_cellv_digests(cells, proofs, sg.rows, idx, b.digests, v->fault, bad, le, n, st);
     const PointSet set_p{proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
-    launch_decompress_points(set_p, &set_c, n, st);
-    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st);
-    launch_cellv_fault_words(v->fault, b.kind_p, b.kind_c, bad, n, st);
+    LWK_HIP(launch_cellv_first_visit(cells, idx, sg.rows, set_p, set_c, b.digests, v->fault, b.status, bad, le, n, st));
     LWK_HIP(hipMemcpyAsync(v->h_head, sg.head, kGroupHeadWords * 4, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(v->h_rowbase, sg.row_base, (g + 1) * 4, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(v->h_gbad, sg.gbad, g * 4, hipMemcpyDeviceToHost, st));
@@ -553,18 +441,18 @@ C_KZG_RET enqueue_groups_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t 
     LWK_HIP(hipMemcpyAsync(v->h_comm, b.comm_in, 48 * n, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipLaunchHostFunc(st, cell_verifier_groups_fn1, j));
     *hf = 1;
-    LWK_HIP(hipMemcpyAsync(v->pw_g, v->h_up_g, g * kGroupUpBytes, hipMemcpyHostToDevice, st));
+    LWK_HIP(hipMemcpyAsync(gb.up, v->gp.up, g * kGroupUpBytes, hipMemcpyHostToDevice, st));
     const size_t workgroups = plan_max_slices(n, g);   // (at most v->max_slices: n and g are within the verifier's capacities)
-    launch_cell_group_slice_table(sg.item_off, sg.row_base, d_gflag, v->slices, v->slice_off, g, workgroups, st);
+    launch_cell_group_slice_table(sg.item_off, sg.row_base, d_gflag, gb.slices, gb.slice_off, g, workgroups, st);
     LWK_HIP(hipMemsetAsync(b.a_mont, 0, n * sizeof(Fr), st));   // (the row weights read whole rows: a flagged group's stay defined)
     launch_cellg_scalars(d_pw, idx, c->tw_fwd, sg.item_group, sg.item_off, d_gflag, b.a_mont, b.sc_a, b.sc_b, n, st);
     launch_cellv_row_weights(b.a_mont, sg.perm_row, sg.row_off, b.sc_c, n, st, sg.head + kGroupHeadM);
-    launch_cellg_interpolants(c, j->mode, cells, b.a_mont, sg.perm_col, sg.col_off, d_gflag, v->colcoef_g, v->rli_g, le, g, st);
-    launch_cellg_sums(v->slices, v->slice_off, d_gflag, b.sc_a, b.sc_b, b.sc_c, b.pts_p, b.kind_p, b.pts_c, b.kind_c, v->part, v->out96_g,
-                      v->inf_g, workgroups, v->slice_off + 3 * g, g, st);
-    LWK_HIP(hipMemcpyAsync(v->h_sums_g, v->out96_g, 3 * 96 * g, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(v->h_inf_g, v->inf_g, 3 * 4 * g, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(v->h_rli_g, v->rli_g, 48 * g, hipMemcpyDeviceToHost, st));
+    launch_cellg_interpolants(c, j->mode, cells, b.a_mont, sg.perm_col, sg.col_off, d_gflag, gb.colcoef, gb.rli48, le, g, st);
+    launch_cellg_sums(gb.slices, gb.slice_off, d_gflag, b.sc_a, b.sc_b, b.sc_c, b.pts_p, b.kind_p, b.pts_c, b.kind_c, gb.part, gb.out96, gb.inf,
+                      workgroups, gb.slice_off + 3 * g, g, st);
+    LWK_HIP(hipMemcpyAsync(v->gp.sums, gb.out96, 3 * 96 * g, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->gp.inf, gb.inf, 3 * 4 * g, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(v->gp.rli48, gb.rli48, 48 * g, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipGetLastError());
     LWK_HIP(hipLaunchHostFunc(st, cell_verifier_groups_fn2, j));
     *hf = 2;
@@ -680,7 +568,7 @@ C_KZG_RET lwkzg_cell_verifier_host_steps(LwkzgCellVerifyResult *out, const uint8
         }
         Fr pw[33];
         cell_batch_powers(pw, r_raw);   // (step 1's other product; the device takes it)
-        r_bytes(out->partials, r_raw, mode);
+        cell_r_bytes(out->partials, r_raw, mode);
         uint8_t sums[3][96];
         int infs[3];
         rc = sums_from_97(sums, infs, sums3x97) ? cell_batch_finish(&ok, out->partials + 32, sums, infs, rli48, s) : C_KZG_BADARGS;

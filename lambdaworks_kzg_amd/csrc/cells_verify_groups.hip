@@ -4,18 +4,22 @@
 // Group j's answer is by definition lwkzg_verify_cell_kzg_proof_batch on its items alone: its own de-duplication and row numbers, its
 // own transcript header, its own r. One call, one stream, two host visits, under the context's lock:
 //   host     the plan (cell_groups_plan.h): offsets checked, every range grouped by the batch call's rule, the slice table
-//   device   the batch call's own launches over all n items at once: digests with the group-local rows, both point sets validated
-//            (the groups' distinct commitments one after the other, padded with infinity encodings to n); digests, status and kinds
-//            come down
-//   host     every group's fault; g transcripts and g power tables on the host threads
+//   device   the first visit the cell verifier runs too (cells_verify.hip: launch_cellv_first_visit) over all n items at once: digests
+//            with the group-local rows, both point sets validated (the groups' distinct commitments one after the other, padded
+//            with infinity encodings to n), the 2 n fault words; digests and fault words come down
+//   host     every group's fault; g transcripts and g power tables on the host threads (cells_verify_host.h: groups_decide)
 //   device   k_cellg_scalars (a_i = r_j^(i - off_j), b_i = a_i c_(k_i)), the row weights over the concatenated rows, k_cellg_columns /
 //            k_cellg_coeffs (the interpolant of every group into one MSM slot per group, a chunk of kInterpChunk groups at a time), the
 //            engine's MSM over the slots, k_cellg_slices (one 64-lane workgroup per slice of one sum of one group: a scalar product
 //            per lane, the six-level tree of cell_each.cuh) and k_cellg_fold (the slices of a sum); sums and RLIs come down
-//   host     cell_batch_finish per live group on the host threads (the pairing does not re-enter them: it forks by SideTask)
+//   host     cell_batch_finish per live group on the host threads (the pairing does not re-enter them: it forks by SideTask) and the
+//            answers (cells_verify_host.h: groups_answers)
 // A dead (bad index) or faulty group is flagged before the second device visit and nothing there reads its points or its indices.
+// Both host steps are the cell verifier's (cells_verify_async.hip) on the plan's view of the call, and the tests reach them without a
+// GPU (lwkzg_cell_verifier_groups_host_steps). The buffers behind r are CellgBufs / CellgPin (cells_verify_groups.h), the verifier's too.
 #include "abi_guard.h"
 #include "cells_verify_groups.h"
+#include "cells_verify_host.h"
 #include "cellv_bufs.h"
 #include "cell_interp.cuh"
 #include "cell_each.cuh"
@@ -27,8 +31,6 @@
 #include <vector>
 
 namespace lwk {
-
-void host_parallel_for(size_t n, const std::function<void(size_t)> &fn);  // sha256_host.hip: persistent workers
 
 namespace {
 
@@ -247,90 +249,49 @@ void launch_cellg_sums(const GroupSlice *slices, const uint32_t *slice_off, cons
 namespace {
 
 // ---- the device side of a call, carved out of one allocation ---------------------------------------------------------------------------------
-// cap counts units: a call of n items in g groups needs max(n, g) of them
-struct Bufs {
-    uint8_t *cells, *proofs, *comm_in, *canon_p, *canon_c, *digests, *out96, *rli48;
-    uint64_t *idx;
-    uint32_t *rows, *perm_row, *row_off, *perm_col, *col_off, *verdict_p, *verdict_c, *sc_a, *sc_b, *sc_c, *item_group, *item_off, *gflag, *slice_off;
-    int32_t *kind_p, *kind_c, *status, *vstatus, *inf;
-    G1Affine29 *pts_p, *pts_c;
-    GroupSlice *slices;
-    G1Xyzz *part;
-    Fr *a_mont, *pw, *colcoef;
+// cap counts units: a call of n items in g groups needs max(n, g) of them. A batch's buffers without what the batch call alone runs
+// behind r, a column list per group (cellv_bufs.h); what a grouped call runs there; the plan's two item lists and the fault words
+struct DevSide {
+    CellvBufs b;      // (carved without the batch call's own: b.out96, rli48, inf, pw, colcoef, tab_*, vm_*, partial, bsum are EMPTY -- gb has a grouped call's)
+    CellgBufs gb;
+    uint32_t *item_group, *item_off;
+    int32_t *fault;   // 2 cap words (k_cellv_fault_words)
 };
 
-size_t carve(Bufs &b, uint8_t *base, size_t cap) {
+size_t carve(DevSide &b, uint8_t *base, size_t cap) {
     Carver cv(base);
-    const size_t slices = plan_max_slices(cap, cap);
-    cv.take(b.cells, cap * kCellBytes);
-    cv.take(b.proofs, cap * 48);
-    cv.take(b.comm_in, cap * 48);
-    cv.take(b.canon_p, cap * 48);
-    cv.take(b.canon_c, cap * 48);
-    cv.take(b.digests, cap * 32);
-    cv.take(b.out96, cap * 3 * 96);
-    cv.take(b.rli48, cap * 48);
-    cv.take(b.idx, cap * 8);
-    cv.take(b.rows, cap * 4);
-    cv.take(b.perm_row, cap * 4);
-    cv.take(b.row_off, (cap + 1) * 4);
-    cv.take(b.perm_col, cap * 4);
-    cv.take(b.col_off, (cap * kCellsPerBlob + 1) * 4);
-    cv.take(b.verdict_p, cap * 4);
-    cv.take(b.verdict_c, cap * 4);
-    cv.take(b.sc_a, cap * 32);
-    cv.take(b.sc_b, cap * 32);
-    cv.take(b.sc_c, cap * 32);
+    cellv_carve(b.b, cv, cap, true, false, cap);
+    cellg_carve(b.gb, cv, cap, plan_max_slices(cap, cap));
     cv.take(b.item_group, cap * 4);
     cv.take(b.item_off, (cap + 1) * 4);
-    cv.take(b.gflag, cap * 4);
-    cv.take(b.slice_off, (3 * cap + 1) * 4);
-    cv.take(b.kind_p, cap * 4);
-    cv.take(b.kind_c, cap * 4);
-    cv.take(b.status, cap * 4);
-    cv.take(b.vstatus, cap * 4);
-    cv.take(b.inf, cap * 3 * 4);
-    cv.take(b.pts_p, cap * sizeof(G1Affine29));
-    cv.take(b.pts_c, cap * sizeof(G1Affine29));
-    cv.take(b.slices, slices * sizeof(GroupSlice));
-    cv.take(b.part, slices * sizeof(G1Xyzz));
-    cv.take(b.a_mont, cap * sizeof(Fr));
-    cv.take(b.pw, cap * kPwWords * sizeof(Fr));
-    cv.take(b.colcoef, kInterpChunk * kInterpGroupBytes);
+    cv.take(b.fault, 2 * cap * 4);
     return cv.bytes();
 }
 
 // the pinned side: what comes down and goes up, per unit
-struct Pin {
-    uint8_t *digests, *sums, *rli48;
-    int32_t *status, *kind_p, *kind_c, *inf;
-    uint32_t *gflag;
-    Fr *pw;
+struct PinSide {
+    CellgPin gp;
+    uint8_t *digests;
+    int32_t *fault;
 };
 
-size_t carve_pin(Pin &p, uint8_t *base, size_t cap) {
+size_t carve_pin(PinSide &p, uint8_t *base, size_t cap) {
     Carver cv(base);
+    cellg_carve_pin(p.gp, cv, cap);
     cv.take(p.digests, cap * 32);
-    cv.take(p.sums, cap * 3 * 96);
-    cv.take(p.rli48, cap * 48);
-    cv.take(p.status, cap * 4);
-    cv.take(p.kind_p, cap * 4);
-    cv.take(p.kind_c, cap * 4);
-    cv.take(p.inf, cap * 3 * 4);
-    cv.take(p.gflag, cap * 4);
-    cv.take(p.pw, cap * kPwWords * sizeof(Fr));
+    cv.take(p.fault, 2 * cap * 4);
     return cv.bytes();
 }
 
 // grow-only, kept with the settings object: first 256 units, then doubling; no allocation in steady state (caller holds c->mu)
-C_KZG_RET reserve(Ctx *c, size_t units, Bufs &b, Pin &p) {
+C_KZG_RET reserve(Ctx *c, size_t units, DevSide &b, PinSide &p) {
     if (c->cellg.cap < units) {
         size_t bytes = 0;
-        C_KZG_RET rc = grow_reserve(c->cellg, units, 256, [&](size_t cap) { Bufs probe; return bytes = carve(probe, nullptr, cap); }, nullptr);
+        C_KZG_RET rc = grow_reserve(c->cellg, units, 256, [&](size_t cap) { DevSide probe; return bytes = carve(probe, nullptr, cap); }, nullptr);
         if (rc == C_KZG_ERROR) return rc;   // the wait failed: both buffers are as they were
         if (c->cellg_pin) hipHostFree(c->cellg_pin);
         c->cellg_pin = nullptr;
-        Pin probe;
+        PinSide probe;
         if (rc == C_KZG_OK && hipHostMalloc((void **)&c->cellg_pin, carve_pin(probe, nullptr, c->cellg.cap)) != hipSuccess) {
             (void)hipGetLastError();
             grow_free(c->cellg);
@@ -376,14 +337,10 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
     const auto t0 = std::chrono::steady_clock::now();
     const int mode = mode_of(s);
     const int le = mode_rules(mode).le();
-    auto answer = [&](size_t j, C_KZG_RET rc, bool ok) {
-        if (partials_out) return;
-        rc_out[j] = rc;
-        ok_out[j] = rc == C_KZG_OK && ok ? 1 : 0;
-    };
     if (n == 0) {   // empty groups alone: the batch call's answer to n == 0, without a context
         if (partials_out) memset(partials_out, 0, g * (size_t)LWKZG_CELL_VERIFY_PARTIAL_BYTES);
-        for (size_t j = 0; j < g; j++) answer(j, C_KZG_OK, true);
+        else
+            for (size_t j = 0; j < g; j++) rc_out[j] = (int32_t)C_KZG_OK, ok_out[j] = 1;
         return C_KZG_OK;
     }
     const uint8_t *comms = (const uint8_t *)comms_v, *cells = (const uint8_t *)cells_v, *proofs = (const uint8_t *)proofs_v;
@@ -410,11 +367,14 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
         plan_groups(plan, h_comms.data(), h_idx.data(), n, offsets, g);
     }
     const auto t1 = std::chrono::steady_clock::now();
-    Bufs b;
-    Pin pin;
-    C_KZG_RET rc = reserve(c, n > g ? n : g, b, pin);
+    DevSide dev;
+    PinSide pin;
+    C_KZG_RET rc = reserve(c, n > g ? n : g, dev, pin);
     if (rc != C_KZG_OK) return rc;
     if ((rc = ctx_reserve(c, g)) != C_KZG_OK) return rc;   // (at most one launch set of slots)
+    const CellvBufs &b = dev.b;
+    const CellgBufs &gb = dev.gb;
+    const CellgPin &gp = pin.gp;
     WsUse wsu(c, st);
     StreamDrain drain{st};   // nothing of this call is in flight when it returns, whatever the exit
     PhaseClock clk;
@@ -431,118 +391,74 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
         LWK_HIP(hipMemcpyAsync(b.idx, idx, 8 * n, hipMemcpyHostToDevice, st));
         d_cells = b.cells, d_proofs = b.proofs, d_idx = b.idx;
     }
-    LWK_HIP(hipMemsetAsync(b.status, 0, 4 * n, st));
-    LWK_HIP(hipMemsetAsync(b.vstatus, 0, 4 * n, st));
     clk.mark(0);
-    const int bad = (int)bad_input(mode);
-    launch_cellv_digests(d_cells, d_proofs, b.rows, d_idx, b.digests, b.status, bad, le, n, st);
-    clk.mark(1);
     const PointSet set_p{d_proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
-    launch_decompress_points(set_p, &set_c, n, st);
-    launch_subgroup_canon(set_p, &set_c, b.vstatus, bad, n, st);   // (its one word per index mixes item i and row i: the kinds tell them apart)
+    LWK_HIP(launch_cellv_first_visit(d_cells, d_idx, b.rows, set_p, set_c, b.digests, dev.fault, b.status, (int)bad_input(mode), le, n, st,
+                                     clk.on ? clk.ev[1] : nullptr));
     clk.mark(2);
     LWK_HIP(hipMemcpyAsync(pin.digests, b.digests, 32 * n, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(pin.status, b.status, 4 * n, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(pin.kind_p, b.kind_p, 4 * n, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(pin.kind_c, b.kind_c, 4 * n, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hipMemcpyAsync(pin.fault, dev.fault, 8 * n, hipMemcpyDeviceToHost, st));
     // the lists of the second visit go up beside the first visit's kernels
     LWK_HIP(upload(b.perm_row, plan.perm_row, st));
     LWK_HIP(upload(b.row_off, plan.row_off, st));
     LWK_HIP(upload(b.perm_col, plan.perm_col, st));
     LWK_HIP(upload(b.col_off, plan.col_off, st));
-    LWK_HIP(upload(b.item_group, plan.item_group, st));
-    LWK_HIP(upload(b.item_off, plan.item_off, st));
-    LWK_HIP(upload(b.slice_off, plan.slice_off, st));
+    LWK_HIP(upload(dev.item_group, plan.item_group, st));
+    LWK_HIP(upload(dev.item_off, plan.item_off, st));
+    LWK_HIP(upload(gb.slice_off, plan.slice_off, st));
     if (!plan.slices.empty())
-        LWK_HIP(hipMemcpyAsync(b.slices, plan.slices.data(), plan.slices.size() * sizeof(GroupSlice), hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(gb.slices, plan.slices.data(), plan.slices.size() * sizeof(GroupSlice), hipMemcpyHostToDevice, st));
     LWK_HIP(hipGetLastError());
     LWK_HIP(hipStreamSynchronize(st));
     const auto t2 = std::chrono::steady_clock::now();
 
-    // ---- the host decides every group's fault; a bad commitment counts for the group whose row it is ----
-    std::vector<uint8_t> live(g, 0);
-    size_t n_live = 0;
-    for (size_t j = 0; j < g; j++) {
-        const uint32_t lo = plan.item_off[j], hi = plan.item_off[j + 1];
-        pin.gflag[j] = 1;
-        if (lo == hi) {
-            answer(j, C_KZG_OK, true);
-            continue;
-        }
-        if (plan.dead[j]) {
-            answer(j, C_KZG_BADARGS, false);
-            continue;
-        }
-        bool fault = false;
-        for (uint32_t i = lo; i < hi && !fault; i++) fault = pin.status[i] != 0 || pin.kind_p[i] == 2;
-        for (uint32_t q = plan.row_base[j]; q < plan.row_base[j + 1] && !fault; q++) fault = pin.kind_c[q] == 2;
-        if (fault) {
-            answer(j, bad_input(mode), false);
-            continue;
-        }
-        pin.gflag[j] = 0;
-        live[j] = 1;
-        n_live++;
-    }
-    if (n_live == 0) return C_KZG_OK;
+    // ---- the host decides every group's fault, then g transcripts and g power tables (cells_verify_host.h: the verifier's step 1 on the
+    // plan's view of the call; nobody asks where in a group the fault is, so there is no first_item) ----
+    std::vector<int32_t> grc(g);
     std::vector<uint32_t> r_raw(8 * g, 0);
-    host_parallel_for(g, [&](size_t j) {
-        if (!live[j]) return;
-        const uint32_t lo = plan.item_off[j], cnt = plan.item_off[j + 1] - lo, rb = plan.row_base[j];
-        cell_batch_challenge(&r_raw[8 * j], plan.distinct.data() + 48 * (size_t)rb, plan.row_base[j + 1] - rb, pin.digests + 32 * (size_t)lo, cnt, le);
-        cell_batch_powers(pin.pw + kPwWords * j, &r_raw[8 * j]);
-    });
+    uint32_t *flags = gp.gflag(g);
+    groups_decide(grc.data(), r_raw.data(), gp.pw(), flags, plan.item_off.data(), g, n, plan.row_base.data(), plan.dead.data(), pin.fault, nullptr,
+                  pin.digests, plan.distinct.data(), mode);
+    size_t n_live = 0;
+    for (size_t j = 0; j < g; j++) n_live += flags[j] == 0;
     const auto t3 = std::chrono::steady_clock::now();
 
-    // ---- second visit ----
-    LWK_HIP(hipMemcpyAsync(b.pw, pin.pw, g * kPwWords * sizeof(Fr), hipMemcpyHostToDevice, st));
-    LWK_HIP(hipMemcpyAsync(b.gflag, pin.gflag, 4 * g, hipMemcpyHostToDevice, st));
-    LWK_HIP(hipMemsetAsync(b.a_mont, 0, n * sizeof(Fr), st));   // (the row weights read whole rows: a flagged group's stay defined)
-    clk.mark(3);
-    launch_cellg_scalars(b.pw, d_idx, c->tw_fwd, b.item_group, b.item_off, b.gflag, b.a_mont, b.sc_a, b.sc_b, n, st);
-    launch_cellv_row_weights(b.a_mont, b.perm_row, b.row_off, b.sc_c, plan.m_total, st);
-    clk.mark(4);
-    launch_cellg_interpolants(c, mode, d_cells, b.a_mont, b.perm_col, b.col_off, b.gflag, b.colcoef, b.rli48, le, g, st);
-    clk.mark(5);
-    launch_cellg_sums(b.slices, b.slice_off, b.gflag, b.sc_a, b.sc_b, b.sc_c, b.pts_p, b.kind_p, b.pts_c, b.kind_c, b.part, b.out96, b.inf,
-                      plan.slices.size(), nullptr, g, st);
-    clk.mark(6);
-    LWK_HIP(hipMemcpyAsync(pin.sums, b.out96, 3 * 96 * g, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(pin.inf, b.inf, 3 * 4 * g, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(pin.rli48, b.rli48, 48 * g, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipGetLastError());
-    LWK_HIP(hipStreamSynchronize(st));
+    // ---- second visit: never enqueued when no group is live ----
+    if (n_live != 0) {
+        LWK_HIP(hipMemcpyAsync(gb.up, gp.up, g * kGroupUpBytes, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemsetAsync(b.a_mont, 0, n * sizeof(Fr), st));   // (the row weights read whole rows: a flagged group's stay defined)
+        clk.mark(3);
+        launch_cellg_scalars(gb.pw(), d_idx, c->tw_fwd, dev.item_group, dev.item_off, gb.gflag(g), b.a_mont, b.sc_a, b.sc_b, n, st);
+        launch_cellv_row_weights(b.a_mont, b.perm_row, b.row_off, b.sc_c, plan.m_total, st);
+        clk.mark(4);
+        launch_cellg_interpolants(c, mode, d_cells, b.a_mont, b.perm_col, b.col_off, gb.gflag(g), gb.colcoef, gb.rli48, le, g, st);
+        clk.mark(5);
+        launch_cellg_sums(gb.slices, gb.slice_off, gb.gflag(g), b.sc_a, b.sc_b, b.sc_c, b.pts_p, b.kind_p, b.pts_c, b.kind_c, gb.part, gb.out96,
+                          gb.inf, plan.slices.size(), nullptr, g, st);
+        clk.mark(6);
+        LWK_HIP(hipMemcpyAsync(gp.sums, gb.out96, 3 * 96 * g, hipMemcpyDeviceToHost, st));
+        LWK_HIP(hipMemcpyAsync(gp.inf, gb.inf, 3 * 4 * g, hipMemcpyDeviceToHost, st));
+        LWK_HIP(hipMemcpyAsync(gp.rli48, gb.rli48, 48 * g, hipMemcpyDeviceToHost, st));
+        LWK_HIP(hipGetLastError());
+        LWK_HIP(hipStreamSynchronize(st));
+    }
     const auto t4 = std::chrono::steady_clock::now();
 
-    // ---- the pairing of every live group on the host threads (cell_batch_finish forks by SideTask, never by host_parallel_for) ----
-    std::vector<int32_t> frc(g, (int32_t)C_KZG_OK);
-    std::vector<uint8_t> fok(g, 0);
-    const bool r_le = mode_rules(mode).little_endian;
-    host_parallel_for(g, [&](size_t j) {
-        if (!live[j]) return;
-        uint8_t sums[3][96];
-        int infs[3];
-        for (int k = 0; k < 3; k++) {
-            memcpy(sums[k], pin.sums + 96 * (3 * j + k), 96);
-            infs[k] = pin.inf[3 * j + k];
-        }
-        uint8_t *part = partials_out ? partials_out + (size_t)LWKZG_CELL_VERIFY_PARTIAL_BYTES * j : nullptr;
-        if (part) {
-            if (r_le) raw_to_le<8>(part, &r_raw[8 * j]);
-            else raw_to_be<8>(part, &r_raw[8 * j]);
-        }
-        bool ok = false;
-        frc[j] = (int32_t)cell_batch_finish(partials_out ? nullptr : &ok, part ? part + 32 : nullptr, sums, infs, pin.rli48 + 48 * j, s);
-        fok[j] = ok;
-    });
-    for (size_t j = 0; j < g; j++) {
-        if (!live[j]) continue;
-        if (frc[j] != (int32_t)C_KZG_OK) {
+    // ---- the pairing of every live group on the host threads, against the caller's settings, and the answers (the verifier's step 2).
+    // A call without a live group comes here too, for its flagged groups' answers and zero partials; every group's answer is written
+    // before a failed finish makes the call C_KZG_ERROR ----
+    groups_answers(ok_out, rc_out, partials_out, grc.data(), r_raw.data(), flags, plan.item_off.data(), g, s, mode,
+                   [&](size_t j, uint8_t sums[3][96], int infs[3], uint8_t rli48[48]) {
+                       sums_from_pinned(sums, infs, gp.sums + 3 * 96 * j, (const uint8_t *)(gp.inf + 3 * j));
+                       memcpy(rli48, gp.rli48 + 48 * j, 48);
+                       return true;
+                   });
+    for (size_t j = 0; j < g; j++)
+        if (!flags[j] && grc[j] != (int32_t)C_KZG_OK) {
             set_error("verify_cell_kzg_proof_groups: the interpolant's commitment of group %zu is not a point", j);
             return C_KZG_ERROR;
         }
-        answer(j, C_KZG_OK, fok[j] != 0);
-    }
+    if (n_live == 0) return C_KZG_OK;   // (no second visit, so no timing line)
     if (clk.on)
         fprintf(stderr, "[lambdaworks_kzg_amd] verify cell groups n=%zu g=%zu rows=%zu slices=%zu live=%zu: host plan %.3f ms | device: digests %.3f, "
                         "validation %.3f, scalars + row weights %.3f, interpolants + MSM %.3f, slices + fold %.3f ms | host: until the first "

@@ -334,6 +334,14 @@ void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint
 // cells_verify_async.hip: fault (2 n words) -- [i] keeps the digests' word of item i and takes proof i's verdict, [n + j] is distinct
 // commitment j's -- from the kinds the validation left
 void launch_cellv_fault_words(int32_t *fault, const int32_t *kind_p, const int32_t *kind_c, int bad_code, size_t n, hipStream_t st);
+// The first visit of the calls that say WHERE a fault is (the cell verifier's batch and grouped calls, the synchronous grouped call): the
+// fills of fault's first n words and of status, the digests (their word into fault[i]), both point sets decompressed and checked -- set_p
+// the n proofs, set_c the distinct commitments padded to n; status takes subgroup_canon's mixed words, which nobody reads --, the fault
+// words. digests_done: an event recorded between the digests and the validation (the synchronous call's timing line), or nullptr.
+// Returns the fills' and the record's error; nothing is read back
+hipError_t launch_cellv_first_visit(const uint8_t *cells, const uint64_t *idx, const uint32_t *rows, const PointSet &set_p, const PointSet &set_c,
+                                    uint8_t *digests32, int32_t *fault, int32_t *status, int bad_code, int le, size_t n, hipStream_t st,
+                                    hipEvent_t digests_done = nullptr);
 
 // ---- grouping the items of a cell proof batch on the device (cell_group.hip, pieces in cell_group.cuh)
 // Scratch and outputs of one grouping, all device memory. Capacities for n items over a table of `slots` slots (cell_group.cuh:

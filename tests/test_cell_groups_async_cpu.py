@@ -167,3 +167,52 @@ def test_host_steps_rejected_groups_read_nothing_behind_what_decides_them(K, ora
         capi.cell_verifier_groups_host_steps(sizes, row_base, [0, 1, 0, 0, 0], [0] * (2 * n), [3, 4], None, None, None, None, C.byref(s), mode)
     assert e.value.rc == K.C_KZG_BADARGS
     del keep
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_host_steps_one_fault_of_each_kind_in_the_order_the_synchronous_call_meets_them(K, oracle, mode):
+    """The host steps are one piece of code (cells_verify_host.h) for the verifier and for lwkzg_verify_cell_kzg_proof_groups, so the
+    synchronous call's decisions are reachable here: empty | a bad index | a cell element out of range at the group's last item | a
+    bad commitment whose row is first seen at the group's second item | honest. The exact (rc, ok) vector, zero partials for the
+    first four, and the hook's refusal of a call without ok_out and rc_out (partials alone are the synchronous
+    lwkzg_cell_verify_groups_partials' form, never the hook's: refused with nothing written, as before the host steps were shared).
+    Not reachable from here: the synchronous call hands the shared steps no first_item (first_fault then counts a bad commitment at
+    item 0), and the hook refuses a NULL first_item; that one branch is covered by tests/test_gpu_cell_groups_one_host_side.py alone."""
+    from lambdaworks_kzg_amd import capi
+    s, keep = _hand_built_settings(capi, oracle)
+    a, b = Poly.seeded(oracle, 3000), Poly.seeded(oracle, 3001)
+    honest = [a.item(5, mode), b.item(5, mode), a.item(64, mode), b.item(5, mode), a.item(127, mode)]
+    dist, dig, first, sums97, rli48, _, _ = _blocks(oracle, honest, mode)
+    sizes = [0, 2, 3, 3, len(honest)]
+    n, g = sum(sizes), len(sizes)
+    off = [sum(sizes[:j]) for j in range(g + 1)]
+    mode_code = K.C_KZG_BADARGS if mode == S.MODE_CKZG else K.C_KZG_ERROR
+    row_base = [0, 0, 0, 2, 4, 4 + len(dist)]      # the empty and the dead group have no rows; groups 2 and 3 two each
+    m_total = row_base[-1]
+    distinct = [bytes([0xc0]) + bytes(47)] * 4 + list(dist)
+    first_item = [off[2], off[2] + 1, off[3], off[3] + 1] + [off[4] + f for f in first]
+    digests = b"\x5a" * (32 * off[4]) + dig        # (what a rejected group would hash if it read them)
+    sums, rli = bytes(3 * 97 * 4) + sums97, bytes(48 * 4) + rli48
+    status = [0] * (2 * n)
+    status[off[3] - 1] = mode_code                 # group 2: an element of its last item's cell
+    status[n + row_base[3] + 1] = mode_code        # group 3: its second row, first seen at its second item
+    bad_words = [0, 1, 0, 0, 0]
+    res, answers, partials = capi.cell_verifier_groups_host_steps(sizes, row_base, bad_words, status, first_item, digests, b"".join(distinct),
+                                                                  sums, rli, C.byref(s), mode)
+    assert answers == [(K.C_KZG_OK, True), (K.C_KZG_BADARGS, False), (mode_code, False), (mode_code, False), (K.C_KZG_OK, True)]
+    assert (res.state, res.rc, res.ok, res.first_bad, res.m) == (1, K.C_KZG_OK, 0, 1, m_total)
+    for j in range(4):
+        assert partials[j] == bytes(capi.CELL_VERIFY_PARTIAL_BYTES), j
+    alone = capi.cell_verifier_host_steps(b"".join(dist), len(dist), dig, len(honest), NONE_BAD, [0] * (2 * len(honest)), first, sums97, rli48,
+                                          C.byref(s), mode)
+    assert (alone.rc, alone.ok) == (K.C_KZG_OK, 1) and partials[4] == bytes(alone.partials) != bytes(capi.CELL_VERIFY_PARTIAL_BYTES)
+    # ok_out = rc_out = NULL with partials_out given: BADARGS, the result complete, the partials untouched
+    out = C.create_string_buffer(b"\x11" * (g * capi.CELL_VERIFY_PARTIAL_BYTES), g * capi.CELL_VERIFY_PARTIAL_BYTES)
+    res = K.CellVerifyResult()
+    u32 = C.c_uint32
+    rc = K.lib().lwkzg_cell_verifier_groups_host_steps(C.byref(res), None, None, out, (C.c_uint64 * (g + 1))(*off), g, n,
+                                                       (u32 * (g + 1))(*row_base), (u32 * g)(*bad_words), (C.c_int32 * (2 * n))(*status),
+                                                       (u32 * m_total)(*first_item), digests, b"".join(distinct), sums, rli, C.byref(s), mode)
+    assert rc == K.C_KZG_BADARGS and (res.state, res.rc, res.ok, res.first_bad) == (1, K.C_KZG_BADARGS, 0, NONE_BAD)
+    assert out.raw == b"\x11" * (g * capi.CELL_VERIFY_PARTIAL_BYTES)
+    del keep
