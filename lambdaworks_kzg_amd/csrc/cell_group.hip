@@ -19,7 +19,10 @@
 // An index >= 128 is never a bin or a subscript here: such an item is left out of the column list, and the verifier's skip word keeps
 // everything that reads idx[] as a subscript from running.
 // The second half of the file is the same for a call of g groups (k_seg_*: the segmented grouping and the slice table of a cell
-// verifier's grouped calls; lwkzg_cell_group_segmented_device is its test hook).
+// verifier's grouped calls; lwkzg_cell_group_segmented_device is its test hook). What the two do alike is
+// written once: the probe of the table (group_probe), and k_group_scan and k_group_offsets, which both launch as they are. What they
+// do differently stays two kernels: the batch keeps a row for every item, whatever its index, and bins columns in LDS; a group with a
+// bad index has no rows at all, and its bins are (group, column) pairs in HBM.
 #include "abi_guard.h"
 #include "carve.h"
 #include "cell_group.cuh"
@@ -59,6 +62,30 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *w
     return before + inc - v;
 }
 
+// Item i (key: its 48 bytes) into the table, probing from slot s: the slot it claimed or shares with the items of its key, or
+// kGroupEmpty where the probe ran out or met a word no lane of this launch writes. may_share(c): may item c be of i's row at all (a
+// segmented grouping: only an item of i's group) -- asked before c's bytes are read.
+template <class MayShare>
+__device__ __forceinline__ uint32_t group_probe(const uint8_t *__restrict__ comms, uint32_t *__restrict__ table, const uint64_t key[6], uint32_t s,
+                                                uint32_t i, uint32_t n, uint32_t slot_mask, MayShare may_share) {
+    uint32_t found = kGroupEmpty;
+#pragma unroll 1
+    for (uint32_t probe = 0; probe <= slot_mask; probe++, s = (s + 1) & slot_mask) {
+        const uint32_t c = atomicCAS(&table[s], kGroupEmpty, i);
+        if (c == kGroupEmpty) {   // claimed
+            found = s;
+            break;
+        }
+        if (c >= n) break;        // (no lane writes such a word: the table is not this launch's)
+        if (may_share(c) && group_equal48(key, comms + 48 * (size_t)c)) {
+            atomicMin(&table[s], i);
+            found = s;
+            break;
+        }
+    }
+    return found;
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(kGroupLanes) void k_group_insert(const uint8_t *__restrict__ comms, const uint64_t *__restrict__ idx,
@@ -70,22 +97,8 @@ __global__ __launch_bounds__(kGroupLanes) void k_group_insert(const uint8_t *__r
     if (idx[i] >= (uint64_t)kGroupColumns) atomicMax(&head[kGroupHeadBad], ~i);
     uint64_t key[6];
     group_load48(key, comms + 48 * (size_t)i);
-    uint32_t s = group_slot_hash(key, seed, hash_mask) & slot_mask;
-    uint32_t found = kGroupEmpty;
-#pragma unroll 1
-    for (uint32_t probe = 0; probe <= slot_mask; probe++, s = (s + 1) & slot_mask) {
-        const uint32_t c = atomicCAS(&table[s], kGroupEmpty, i);
-        if (c == kGroupEmpty) {   // claimed
-            found = s;
-            break;
-        }
-        if (c >= n) break;        // (no lane writes such a word: the table is not this launch's)
-        if (group_equal48(key, comms + 48 * (size_t)c)) {
-            atomicMin(&table[s], i);
-            found = s;
-            break;
-        }
-    }
+    uint32_t found = group_probe(comms, table, key, group_slot_hash(key, seed, hash_mask) & slot_mask, i, n, slot_mask,
+                                 [](uint32_t) { return true; });
     if (found == kGroupEmpty) {
         atomicOr(&head[kGroupHeadErr], 1u);
         found = 0;
@@ -93,22 +106,25 @@ __global__ __launch_bounds__(kGroupLanes) void k_group_insert(const uint8_t *__r
     slot_of[i] = found;
 }
 
+// pre (nullptr for the batch): the flags' exclusive scan itself, pre[i] for i <= n -- what the segmented grouping reads a group's first
+// row off. An item without a slot (slot_of[i] == kGroupEmpty: only the segmented insertion leaves one) is nobody's first occurrence.
 __global__ __launch_bounds__(kScanLanes) void k_group_scan(const uint8_t *__restrict__ comms, const uint32_t *__restrict__ table,
                                                            const uint32_t *__restrict__ slot_of, uint32_t *__restrict__ slot_row,
                                                            uint32_t *__restrict__ first_item, uint8_t *__restrict__ distinct,
-                                                           uint32_t *__restrict__ head, uint32_t n) {
+                                                           uint32_t *__restrict__ pre, uint32_t *__restrict__ head, uint32_t n) {
     __shared__ uint32_t wave_tot[kScanWaves];
     uint32_t run = 0;
 #pragma unroll 1
     for (uint32_t base = 0; base < n; base += kScanLanes) {   // (n is the same for every lane: they all meet the barriers)
         const uint32_t i = base + threadIdx.x;
-        uint32_t s = 0, flag = 0;
+        uint32_t s = kGroupEmpty, flag = 0;
         if (i < n) {
             s = slot_of[i];
-            flag = table[s] == i ? 1u : 0u;
+            flag = s != kGroupEmpty && table[s] == i ? 1u : 0u;
         }
         uint32_t total;
         const uint32_t before = block_exclusive_scan(flag, wave_tot, &total);
+        if (pre && i < n) pre[i] = run + before;
         if (flag) {
             const uint32_t row = run + before;   // < n: at most one flag per item
             slot_row[s] = row;
@@ -120,7 +136,10 @@ __global__ __launch_bounds__(kScanLanes) void k_group_scan(const uint8_t *__rest
         }
         run += total;
     }
-    if (threadIdx.x == 0) head[kGroupHeadM] = run;
+    if (threadIdx.x == 0) {
+        head[kGroupHeadM] = run;
+        if (pre) pre[n] = run;
+    }
 }
 
 __global__ __launch_bounds__(kGroupLanes) void k_group_rows(const uint64_t *__restrict__ idx, const uint32_t *__restrict__ slot_of,
@@ -152,16 +171,17 @@ __global__ __launch_bounds__(kGroupLanes) void k_group_rows(const uint64_t *__re
     if (threadIdx.x < kGroupColumns && bins[threadIdx.x]) atomicAdd(&col_cnt[threadIdx.x], bins[threadIdx.x]);
 }
 
-// workgroup 0: row_off[0 .. m] from row_cnt; workgroup 1: col_off[0 .. 128] from col_cnt
+// workgroup 0: row_off[0 .. m] from row_cnt; workgroup 1: col_off[0 .. cols] from col_cnt (cols: 128 for the batch, 128 g for a call
+// of g groups)
 __global__ __launch_bounds__(kScanLanes) void k_group_offsets(const uint32_t *__restrict__ row_cnt, const uint32_t *__restrict__ col_cnt,
                                                               uint32_t *__restrict__ row_off, uint32_t *__restrict__ col_off,
-                                                              const uint32_t *__restrict__ head, uint32_t n) {
+                                                              const uint32_t *__restrict__ head, uint32_t n, uint32_t cols) {
     __shared__ uint32_t wave_tot[kScanWaves];
-    const bool cols = blockIdx.x != 0;
-    const uint32_t *cnt = cols ? col_cnt : row_cnt;
-    uint32_t *off = cols ? col_off : row_off;
-    uint32_t len = cols ? kGroupColumns : head[kGroupHeadM];
-    if (len > n && !cols) len = n;
+    const bool by_col = blockIdx.x != 0;
+    const uint32_t *cnt = by_col ? col_cnt : row_cnt;
+    uint32_t *off = by_col ? col_off : row_off;
+    uint32_t len = by_col ? cols : head[kGroupHeadM];
+    if (len > n && !by_col) len = n;
     uint32_t run = 0;
 #pragma unroll 1
     for (uint32_t base = 0; base < len; base += kScanLanes) {
@@ -219,7 +239,7 @@ void launch_cell_group(const uint8_t *comms48, const uint64_t *idx, size_t n, si
     {
         ProfScope p("k_group_scan", st);
         hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(kScanLanes), 0, st, comms48, (const uint32_t *)g.table, (const uint32_t *)g.slot_of,
-                           g.slot_row, g.first_item, g.distinct, g.head, n32);
+                           g.slot_row, g.first_item, g.distinct, (uint32_t *)nullptr, g.head, n32);
     }
     {
         ProfScope p("k_group_rows", st);
@@ -229,7 +249,7 @@ void launch_cell_group(const uint8_t *comms48, const uint64_t *idx, size_t n, si
     {
         ProfScope p("k_group_offsets", st);
         hipLaunchKernelGGL(k_group_offsets, dim3(2), dim3(kScanLanes), 0, st, (const uint32_t *)g.row_cnt, (const uint32_t *)g.col_cnt,
-                           g.row_off, g.col_off, (const uint32_t *)g.head, n32);
+                           g.row_off, g.col_off, (const uint32_t *)g.head, n32, kGroupColumns);
     }
     ProfScope p("k_group_scatter", st);
     hipLaunchKernelGGL(k_group_scatter, per_item, dim3(kGroupLanes), 0, st, idx, (const uint32_t *)g.rows, (const uint32_t *)g.row_off,
@@ -245,11 +265,11 @@ void launch_cell_group(const uint8_t *comms48, const uint64_t *idx, size_t n, si
 //   k_seg_insert      k_group_insert with the group in the slot hash and in the equality test. Whether the item found in a slot is of
 //                     the same group is read off the OFFSETS (immutable), not off another lane's store. The items of a group with a
 //                     bad word take no slot.
-//   k_seg_scan        one workgroup: the flags' exclusive scan pre[i] (pre[n] = M); a first occurrence writes slot_row, first_item, distinct
+//   k_group_scan      as above, and it keeps the flags' exclusive scan pre[i] (pre[n] = M)
 //   k_seg_rows        the concatenated row of every item (kept in slot_of), its group-local row, both histograms (in HBM: the bins are
 //                     (group, column) pairs), row_base[j] = pre[item_off[j]] -- right for an empty group and for groups at the very
 //                     end, whose offset is n -- and the infinity encodings behind the M-th distinct commitment
-//   k_seg_offsets     two workgroups: the exclusive scans row_off[M + 1] and col_off[128 g + 1]
+//   k_group_offsets   as above: the exclusive scans row_off[M + 1] and col_off[128 g + 1]
 //   k_seg_scatter     perm_row / perm_col, places counted down from the counters as in k_group_scatter
 // An index >= 128 is never a bin or a subscript: its whole group has no slot, row, column or place in a list.
 namespace {
@@ -293,55 +313,10 @@ __global__ __launch_bounds__(kGroupLanes) void k_seg_insert(const uint8_t *__res
     const uint32_t lo = item_off[j], hi = item_off[j + 1];
     uint64_t key[6];
     group_load48(key, comms + 48 * (size_t)i);
-    uint32_t s = group_slot_hash_seg(key, j, seed, hash_mask) & slot_mask;
-    uint32_t found = kGroupEmpty;
-#pragma unroll 1
-    for (uint32_t probe = 0; probe <= slot_mask; probe++, s = (s + 1) & slot_mask) {
-        const uint32_t c = atomicCAS(&table[s], kGroupEmpty, i);
-        if (c == kGroupEmpty) {   // claimed
-            found = s;
-            break;
-        }
-        if (c >= n) break;        // (no lane writes such a word: the table is not this launch's)
-        if (c >= lo && c < hi && group_equal48(key, comms + 48 * (size_t)c)) {
-            atomicMin(&table[s], i);
-            found = s;
-            break;
-        }
-    }
+    const uint32_t found = group_probe(comms, table, key, group_slot_hash_seg(key, j, seed, hash_mask) & slot_mask, i, n, slot_mask,
+                                       [lo, hi](uint32_t c) { return c >= lo && c < hi; });
     if (found == kGroupEmpty) atomicOr(&head[kGroupHeadErr], 1u);   // (the item is in no row; host function 1 fails the call)
     slot_of[i] = found;
-}
-
-__global__ __launch_bounds__(kScanLanes) void k_seg_scan(const uint8_t *__restrict__ comms, const uint32_t *__restrict__ table,
-                                                         const uint32_t *__restrict__ slot_of, uint32_t *__restrict__ slot_row,
-                                                         uint32_t *__restrict__ first_item, uint8_t *__restrict__ distinct,
-                                                         uint32_t *__restrict__ pre, uint32_t *__restrict__ head, uint32_t n) {
-    __shared__ uint32_t wave_tot[kScanWaves];
-    uint32_t run = 0;
-#pragma unroll 1
-    for (uint32_t base = 0; base < n; base += kScanLanes) {   // (n is the same for every lane: they all meet the barriers)
-        const uint32_t i = base + threadIdx.x;
-        uint32_t s = kGroupEmpty, flag = 0;
-        if (i < n) {
-            s = slot_of[i];
-            flag = s != kGroupEmpty && table[s] == i ? 1u : 0u;
-        }
-        uint32_t total;
-        const uint32_t before = block_exclusive_scan(flag, wave_tot, &total);
-        if (i < n) pre[i] = run + before;
-        if (flag) {
-            const uint32_t row = run + before;   // < n: at most one flag per item
-            slot_row[s] = row;
-            first_item[row] = i;
-            const uint64_t *src = (const uint64_t *)(comms + 48 * (size_t)i);
-            uint64_t *dst = (uint64_t *)(distinct + 48 * (size_t)row);
-#pragma unroll
-            for (int k = 0; k < 6; k++) dst[k] = src[k];
-        }
-        run += total;
-    }
-    if (threadIdx.x == 0) head[kGroupHeadM] = pre[n] = run;
 }
 
 // lanes 0 .. max(n, g + 1) - 1
@@ -380,29 +355,6 @@ __global__ __launch_bounds__(kGroupLanes) void k_seg_rows(const uint64_t *__rest
 #pragma unroll
         for (int q = 1; q < 6; q++) dst[q] = 0;
     }
-}
-
-// workgroup 0: row_off[0 .. M] from row_cnt; workgroup 1: col_off[0 .. cols] from col_cnt (cols = 128 g)
-__global__ __launch_bounds__(kScanLanes) void k_seg_offsets(const uint32_t *__restrict__ row_cnt, const uint32_t *__restrict__ col_cnt,
-                                                            uint32_t *__restrict__ row_off, uint32_t *__restrict__ col_off,
-                                                            const uint32_t *__restrict__ head, uint32_t n, uint32_t cols) {
-    __shared__ uint32_t wave_tot[kScanWaves];
-    const bool by_col = blockIdx.x != 0;
-    const uint32_t *cnt = by_col ? col_cnt : row_cnt;
-    uint32_t *off = by_col ? col_off : row_off;
-    uint32_t len = by_col ? cols : head[kGroupHeadM];
-    if (len > n && !by_col) len = n;
-    uint32_t run = 0;
-#pragma unroll 1
-    for (uint32_t base = 0; base < len; base += kScanLanes) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < len ? cnt[i] : 0u;
-        uint32_t total;
-        const uint32_t before = block_exclusive_scan(v, wave_tot, &total);
-        if (i < len) off[i] = run + before;
-        run += total;
-    }
-    if (threadIdx.x == 0) off[len] = run;
 }
 
 __global__ __launch_bounds__(kGroupLanes) void k_seg_scatter(const uint64_t *__restrict__ idx, const uint32_t *__restrict__ item_group,
@@ -476,9 +428,9 @@ void launch_cell_group_seg(const uint8_t *comms48, const uint64_t *idx, size_t n
                            (const uint32_t *)s.item_group, (const uint32_t *)s.gbad, s.table, s.slot_of, s.head, n32, (uint32_t)(slots - 1), seed,
                            hash_mask);
     }
-    {
+    {   // (the two shared kernels keep this call's names in the profile)
         ProfScope p("k_seg_scan", st);
-        hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(kScanLanes), 0, st, comms48, (const uint32_t *)s.table, (const uint32_t *)s.slot_of,
+        hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(kScanLanes), 0, st, comms48, (const uint32_t *)s.table, (const uint32_t *)s.slot_of,
                            s.slot_row, s.first_item, s.distinct, s.pre, s.head, n32);
     }
     {
@@ -489,7 +441,7 @@ void launch_cell_group_seg(const uint8_t *comms48, const uint64_t *idx, size_t n
     }
     {
         ProfScope p("k_seg_offsets", st);
-        hipLaunchKernelGGL(k_seg_offsets, dim3(2), dim3(kScanLanes), 0, st, (const uint32_t *)s.row_cnt, (const uint32_t *)s.col_cnt, s.row_off,
+        hipLaunchKernelGGL(k_group_offsets, dim3(2), dim3(kScanLanes), 0, st, (const uint32_t *)s.row_cnt, (const uint32_t *)s.col_cnt, s.row_off,
                            s.col_off, (const uint32_t *)s.head, n32, (uint32_t)(kGroupColumns * g));
     }
     ProfScope p("k_seg_scatter", st);
@@ -518,11 +470,27 @@ size_t hook_carve(CellGroupBufs &g, uint8_t *base, size_t n, size_t slots) {
     return cv.bytes();
 }
 
-C_KZG_RET cell_group_hook(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, uint32_t *first_item, uint32_t *perm_row, uint32_t *row_off,
-                          uint32_t *perm_col, uint32_t *col_off, uint32_t *bad_index, const uint8_t *comms, const uint64_t *idx, size_t n,
-                          uint64_t seed, uint32_t hash_mask, hipStream_t st) {
-    if (n == 0 || n >= 0x7fffffffu || !rows || !m_out || !distinct48 || !first_item || !perm_row || !row_off || !perm_col || !col_off ||
-        !bad_index || !comms || !idx)
+// where a hook's answers go on the host (row_base .. slice_off: the segmented hook's alone)
+struct HookOut {
+    uint32_t *rows, *m_out, *first_item, *perm_row, *row_off, *perm_col, *col_off, *row_base, *bad_words, *slices, *slice_off;
+    uint8_t *distinct48;
+};
+
+// what both hooks bring down, enqueued on st: the head words and the seven outputs a grouping of n items over `cols` column lists has,
+// from where g has them; the first error
+hipError_t hook_copies_down(uint32_t head[kGroupHeadWords], const HookOut &o, const CellGroupBufs &g, size_t n, size_t cols, hipStream_t st) {
+    const struct { void *dst; const void *src; size_t bytes; } copies[8] = {
+        {head, g.head, kGroupHeadWords * 4}, {o.rows, g.rows, n * 4},           {o.distinct48, g.distinct, n * 48}, {o.first_item, g.first_item, n * 4},
+        {o.perm_row, g.perm_row, n * 4},     {o.row_off, g.row_off, (n + 1) * 4}, {o.perm_col, g.perm_col, n * 4},    {o.col_off, g.col_off, (cols + 1) * 4}};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 8 && e == hipSuccess; k++) e = hipMemcpyAsync(copies[k].dst, copies[k].src, copies[k].bytes, hipMemcpyDeviceToHost, st);
+    return e;
+}
+
+C_KZG_RET cell_group_hook(const HookOut &o, uint32_t *bad_index, const uint8_t *comms, const uint64_t *idx, size_t n, uint64_t seed,
+                          uint32_t hash_mask, hipStream_t st) {
+    if (n == 0 || n >= 0x7fffffffu || !o.rows || !o.m_out || !o.distinct48 || !o.first_item || !o.perm_row || !o.row_off || !o.perm_col ||
+        !o.col_off || !bad_index || !comms || !idx)
         return C_KZG_BADARGS;
     const size_t slots = group_table_slots(n);
     CellGroupBufs g;
@@ -540,16 +508,9 @@ C_KZG_RET cell_group_hook(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, 
     launch_cell_group(comms, idx, n, slots, seed, hash_mask, g, st);
     LWK_HIP(hipGetLastError());
     uint32_t head[kGroupHeadWords];
-    LWK_HIP(hipMemcpyAsync(head, g.head, sizeof head, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(rows, g.rows, n * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(distinct48, g.distinct, n * 48, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(first_item, g.first_item, n * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(perm_row, g.perm_row, n * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(row_off, g.row_off, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(perm_col, g.perm_col, n * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(col_off, g.col_off, (kGroupColumns + 1) * 4, hipMemcpyDeviceToHost, st));
+    LWK_HIP(hook_copies_down(head, o, g, n, kGroupColumns, st));
     LWK_HIP(hipStreamSynchronize(st));
-    *m_out = head[kGroupHeadM];
+    *o.m_out = head[kGroupHeadM];
     *bad_index = ~head[kGroupHeadBad];
     if (head[kGroupHeadErr] || head[kGroupHeadM] == 0 || head[kGroupHeadM] > n) {
         set_error("lwkzg_cell_group_device: the grouping failed (error word %u, m = %u)", head[kGroupHeadErr], head[kGroupHeadM]);
@@ -558,12 +519,7 @@ C_KZG_RET cell_group_hook(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, 
     return C_KZG_OK;
 }
 
-struct SegHookOut {
-    uint32_t *rows, *m_out, *first_item, *perm_row, *row_off, *perm_col, *col_off, *row_base, *bad_words, *slices, *slice_off;
-    uint8_t *distinct48;
-};
-
-C_KZG_RET cell_group_seg_hook(const SegHookOut &o, const uint32_t *gflag, const uint8_t *comms, const uint64_t *idx, size_t n,
+C_KZG_RET cell_group_seg_hook(const HookOut &o, const uint32_t *gflag, const uint8_t *comms, const uint64_t *idx, size_t n,
                               const uint64_t *offsets, size_t g, uint64_t seed, uint32_t hash_mask, hipStream_t st) {
     if (n == 0 || g == 0 || n >= 0x7fffffffu || g > 0x40000000u || !o.rows || !o.m_out || !o.distinct48 || !o.first_item || !o.perm_row ||
         !o.row_off || !o.perm_col || !o.col_off || !o.row_base || !o.bad_words || !comms || !idx || !group_offsets_valid(offsets, g, n) ||
@@ -606,14 +562,9 @@ C_KZG_RET cell_group_seg_hook(const SegHookOut &o, const uint32_t *gflag, const 
     }
     LWK_HIP(hipGetLastError());
     uint32_t head[kGroupHeadWords];
-    LWK_HIP(hipMemcpyAsync(head, sb.head, sizeof head, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(o.rows, sb.rows, n * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(o.distinct48, sb.distinct, n * 48, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(o.first_item, sb.first_item, n * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(o.perm_row, sb.perm_row, n * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(o.row_off, sb.row_off, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(o.perm_col, sb.perm_col, n * 4, hipMemcpyDeviceToHost, st));
-    LWK_HIP(hipMemcpyAsync(o.col_off, sb.col_off, (kGroupColumns * g + 1) * 4, hipMemcpyDeviceToHost, st));
+    CellGroupBufs down = gb;   // (sb's outputs are gb's, but for its own head and its 128 g column lists)
+    down.head = sb.head, down.col_off = sb.col_off;
+    LWK_HIP(hook_copies_down(head, o, down, n, kGroupColumns * g, st));
     LWK_HIP(hipMemcpyAsync(o.row_base, sb.row_base, (g + 1) * 4, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(o.bad_words, sb.gbad, g * 4, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipStreamSynchronize(st));
@@ -638,7 +589,7 @@ extern "C" C_KZG_RET lwkzg_cell_group_segmented_device(uint32_t *rows, uint32_t 
                                                        size_t n, const uint64_t *group_offsets, size_t g, uint64_t seed, uint32_t hash_mask,
                                                        void *stream) {
     return guarded("lwkzg_cell_group_segmented_device", [&] {
-        const SegHookOut o{rows, m_out, first_item, perm_row, row_off, perm_col, col_off, row_base, bad_words, slices_out, slice_off_out, distinct48};
+        const HookOut o{rows, m_out, first_item, perm_row, row_off, perm_col, col_off, row_base, bad_words, slices_out, slice_off_out, distinct48};
         return cell_group_seg_hook(o, gflag, (const uint8_t *)commitments48_dev, (const uint64_t *)cell_indices_dev, n, group_offsets, g, seed,
                                    hash_mask, (hipStream_t)stream);
     });
@@ -649,7 +600,8 @@ extern "C" C_KZG_RET lwkzg_cell_group_device(uint32_t *rows, uint32_t *m_out, ui
                                              const void *commitments48_dev, const void *cell_indices_dev, size_t n, uint64_t seed,
                                              uint32_t hash_mask, void *stream) {
     return guarded("lwkzg_cell_group_device", [&] {
-        return cell_group_hook(rows, m_out, distinct48, first_item, perm_row, row_off, perm_col, col_off, bad_index,
-                               (const uint8_t *)commitments48_dev, (const uint64_t *)cell_indices_dev, n, seed, hash_mask, (hipStream_t)stream);
+        const HookOut o{rows, m_out, first_item, perm_row, row_off, perm_col, col_off, nullptr, nullptr, nullptr, nullptr, distinct48};
+        return cell_group_hook(o, bad_index, (const uint8_t *)commitments48_dev, (const uint64_t *)cell_indices_dev, n, seed, hash_mask,
+                               (hipStream_t)stream);
     });
 }

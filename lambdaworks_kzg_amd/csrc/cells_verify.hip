@@ -9,22 +9,17 @@
 //  * Column sums and interpolation: S_k[t] = sum_{k_i = k} a_i cell_i[t], a 64-point inverse transform of S_k in LDS (the cell's
 //    elements are the evaluations on the coset h_k <w64> in bit-reversed order: exactly the order a decimation-in-time transform
 //    consumes), coefficient t scaled by h_k^-t / 64, and the 128 columns summed into the 64 coefficients of I(X) = sum a_i I_i(X),
-//    written as canonical limbs into one 4096-scalar MSM slot whose other 4032 scalars are zero.
+//    written as canonical limbs into one 4096-scalar MSM slot whose other 4032 scalars are zero. The two kernels run on a grid of
+//    (.., groups): a call of g groups (cells_verify_groups.hip) is the same launches with one interpolant and one slot per group,
+//    and the batch is one group.
 //
 // Items are grouped by row and by column on the host (a counting sort over the indices it holds anyway) or, for an asynchronous
 // verifier, by cell_group.hip on the device: perm_* lists the items of group g at [off[g], off[g + 1]), in any order.
 #include "kernels.h"
 #include "cell_interp.cuh"
-#include "glv.cuh"
 #include "sha256_round.cuh"
 
 namespace lwk {
-
-// w8192^-1 and 1/64 in Montgomery form (w8192 = 7^((r-1)/8192); tests/test_cell_verify_cpu.py holds both against Python's pow)
-__device__ __constant__ uint32_t kInvOmega8192Mont[8] = {0xa1355e75u, 0x507dbef9u, 0x9b69cc1au, 0xeb71fd25u,
-                                                         0xee0557f8u, 0x6042c8dbu, 0x9dbce162u, 0x2415d770u};
-__device__ __constant__ uint32_t kInv64Mont[8] = {0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u,
-                                                  0x00000000u, 0x00000000u, 0x00000000u, 0x04000000u};
 
 namespace {
 
@@ -33,16 +28,6 @@ __device__ __forceinline__ void absorb(uint32_t w[16], int j, const uint4 &c) {
     w[4 * j + 1] = __builtin_bswap32(c.y);
     w[4 * j + 2] = __builtin_bswap32(c.z);
     w[4 * j + 3] = __builtin_bswap32(c.w);
-}
-
-__device__ __forceinline__ void store_split(uint32_t *sc, size_t i, const uint32_t raw[8]) {
-    uint32_t lo[4], hi[4];
-    split_by_z2_barrett(lo, hi, raw);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        sc[8 * i + q] = lo[q];
-        sc[8 * i + 4 + q] = hi[q];
-    }
 }
 
 }  // namespace
@@ -123,26 +108,15 @@ void launch_cellv_digests(const uint8_t *cells, const uint8_t *proofs48, const u
 
 // ---- behind r: a_i = r^i, b_i = a_i c_{k_i} ------------------------------------------------------------------------------------------
 // pw as k_vmsm_scalars takes it (r^(2^k), k < 32, then r^first; the cell batch starts at r^0). a_mont keeps a_i in Montgomery form
-// for the weights and the column sums; sc_a / sc_b are the split forms of a_i and b_i.
+// for the weights and the column sums; sc_a / sc_b are the split forms of a_i and b_i (cell_interp.cuh: cell_item_scalars, which
+// k_cellg_scalars runs too, on its group's table).
 __global__ __launch_bounds__(64) void k_cellv_scalars(const Fr *__restrict__ pw, const uint64_t *__restrict__ idx, const Fr *__restrict__ tw_fwd,
                                                       Fr *__restrict__ a_mont, uint32_t *__restrict__ sc_a, uint32_t *__restrict__ sc_b,
                                                       uint32_t n, const uint32_t *__restrict__ skip) {
     if (skip && *skip) return;  // a rejected batch of an asynchronous verifier (cells_verify_async.hip): its indices are unchecked
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fr a = pw[32];
-#pragma unroll 1
-    for (int k = 0; k < 32; k++) {
-        if ((i >> k) == 0) break;
-        if ((i >> k) & 1u) a = a * pw[k];
-    }
-    a_mont[i] = a;
-    const Fr b = a * c_of_cell(tw_fwd, (uint32_t)idx[i]);
-    uint32_t raw[8];
-    fe_to_raw<FrParams>(raw, a);
-    store_split(sc_a, i, raw);
-    fe_to_raw<FrParams>(raw, b);
-    store_split(sc_b, i, raw);
+    cell_item_scalars(pw, i, i, idx, tw_fwd, a_mont, sc_a, sc_b);
 }
 
 // w_j = sum of a_i over the items of row j, one wave per row. m_dev (optional): the number of rows where only the device knows it -- the
@@ -219,22 +193,25 @@ hipError_t launch_cellv_first_visit(const uint8_t *cells, const uint64_t *idx, c
 }
 
 // ---- behind r: the column sums, their interpolation, and the 64 coefficients of I(X) ------------------------------------------------
-// One workgroup per column k, four waves: wave v sums every fourth item of the column (lane t = element t of the cell; a wave reads
-// a cell's 2 KiB in one pass), the four partial sums meet in LDS, and 32 lanes run the six stages of the 64-point decimation-in-time
-// inverse transform in place. The cell's values are canonical integers and stay so: a Montgomery product of a Montgomery-form
-// factor (a_i, a twiddle, the scale) with a raw value is the raw product. colcoef[64 k + t]: coefficient t of column k's share,
-// canonical limbs (zero for a column nobody sampled).
+// One workgroup per (column k, group first + blockIdx.y), four waves: wave v sums every fourth item of the column (lane t = element t
+// of the cell; a wave reads a cell's 2 KiB in one pass), the four partial sums meet in LDS, and 32 lanes run the six stages of the
+// 64-point decimation-in-time inverse transform in place. The cell's values are canonical integers and stay so: a Montgomery product
+// of a Montgomery-form factor (a_i, a twiddle, the scale) with a raw value is the raw product. col_off: the group's column k is list
+// 128 (first + blockIdx.y) + k. colcoef[(128 blockIdx.y + k) 64 + t]: coefficient t of the column's share of the group's interpolant,
+// canonical limbs (zero for a column nobody sampled). flag (nullptr: nobody is flagged): one word per group -- a batch's skip word
+// (one group, first = 0), a grouped call's flags.
 __global__ __launch_bounds__(256) void k_cellv_columns(const uint4 *__restrict__ cells, const Fr *__restrict__ a_mont,
                                                        const uint32_t *__restrict__ perm_col, const uint32_t *__restrict__ col_off,
-                                                       const Fr *__restrict__ tw_inv, Fr *__restrict__ colcoef, int le,
-                                                       const uint32_t *__restrict__ skip) {
+                                                       const uint32_t *__restrict__ flag, const Fr *__restrict__ tw_inv,
+                                                       Fr *__restrict__ colcoef, int le, uint32_t first) {
     __shared__ Fr part[4][kCellElems];
     __shared__ Fr buf[kCellElems];
-    if (skip && *skip) return;  // (the whole workgroup, before its first barrier; k_cellv_coeffs then reads nothing of colcoef)
-    const uint32_t k = blockIdx.x, t = threadIdx.x & 63u, v = threadIdx.x >> 6;
-    const uint32_t lo = col_off[k], hi = col_off[k + 1];
+    const uint32_t k = blockIdx.x, jj = blockIdx.y, j = first + jj, t = threadIdx.x & 63u, v = threadIdx.x >> 6;
+    if (flag && flag[j]) return;  // (the whole workgroup, before its first barrier; k_cellv_coeffs then reads nothing of its scratch)
+    Fr *out = colcoef + ((size_t)kCellsPerBlob * jj + k) * kCellElems;
+    const uint32_t lo = col_off[(size_t)kCellsPerBlob * j + k], hi = col_off[(size_t)kCellsPerBlob * j + k + 1];
     if (lo == hi) {   // (the same for the whole workgroup: no barrier is left behind)
-        if (v == 0) colcoef[kCellElems * k + t] = Fr::zero();
+        if (v == 0) out[t] = Fr::zero();
         return;
     }
     Fr acc = Fr::zero();
@@ -256,35 +233,33 @@ __global__ __launch_bounds__(256) void k_cellv_columns(const uint4 *__restrict__
         __syncthreads();
     }
     if (v != 0) return;
-    // times h_k^-t / 64 (cell_interp.cuh)
-    const Fr sc = cell_coeff_twist(tw_inv, k, t, kInvOmega8192Mont);
-    Fr c;
-#pragma unroll
-    for (int j = 0; j < 8; j++) c.l[j] = kInv64Mont[j];
-    colcoef[kCellElems * k + t] = (sc * c) * buf[t];
+    out[t] = cell_coeff_scale(tw_inv, k, t) * buf[t];   // times h_k^-t / 64
 }
 
-// scalar t of the MSM slot: the sum of the 128 columns' coefficient t for t < 64, zero above. Under skip all 4096 scalars are zero: the
-// engine's launch set behind this kernel has no skip argument, so its slot is defined either way
-__global__ __launch_bounds__(256) void k_cellv_coeffs(const Fr *__restrict__ colcoef, Fr *__restrict__ slot, const uint32_t *__restrict__ skip) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+// scalar t of MSM slot blockIdx.y (group first + blockIdx.y): the sum of the 128 columns' coefficient t for t < 64, zero above; all 4096
+// zero for a flagged group (the engine's launch set behind this kernel takes no flag, so its slot is defined either way)
+__global__ __launch_bounds__(256) void k_cellv_coeffs(const Fr *__restrict__ colcoef, const uint32_t *__restrict__ flag, Fr *__restrict__ slots,
+                                                      uint32_t first) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, jj = blockIdx.y;
     Fr acc = Fr::zero();
-    if (t < (uint32_t)kCellElems && !(skip && *skip)) {
+    if (t < (uint32_t)kCellElems && !(flag && flag[first + jj])) {
+        const Fr *cc = colcoef + (size_t)kCellsPerBlob * kCellElems * jj;
 #pragma unroll 1
-        for (int k = 0; k < kCellsPerBlob; k++) acc = acc + colcoef[kCellElems * k + t];
+        for (int k = 0; k < kCellsPerBlob; k++) acc = acc + cc[kCellElems * k + t];
     }
-    slot[t] = acc;
+    slots[(size_t)kBlobElems * jj + t] = acc;
 }
 
 void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off, const Fr *tw_inv,
-                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st, const uint32_t *skip) {
+                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st, const uint32_t *flag, size_t first, size_t groups) {
     {
         ProfScope p("k_cellv_columns", st);
-        hipLaunchKernelGGL(k_cellv_columns, dim3(kCellsPerBlob), dim3(256), 0, st, (const uint4 *)cells, a_mont, perm_col, col_off, tw_inv,
-                           colcoef, le, skip);
+        hipLaunchKernelGGL(k_cellv_columns, dim3(kCellsPerBlob, (unsigned)groups), dim3(256), 0, st, (const uint4 *)cells, a_mont, perm_col,
+                           col_off, flag, tw_inv, colcoef, le, (uint32_t)first);
     }
     ProfScope p("k_cellv_coeffs", st);
-    hipLaunchKernelGGL(k_cellv_coeffs, dim3(kBlobElems / 256), dim3(256), 0, st, (const Fr *)colcoef, (Fr *)slot_raw, skip);
+    hipLaunchKernelGGL(k_cellv_coeffs, dim3(kBlobElems / 256, (unsigned)groups), dim3(256), 0, st, (const Fr *)colcoef, flag, (Fr *)slot_raw,
+                       (uint32_t)first);
 }
 
 }  // namespace lwk

@@ -27,17 +27,8 @@ namespace lwk {
 
 namespace {
 
-#include "recover_consts.inc"   // w8192^-1 and 1/64 in Montgomery form, as recover.hip takes them
-
 // the status word of an item whose index is not below 128: no C_KZG_RET, so that the host can answer C_KZG_BADARGS for it in both modes
 constexpr int32_t kStatusBadIndex = 0x100;
-
-__device__ __forceinline__ Fr const_fr(const uint32_t *limbs) {
-    Fr c;
-#pragma unroll
-    for (int j = 0; j < 8; j++) c.l[j] = limbs[j];
-    return c;
-}
 
 // One wave (one workgroup) per item, lane t = element t of its cell = coefficient t of its interpolant = setup point t.
 // status[i] comes in as the validation left it (0, or bad_code where a point is bad). An index that is not below 128 is decided first
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(64) void k_celleach_commit(const uint4 *__restrict_
     }
     // I_i[t]: times h_k^-t / 64, a canonical integer
     uint32_t coef[8];
-    cell_each_coeff_raw(coef, cell_coeff_twist(tw_inv, k, t, kRecInvOmega8192Mont) * const_fr(kRecInv64Mont), buf[t]);
+    cell_each_coeff_raw(coef, cell_coeff_scale(tw_inv, k, t), buf[t]);
     __syncthreads();   // buf is read; the tree may write over it
     const G1Affine q = setup[t];
     G1Xyzz acc = glv_mul_affine(q.x, q.y, beta, coef);

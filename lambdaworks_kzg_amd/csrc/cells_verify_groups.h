@@ -52,7 +52,7 @@ inline void cellg_carve_pin(CellgPin &p, Carver &cv, size_t gcap) {
 // a_i = r_j^(i - off_j), b_i = a_i c_(k_i) for the items of the groups with gflag[j] == 0; pw: group j's table at 33 j
 void launch_cellg_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, const uint32_t *item_group, const uint32_t *item_off,
                           const uint32_t *gflag, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b, size_t n, hipStream_t st);
-// every group's interpolant committed: k_cellg_columns / k_cellg_coeffs a chunk of kInterpChunk groups at a time into the context's MSM
+// every group's interpolant committed: launch_cellv_interpolant (k_cellv_columns / k_cellv_coeffs) a chunk of kInterpChunk groups at a time into the context's MSM
 // slots, the engine's MSM a launch set of up to kMaxChunk slots at a time; rli48[48 j]: group j's commitment, compressed. The caller
 // holds the context's lock and workspace and has reserved it for min(g, kMaxChunk) slots. colcoef: cellg_colcoef_bytes() of scratch
 void launch_cellg_interpolants(Ctx *c, int mode, const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off,

@@ -8,9 +8,9 @@
 //            with the group-local rows, both point sets validated (the groups' distinct commitments one after the other, padded
 //            with infinity encodings to n), the 2 n fault words; digests and fault words come down
 //   host     every group's fault; g transcripts and g power tables on the host threads (cells_verify_host.h: groups_decide)
-//   device   k_cellg_scalars (a_i = r_j^(i - off_j), b_i = a_i c_(k_i)), the row weights over the concatenated rows, k_cellg_columns /
-//            k_cellg_coeffs (the interpolant of every group into one MSM slot per group, a chunk of kInterpChunk groups at a time), the
-//            engine's MSM over the slots, k_cellg_slices (one 64-lane workgroup per slice of one sum of one group: a scalar product
+//   device   k_cellg_scalars (a_i = r_j^(i - off_j), b_i = a_i c_(k_i)), the row weights over the concatenated rows, the batch call's
+//            k_cellv_columns / k_cellv_coeffs on a grid of (.., groups) (cells_verify.hip: the interpolant of every group into one MSM
+//            slot per group, a chunk of kInterpChunk groups at a time), the engine's MSM over the slots, k_cellg_slices (one 64-lane workgroup per slice of one sum of one group: a scalar product
 //            per lane, the six-level tree of cell_each.cuh) and k_cellg_fold (the slices of a sum); sums and RLIs come down
 //   host     cell_batch_finish per live group on the host threads (the pairing does not re-enter them: it forks by SideTask) and the
 //            answers (cells_verify_host.h: groups_answers)
@@ -34,8 +34,6 @@ namespace lwk {
 
 namespace {
 
-#include "recover_consts.inc"   // w8192^-1 and 1/64 in Montgomery form
-
 static_assert(kPlanSliceTerms == (uint32_t)kCellElems, "a slice is one term per lane of the tree's 64-lane workgroup");
 static_assert(sizeof(GroupSlice) == 16, "four words per slice on the device");
 
@@ -45,7 +43,7 @@ constexpr size_t kInterpGroupBytes = (size_t)kCellsPerBlob * kCellElems * sizeof
 
 // ---- behind r: a_i = r_j^(i - off_j), b_i = a_i c_(k_i) for the items of the live groups -------------------------------------------------
 // pw: group j's table at 33 j (r_j^(2^k), k < 32, then 1). One lane per item and no barrier: a lane of a flagged group leaves alone, before
-// its index is looked at. a_mont / sc_a / sc_b as k_cellv_scalars writes them.
+// its index is looked at. a_mont / sc_a / sc_b as k_cellv_scalars writes them, by the same body (cell_interp.cuh: cell_item_scalars).
 __global__ __launch_bounds__(64) void k_cellg_scalars(const Fr *__restrict__ pw, const uint64_t *__restrict__ idx, const Fr *__restrict__ tw_fwd,
                                                       const uint32_t *__restrict__ item_group, const uint32_t *__restrict__ item_off,
                                                       const uint32_t *__restrict__ gflag, Fr *__restrict__ a_mont, uint32_t *__restrict__ sc_a,
@@ -54,83 +52,7 @@ __global__ __launch_bounds__(64) void k_cellg_scalars(const Fr *__restrict__ pw,
     if (i >= n) return;
     const uint32_t j = item_group[i];
     if (gflag[j]) return;
-    const Fr *tab = pw + kPwWords * (size_t)j;
-    const uint32_t e = i - item_off[j];
-    Fr a = tab[32];
-#pragma unroll 1
-    for (int k = 0; k < 32; k++) {
-        if ((e >> k) == 0) break;
-        if ((e >> k) & 1u) a = a * tab[k];
-    }
-    a_mont[i] = a;
-    const Fr b = a * c_of_cell(tw_fwd, (uint32_t)idx[i]);
-    uint32_t raw[8], lo[4], hi[4];
-    fe_to_raw<FrParams>(raw, a);
-    split_by_z2_barrett(lo, hi, raw);
-#pragma unroll
-    for (int q = 0; q < 4; q++) sc_a[8 * (size_t)i + q] = lo[q], sc_a[8 * (size_t)i + 4 + q] = hi[q];
-    fe_to_raw<FrParams>(raw, b);
-    split_by_z2_barrett(lo, hi, raw);
-#pragma unroll
-    for (int q = 0; q < 4; q++) sc_b[8 * (size_t)i + q] = lo[q], sc_b[8 * (size_t)i + 4 + q] = hi[q];
-}
-
-// ---- behind r: the column sums of k_cellv_columns per (column, group) ----------------------------------------------------------------------
-// Workgroup (k, jj): column k of group first + jj, four waves as there. col_off: list 128 j + k of the call. colcoef[(128 jj + k) 64 + t]:
-// coefficient t of the column's share of the group's interpolant (zero for a column the group did not sample). A flagged group's
-// workgroups leave whole, before their first barrier; k_cellg_coeffs then reads nothing of their scratch.
-__global__ __launch_bounds__(256) void k_cellg_columns(const uint4 *__restrict__ cells, const Fr *__restrict__ a_mont,
-                                                       const uint32_t *__restrict__ perm_col, const uint32_t *__restrict__ col_off,
-                                                       const uint32_t *__restrict__ gflag, const Fr *__restrict__ tw_inv,
-                                                       Fr *__restrict__ colcoef, int le, uint32_t first) {
-    __shared__ Fr part[4][kCellElems];
-    __shared__ Fr buf[kCellElems];
-    const uint32_t k = blockIdx.x, jj = blockIdx.y, j = first + jj, t = threadIdx.x & 63u, v = threadIdx.x >> 6;
-    if (gflag[j]) return;
-    Fr *out = colcoef + ((size_t)kCellsPerBlob * jj + k) * kCellElems;
-    const uint32_t lo = col_off[(size_t)kCellsPerBlob * j + k], hi = col_off[(size_t)kCellsPerBlob * j + k + 1];
-    if (lo == hi) {   // (the same for the whole workgroup: no barrier is left behind)
-        if (v == 0) out[t] = Fr::zero();
-        return;
-    }
-    Fr acc = Fr::zero();
-#pragma unroll 1
-    for (uint32_t s = lo + v; s < hi; s += 4) {
-        const uint32_t i = perm_col[s];
-        const uint4 *e = cells + ((size_t)kCellElems * i + t) * 2;
-        Fr x;
-        element_limbs(x.l, e[0], e[1], le);
-        acc = acc + a_mont[i] * x;
-    }
-    part[v][t] = acc;
-    __syncthreads();
-    if (v == 0) buf[t] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
-    __syncthreads();
-#pragma unroll 1
-    for (int s = 0; s < 6; s++) {
-        if (threadIdx.x < 32) cell_idft64_stage(buf, tw_inv, s, threadIdx.x);
-        __syncthreads();
-    }
-    if (v != 0) return;
-    const Fr sc = cell_coeff_twist(tw_inv, k, t, kRecInvOmega8192Mont);   // times h_k^-t / 64 (cell_interp.cuh)
-    Fr c;
-#pragma unroll
-    for (int q = 0; q < 8; q++) c.l[q] = kRecInv64Mont[q];
-    out[t] = (sc * c) * buf[t];
-}
-
-// scalar t of MSM slot jj (group first + jj): the sum of the 128 columns' coefficient t for t < 64, zero above; all 4096 zero for a
-// flagged group (the engine's launch set behind this kernel takes no flag, so its slot is defined either way)
-__global__ __launch_bounds__(256) void k_cellg_coeffs(const Fr *__restrict__ colcoef, const uint32_t *__restrict__ gflag, Fr *__restrict__ slots,
-                                                      uint32_t first) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, jj = blockIdx.y;
-    Fr acc = Fr::zero();
-    if (t < (uint32_t)kCellElems && !gflag[first + jj]) {
-        const Fr *cc = colcoef + (size_t)kCellsPerBlob * kCellElems * jj;
-#pragma unroll 1
-        for (int k = 0; k < kCellsPerBlob; k++) acc = acc + cc[kCellElems * k + t];
-    }
-    slots[(size_t)kBlobElems * jj + t] = acc;
+    cell_item_scalars(pw + kPwWords * (size_t)j, i - item_off[j], i, idx, tw_fwd, a_mont, sc_a, sc_b);
 }
 
 // ---- behind r: the three variable-base sums of every group -------------------------------------------------------------------------------
@@ -215,15 +137,8 @@ void launch_cellg_interpolants(Ctx *c, int mode, const uint8_t *cells, const Fr 
         const size_t set = min_sz(g - base, kMaxChunk);
         for (size_t off = 0; off < set; off += kInterpChunk) {
             const size_t m = min_sz(set - off, kInterpChunk);
-            const uint32_t first = (uint32_t)(base + off);
-            {
-                ProfScope p("k_cellg_columns", st);
-                hipLaunchKernelGGL(k_cellg_columns, dim3(kCellsPerBlob, (unsigned)m), dim3(256), 0, st, (const uint4 *)cells, a_mont, perm_col,
-                                   col_off, gflag, (const Fr *)c->tw_inv, colcoef, le, first);
-            }
-            ProfScope p("k_cellg_coeffs", st);
-            hipLaunchKernelGGL(k_cellg_coeffs, dim3(kBlobElems / 256, (unsigned)m), dim3(256), 0, st, (const Fr *)colcoef, gflag,
-                               (Fr *)c->ws.scalars2 + (size_t)kBlobElems * off, first);
+            launch_cellv_interpolant(cells, a_mont, perm_col, col_off, c->tw_inv, colcoef, c->ws.scalars2 + 8 * (size_t)kBlobElems * off, le, st,
+                                     gflag, base + off, m);
         }
         const bool lg = coefficients_to_msm_form(c, mode, set, st);
         msm_stages(c, c->ws.scalars2, rli48 + 48 * base, set, st, 0, false, lg);

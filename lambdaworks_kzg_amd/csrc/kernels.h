@@ -328,9 +328,13 @@ void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, F
 void launch_cellv_row_weights(const Fr *a_mont, const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t rows, hipStream_t st,
                               const uint32_t *m_dev = nullptr, const uint32_t *skip = nullptr);
 // slot_raw: 4096 canonical scalars, the first 64 the coefficients of sum_i r^i I_i(X), the rest zero. perm_col / col_off (129 words): the
-// items by column; colcoef: 128 x 64 Fr of scratch. Under skip slot_raw is 4096 zero scalars (the MSM behind it takes no skip word)
+// items by column; colcoef: 128 x 64 Fr of scratch. Under skip slot_raw is 4096 zero scalars (the MSM behind it takes no skip word).
+// The two launches (k_cellv_columns, k_cellv_coeffs) serve a call of groups too (cells_verify_groups.hip): groups first .. first +
+// groups - 1 of the call, one word of flag each (the batch's skip word is the flag of its one group), col_off the lists 128 j + k of the
+// whole call, colcoef and slot_raw one 128 x 64 scratch and one slot per group of THIS launch
 void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off, const Fr *tw_inv,
-                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st, const uint32_t *skip = nullptr);
+                              Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st, const uint32_t *flag = nullptr, size_t first = 0,
+                              size_t groups = 1);
 // cells_verify_async.hip: fault (2 n words) -- [i] keeps the digests' word of item i and takes proof i's verdict, [n + j] is distinct
 // commitment j's -- from the kinds the validation left
 void launch_cellv_fault_words(int32_t *fault, const int32_t *kind_p, const int32_t *kind_c, int bad_code, size_t n, hipStream_t st);
@@ -403,7 +407,9 @@ inline void cell_group_seg_carve(CellGroupSegBufs &s, const CellGroupBufs &g, Ca
     cv.take(s.row_base, (gcap + 1) * 4);
     cv.take(s.col_off, (128 * gcap + 1) * 4);
 }
-// s.item_off holds the call's g + 1 offsets (valid: group_offsets_valid). Seven launches and four fills on st; nothing is read back
+// s.item_off holds the call's g + 1 offsets (valid: group_offsets_valid). Seven launches and four fills on st; nothing is read back.
+// Two of the seven are launch_cell_group's own kernels (k_group_scan with s.pre, k_group_offsets over 128 g column lists), under this
+// call's names in the profile (k_seg_scan, k_seg_offsets); the insertion shares its probe with k_group_insert
 void launch_cell_group_seg(const uint8_t *comms48, const uint64_t *idx, size_t n, size_t g, size_t slots, uint64_t seed, uint32_t hash_mask,
                            const CellGroupSegBufs &s, hipStream_t st);
 // the slice table of the call (cell_groups_plan.h: plan_slice_count / plan_slice): slice_off[3 g + 1], slices[slice_off[3 g]]; a

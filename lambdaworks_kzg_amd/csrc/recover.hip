@@ -24,16 +24,7 @@
 
 namespace lwk {
 
-#include "recover_consts.inc"
-
 namespace {
-
-__device__ __forceinline__ Fr const_fr(const uint32_t *limbs) {
-    Fr c;
-#pragma unroll
-    for (int j = 0; j < 8; j++) c.l[j] = limbs[j];
-    return c;
-}
 
 __device__ __forceinline__ uint32_t bitrev7(uint32_t q) { return __brev(q) >> 25; }
 
@@ -142,7 +133,7 @@ __device__ __forceinline__ void recover_interp_body(const uint4 *__restrict__ ce
         __syncthreads();
     }
     // I_k[t] Zs(c_k): times h_k^-t, and Zs(c_k) / 64 from the table
-    const Fr sc = cell_coeff_twist(tw_inv, k, t, kRecInvOmega8192Mont) * tab[q];
+    const Fr sc = cell_coeff_twist(tw_inv, k, t) * tab[q];
     scratch[((size_t)blob * kCellElems + t) * kCellsPerBlob + q] = sc * buf[t];
 }
 

@@ -109,7 +109,7 @@ def test_argument_checks_need_no_gpu(K):
 
 
 def _limbs(name):
-    src = open(os.path.join(ROOT, "lambdaworks_kzg_amd", "csrc", "cells_verify.hip")).read()
+    src = open(os.path.join(ROOT, "lambdaworks_kzg_amd", "csrc", "recover_consts.inc")).read()
     m = re.search(name + r"\[8\]\s*=\s*\{([^}]*)\}", src)
     words = [int(x.strip().rstrip("u"), 16) for x in m.group(1).split(",")]
     return sum(w << (32 * i) for i, w in enumerate(words))
@@ -117,8 +117,8 @@ def _limbs(name):
 
 def test_kernel_constants():
     mont = pow(2, 256, S.R)
-    assert _limbs("kInvOmega8192Mont") == pow(S.W8192, S.R - 2, S.R) * mont % S.R
-    assert _limbs("kInv64Mont") == pow(64, S.R - 2, S.R) * mont % S.R
+    assert _limbs("kRecInvOmega8192Mont") == pow(S.W8192, S.R - 2, S.R) * mont % S.R
+    assert _limbs("kRecInv64Mont") == pow(64, S.R - 2, S.R) * mont % S.R
     # what k_cellv_columns relies on: D[64 k] = w8192^bitrev7(k), and the inverse twiddle of exponent e is -w4096^-(e - 2048) above 2048
     for k in (0, 1, 64, 77, 127):
         assert S.coset_for_cell(k)[0] == pow(S.W8192, S.rev(k, 7), S.R)

@@ -7,7 +7,7 @@ import pytest
 import blobs as B
 import cells_spec as S
 from conftest import R, SETUP_PATH
-from test_gpu_cell_verify import MODES, _mode, _x_off_the_curve
+from test_gpu_cell_verify import MODES, _mode, _rc, _x_off_the_curve
 from test_gpu_cell_verify_async import NONE_BAD, _Dev, _long_work
 
 pytestmark = pytest.mark.gpu
@@ -89,6 +89,34 @@ def test_sixty_five_groups_of_one_item(K, gpu_setup, verifier, library_cells, mo
     with _mode(K, gpu_setup, mode):
         got, _ = _same_as_the_synchronous_call(K, gpu_setup, verifier, [[it] for it in items], "65 x 1")
     assert got == [(K.C_KZG_OK, True)] * 65
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_flagged_groups_in_the_second_interpolant_chunk(K, gpu_setup, verifier, library_cells, mode):
+    """66 groups of one item: groups 64 and 65 are the second chunk of the interpolant kernels (first = 64), whose workgroups read their
+    group's flag at first + blockIdx.y. Group 64 has the index 128, group 65 a proof with one byte changed; every group answers as the
+    batch call on its item alone, through enqueue_groups and through the synchronous grouped call"""
+    items = list(library_cells[mode][200:266])
+    items[64] = (items[64][0], 128) + items[64][2:]
+    proof = items[65][3]
+    items[65] = items[65][:3] + (proof[:47] + bytes([proof[47] ^ 1]),)
+    groups = [[it] for it in items]
+    with _mode(K, gpu_setup, mode):
+        got, _ = _same_as_the_synchronous_call(K, gpu_setup, verifier, groups, "66 x 1, flags in the second chunk")
+        alone = [_rc(K, gpu_setup, grp) for grp in groups]
+    print("groups 64, 65:", got[64:], "alone:", alone[64:])
+    assert got == alone
+    assert got[:64] == [(K.C_KZG_OK, True)] * 64
+    assert got[64] == (K.C_KZG_BADARGS, False) and got[65] != (K.C_KZG_OK, True)
+    # and the other way round: group 1 flagged, groups 64 and 65 live -- a kernel that read its flag at blockIdx.y would zero group 65's slot
+    items = list(library_cells[mode][200:266])
+    items[1] = (items[1][0], 128) + items[1][2:]
+    groups = [[it] for it in items]
+    with _mode(K, gpu_setup, mode):
+        got, _ = _same_as_the_synchronous_call(K, gpu_setup, verifier, groups, "66 x 1, a flag in the first chunk")
+        alone = [_rc(K, gpu_setup, grp) for grp in groups]
+    assert got == alone
+    assert got == [(K.C_KZG_OK, True)] + [(K.C_KZG_BADARGS, False)] + [(K.C_KZG_OK, True)] * 64
 
 
 @pytest.mark.parametrize("sizes", [[100, 156, 0, 1], [3, 700, 0, 321, 1]], ids=["n257", "n1025"])
