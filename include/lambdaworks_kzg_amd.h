@@ -848,6 +848,49 @@ C_KZG_RET lwkzg_cell_verify_groups_partials(uint8_t *out /* g x LWKZG_CELL_VERIF
                                             const uint64_t *cell_indices, const Cell *cells, const Bytes48 *proofs, size_t n,
                                             const uint64_t *group_offsets /* g + 1 */, size_t g, const KZGSettings *s);
 
+/* Cell proofs of WHOLE BLOBS: do the 128 cell proofs of each blob belong to the blob and its commitment? What the holder of a Fulu
+ * blob transaction asks -- (blob, commitment, 128 proofs), no cells. Both calls are DEFINED by the calls above. For blob b let cells_b
+ * be the 128 cells lwkzg_compute_cells_and_kzg_proofs(cells, NULL, &blobs[b], s) writes in the mode the settings answer in; the
+ * expanded items of a call are the 128 n items (commitments[b], k, cells_b[k], cell_proofs[128 b + k]) in the order i = 128 b + k.
+ *   batch    the return code and *ok are those of lwkzg_verify_cell_kzg_proof_batch on the expanded items: the same de-duplication
+ *            of commitments, transcript and r. n == 0: C_KZG_OK, *ok = true.
+ *   groups   group j is the BLOBS group_offsets[j] .. group_offsets[j + 1] - 1; rc_out[j] and ok_out[j] are those of
+ *            lwkzg_verify_cell_kzg_proof_groups for the items 128 group_offsets[j] .. 128 group_offsets[j + 1] - 1 of the expanded
+ *            items. An empty group answers (C_KZG_OK, 1); a bad group is an answer and does not spread.
+ * A blob that the compute call rejects -- an element not below r in LWKZG_MODE_CKZG and LWKZG_MODE_ETH; reference mode reduces and
+ * rejects nothing -- answers the mode's bad-input code, the code a cell element not below r gets: the batch call returns it with
+ * *ok = false; in the groups call exactly the blob's own group takes it as rc_out[j] with ok_out[j] = 0, and nothing behind r runs on
+ * that group. C_KZG_BADARGS, decided before any device work and with nothing written beyond *ok = false: s or ok NULL; blobs,
+ * commitments or cell_proofs NULL with n > 0; for the groups call the list of lwkzg_verify_cell_kzg_proof_groups, with "item array"
+ * read as these three and the offsets counting blobs. All three modes, every MSM engine; no proofs are computed, so the cell proof
+ * engine (below) does not matter. Synchronous.
+ * Memory: the cells live in a grow-only scratch of the settings object, 256 KiB + 16 bytes per blob (and, once, the host forms' upload
+ * slice: 128 KiB per blob of the call, at most 8 MiB), beside what the call over 128 n items keeps; a second call of the same size
+ * allocates nothing, free_trusted_setup frees it. C_KZG_MALLOC, the error text naming the size, when it does not fit.
+ * Use these when you hold blobs; the calls over items when you hold cells.
+ * Out of scope: forms that do not block, lwkzg_multi_* forms, stream capture, versioned hashes, column sidecars in their own layout. */
+C_KZG_RET lwkzg_verify_blob_cell_kzg_proofs_batch(bool *ok, const Blob *blobs, const Bytes48 *commitments /* n */,
+                                                  const Bytes48 *cell_proofs /* n x 128 */, size_t n, const KZGSettings *s);
+/* the same for inputs already in HBM (device pointers, 16-byte aligned, produced on `stream`, NULL = already complete). The blobs and
+ * their cells never come to the host; the n commitments do, to be de-duplicated, and only n-entry tables go up. */
+C_KZG_RET lwkzg_verify_blob_cell_kzg_proofs_batch_device(bool *ok, const void *blobs_dev, const void *commitments48_dev,
+                                                         const void *cell_proofs48_dev, size_t n, const KZGSettings *s, void *stream);
+/* test hook: exactly the bytes lwkzg_cell_verify_partials writes for the expanded items, by the verdict call's own code path */
+C_KZG_RET lwkzg_blob_cell_verify_partials(uint8_t *out /* LWKZG_CELL_VERIFY_PARTIAL_BYTES */, const Blob *blobs, const Bytes48 *commitments,
+                                          const Bytes48 *cell_proofs, size_t n, const KZGSettings *s);
+C_KZG_RET lwkzg_verify_blob_cell_kzg_proofs_groups(uint8_t *ok_out, int32_t *rc_out, const Blob *blobs, const Bytes48 *commitments,
+                                                   const Bytes48 *cell_proofs, size_t n,
+                                                   const uint64_t *group_offsets /* in BLOBS, g + 1 */, size_t g, const KZGSettings *s);
+/* device pointers as in the batch form; the offsets stay a HOST array, read before the call returns */
+C_KZG_RET lwkzg_verify_blob_cell_kzg_proofs_groups_device(uint8_t *ok_out, int32_t *rc_out, const void *blobs_dev,
+                                                          const void *commitments48_dev, const void *cell_proofs48_dev, size_t n,
+                                                          const uint64_t *group_offsets /* HOST, in BLOBS, g + 1 */, size_t g,
+                                                          const KZGSettings *s, void *stream);
+/* test hook: per group exactly what lwkzg_cell_verify_groups_partials writes for the expanded items (out NULL with g > 0: C_KZG_BADARGS) */
+C_KZG_RET lwkzg_blob_cell_verify_groups_partials(uint8_t *out /* g x LWKZG_CELL_VERIFY_PARTIAL_BYTES */, const Blob *blobs,
+                                                 const Bytes48 *commitments, const Bytes48 *cell_proofs, size_t n,
+                                                 const uint64_t *group_offsets /* in BLOBS, g + 1 */, size_t g, const KZGSettings *s);
+
 /* The engine behind the cell proofs of lwkzg_compute_cells_and_kzg_proofs* and lwkzg_recover_cells_and_kzg_proofs* (DESIGN.md section 4h),
  * a per-settings choice. FK20 (Feist-Khovratovich): the 128 proofs of a blob as a Toeplitz product over G1 -- 64 coefficient transforms,
  * 128 MSMs of 64 terms over a per-settings window table of 8192 transformed bases, and two 128-point transforms over G1 -- instead of 128

@@ -19,6 +19,8 @@ from .capi import (  # noqa: F401
     verify_cell_kzg_proof_batch, verify_cell_kzg_proof_batch_device, cell_verify_partials, cell_batch_challenge_host,
     verify_cell_kzg_proof_each, verify_cell_kzg_proof_each_device, cell_verify_each_points,
     verify_cell_kzg_proof_groups, verify_cell_kzg_proof_groups_device, cell_verify_groups_partials,
+    verify_blob_cell_kzg_proofs_batch, verify_blob_cell_kzg_proofs_batch_device, blob_cell_verify_partials,
+    verify_blob_cell_kzg_proofs_groups, verify_blob_cell_kzg_proofs_groups_device, blob_cell_verify_groups_partials,
     CellVerifier, CellVerifyResult, cell_verifier_host_steps, cell_group_device,
     GroupedCellAnswers, cell_group_segmented_device, cell_verifier_groups_host_steps,
     recover_cells_and_kzg_proofs, recover_cells_and_kzg_proofs_batch, recover_cells_and_kzg_proofs_batch_device,

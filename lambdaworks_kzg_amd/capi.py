@@ -86,6 +86,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_cell_batch_challenge_host",
     "lwkzg_verify_cell_kzg_proof_each", "lwkzg_verify_cell_kzg_proof_each_device", "lwkzg_cell_verify_each_points",
     "lwkzg_verify_cell_kzg_proof_groups", "lwkzg_verify_cell_kzg_proof_groups_device", "lwkzg_cell_verify_groups_partials",
+    "lwkzg_verify_blob_cell_kzg_proofs_batch", "lwkzg_verify_blob_cell_kzg_proofs_batch_device", "lwkzg_blob_cell_verify_partials",
+    "lwkzg_verify_blob_cell_kzg_proofs_groups", "lwkzg_verify_blob_cell_kzg_proofs_groups_device", "lwkzg_blob_cell_verify_groups_partials",
     "lwkzg_recover_cells_and_kzg_proofs", "lwkzg_recover_cells_and_kzg_proofs_batch", "lwkzg_recover_cells_and_kzg_proofs_batch_device",
     "lwkzg_recover_cells_and_kzg_proofs_mixed", "lwkzg_recover_cells_and_kzg_proofs_mixed_device",
     "lwkzg_set_cell_proof_engine", "lwkzg_cell_proof_engine", "lwkzg_fk20_table_bytes", "lwkzg_fk20_chunk_blobs", "lwkzg_fk20_points",
@@ -162,6 +164,12 @@ def lib():
     l.lwkzg_verify_cell_kzg_proof_groups.argtypes = [pu8, pi32, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, pu64, sz, ps]
     l.lwkzg_verify_cell_kzg_proof_groups_device.argtypes = [pu8, pi32, vp, vp, vp, vp, sz, pu64, sz, ps, vp]
     l.lwkzg_cell_verify_groups_partials.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.c_char_p, sz, pu64, sz, ps]
+    l.lwkzg_verify_blob_cell_kzg_proofs_batch.argtypes = [C.POINTER(C.c_bool), C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_verify_blob_cell_kzg_proofs_batch_device.argtypes = [C.POINTER(C.c_bool), vp, vp, vp, sz, ps, vp]
+    l.lwkzg_blob_cell_verify_partials.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, ps]
+    l.lwkzg_verify_blob_cell_kzg_proofs_groups.argtypes = [pu8, pi32, C.c_char_p, C.c_char_p, C.c_char_p, sz, pu64, sz, ps]
+    l.lwkzg_verify_blob_cell_kzg_proofs_groups_device.argtypes = [pu8, pi32, vp, vp, vp, sz, pu64, sz, ps, vp]
+    l.lwkzg_blob_cell_verify_groups_partials.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, sz, pu64, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, sz, ps, C.POINTER(sz)]
     l.lwkzg_recover_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, pu64, vp, sz, sz, ps, vp, vp]
@@ -991,6 +999,76 @@ def cell_verify_groups_partials(groups, ts):
     cm, idx, ce, pf, n, off, g = _cell_groups(groups)
     out = C.create_string_buffer(CELL_VERIFY_PARTIAL_BYTES * max(g, 1))
     _check("lwkzg_cell_verify_groups_partials", lib().lwkzg_cell_verify_groups_partials(out, cm, idx, ce, pf, n, off, g, ts.ref()))
+    return [out.raw[CELL_VERIFY_PARTIAL_BYTES * j:CELL_VERIFY_PARTIAL_BYTES * (j + 1)] for j in range(g)]
+
+
+def _blob_items(blobs, commitments, cell_proofs):
+    """lists (or concatenated bytes) of n blobs, n commitments and n x 128 cell proofs -> the C arguments"""
+    bl = blobs if isinstance(blobs, (bytes, bytearray)) else b"".join(blobs)
+    cm = commitments if isinstance(commitments, (bytes, bytearray)) else b"".join(commitments)
+    pf = cell_proofs if isinstance(cell_proofs, (bytes, bytearray)) else b"".join(cell_proofs)
+    n = len(cm) // 48
+    if len(cm) != 48 * n or len(bl) != BYTES_PER_BLOB * n or len(pf) != 48 * CELLS_PER_EXT_BLOB * n:
+        raise ValueError("blobs, commitments and cell proofs must hold one blob, one commitment and 128 proofs per blob")
+    return bytes(bl), bytes(cm), bytes(pf), n
+
+
+def verify_blob_cell_kzg_proofs_batch(blobs, commitments, cell_proofs, ts):
+    """do the 128 cell proofs of every blob belong to the blob and its commitment (lwkzg_verify_blob_cell_kzg_proofs_batch)? The
+    answer of verify_cell_kzg_proof_batch on the 128 n items (commitments[b], k, cell k of blob b, cell_proofs[128 b + k]), without
+    the cells ever being passed. The empty call answers True."""
+    bl, cm, pf, n = _blob_items(blobs, commitments, cell_proofs)
+    ok = C.c_bool(False)
+    _check("lwkzg_verify_blob_cell_kzg_proofs_batch", lib().lwkzg_verify_blob_cell_kzg_proofs_batch(C.byref(ok), bl, cm, pf, n, ts.ref()))
+    return bool(ok.value)
+
+
+def verify_blob_cell_kzg_proofs_batch_device(blobs_ptr, comm_ptr, cell_proofs_ptr, n, ts, stream=None):
+    """the same on DEVICE pointers (n blobs, 48 n commitment bytes, 128 x 48 n proof bytes, produced on `stream`); the verdict is a
+    host bool, the call synchronous"""
+    ok = C.c_bool(False)
+    _check("lwkzg_verify_blob_cell_kzg_proofs_batch_device",
+           lib().lwkzg_verify_blob_cell_kzg_proofs_batch_device(C.byref(ok), blobs_ptr, comm_ptr, cell_proofs_ptr, n, ts.ref(), stream))
+    return bool(ok.value)
+
+
+def blob_cell_verify_partials(blobs, commitments, cell_proofs, ts):
+    """what cell_verify_partials gives for the 128 n items of these blobs, by the verdict call's own code path up to the pairing"""
+    bl, cm, pf, n = _blob_items(blobs, commitments, cell_proofs)
+    out = C.create_string_buffer(CELL_VERIFY_PARTIAL_BYTES)
+    _check("lwkzg_blob_cell_verify_partials", lib().lwkzg_blob_cell_verify_partials(out, bl, cm, pf, n, ts.ref()))
+    return out.raw
+
+
+def verify_blob_cell_kzg_proofs_groups(blobs, commitments, cell_proofs, group_sizes, ts):
+    """one verify_blob_cell_kzg_proofs_batch answer per group of blobs in one call (lwkzg_verify_blob_cell_kzg_proofs_groups):
+    group_sizes (in blobs) cuts the n blobs into consecutive groups -- the blobs of a transaction each; a list of (rc, ok)"""
+    bl, cm, pf, n = _blob_items(blobs, commitments, cell_proofs)
+    if sum(group_sizes) != n:
+        raise ValueError("group_sizes must add up to the number of blobs")
+    off, g = _group_offsets(group_sizes), len(group_sizes)
+    return _each("lwkzg_verify_blob_cell_kzg_proofs_groups", g,
+                 lambda ok, rc: lib().lwkzg_verify_blob_cell_kzg_proofs_groups(ok, rc, bl, cm, pf, n, off, g, ts.ref()))
+
+
+def verify_blob_cell_kzg_proofs_groups_device(blobs_ptr, comm_ptr, cell_proofs_ptr, n, group_sizes, ts, stream=None):
+    """the same on DEVICE pointers; group_sizes stays a host list; the answers come to the host, the call is synchronous"""
+    if sum(group_sizes) != n:
+        raise ValueError("group_sizes must add up to n")
+    off, g = _group_offsets(group_sizes), len(group_sizes)
+    return _each("lwkzg_verify_blob_cell_kzg_proofs_groups_device", g,
+                 lambda ok, rc: lib().lwkzg_verify_blob_cell_kzg_proofs_groups_device(ok, rc, blobs_ptr, comm_ptr, cell_proofs_ptr, n, off, g,
+                                                                                      ts.ref(), stream))
+
+
+def blob_cell_verify_groups_partials(blobs, commitments, cell_proofs, group_sizes, ts):
+    """per group of blobs what cell_verify_groups_partials gives for the group's 128-per-blob items: a list of g bytes objects"""
+    bl, cm, pf, n = _blob_items(blobs, commitments, cell_proofs)
+    if sum(group_sizes) != n:
+        raise ValueError("group_sizes must add up to the number of blobs")
+    off, g = _group_offsets(group_sizes), len(group_sizes)
+    out = C.create_string_buffer(CELL_VERIFY_PARTIAL_BYTES * max(g, 1))
+    _check("lwkzg_blob_cell_verify_groups_partials", lib().lwkzg_blob_cell_verify_groups_partials(out, bl, cm, pf, n, off, g, ts.ref()))
     return [out.raw[CELL_VERIFY_PARTIAL_BYTES * j:CELL_VERIFY_PARTIAL_BYTES * (j + 1)] for j in range(g)]
 
 

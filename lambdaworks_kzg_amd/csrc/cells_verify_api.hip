@@ -15,6 +15,7 @@
 // attribution share (cells_verify_host.h) it takes cell_r_bytes, and sums_from_pinned of async_verifier.h.
 #include "abi_guard.h"
 #include "cell_groups_plan.h"
+#include "cells_verify_blobs.h"
 #include "cells_verify_host.h"
 #include "cellv_bufs.h"
 #include "knobs.h"
@@ -59,13 +60,15 @@ C_KZG_RET reserve(Ctx *c, size_t n, Bufs &b) {
 
 // r (canonical limbs), the three sums of vmsm.hip and the compressed RLI of a batch. Host pointers are uploaded into the context's
 // buffer; device pointers (device_inputs) are read where they are, except the commitments and the indices, which come down first.
+// front (cells_verify_blobs.h): the caller makes the items, the lists and the grouping itself; the four item arrays are not read.
 C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], uint8_t rli48[48], const uint8_t *comms, const uint64_t *idx,
                           const uint8_t *cells, const uint8_t *proofs, size_t n, const KZGSettings *s, int mode, bool device_inputs,
-                          hipStream_t caller) {
+                          hipStream_t caller, const CellFront *front = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     const int le = mode_rules(mode).le();
-    Grouping g;
-    if (!device_inputs && !group_items(g, comms, idx, n)) {   // before any device work: decidable without a GPU
+    Grouping own;
+    const Grouping &g = front ? front->g : own;
+    if (!front && !device_inputs && !group_items(own, comms, idx, n)) {   // before any device work: decidable without a GPU
         set_error("verify_cell_kzg_proof_batch: a cell index is not below %d", kCellsPerBlob);
         return C_KZG_BADARGS;
     }
@@ -87,7 +90,7 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
         LWK_HIP(hipMemcpyAsync(h_comms.data(), comms, 48 * n, hipMemcpyDeviceToHost, st));
         LWK_HIP(hipMemcpyAsync(h_idx.data(), idx, 8 * n, hipMemcpyDeviceToHost, st));
         LWK_HIP(hipStreamSynchronize(st));
-        if (!group_items(g, h_comms.data(), h_idx.data(), n)) {
+        if (!group_items(own, h_comms.data(), h_idx.data(), n)) {
             set_error("verify_cell_kzg_proof_batch: a cell index is not below %d", kCellsPerBlob);
             return C_KZG_BADARGS;
         }
@@ -106,18 +109,23 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
     int32_t *pin_status = (int32_t *)(pin + 32 * c->cellv.cap);
 
     // the distinct commitments, padded with infinity encodings to the proofs' count: both point sets go through the two-set launches
-    std::vector<uint8_t> padded(48 * n, 0);
-    memcpy(padded.data(), g.distinct.data(), 48 * g.m);
-    for (size_t j = g.m; j < n; j++) padded[48 * j] = 0xc0;
-    LWK_HIP(hipMemcpyAsync(b.comm_in, padded.data(), 48 * n, hipMemcpyHostToDevice, st));
-    LWK_HIP(hipMemcpyAsync(b.rows, g.rows.data(), 4 * n, hipMemcpyHostToDevice, st));
-    LWK_HIP(hipMemcpyAsync(b.perm_row, g.perm_row.data(), 4 * n, hipMemcpyHostToDevice, st));
-    LWK_HIP(hipMemcpyAsync(b.row_off, g.row_off.data(), 4 * (g.m + 1), hipMemcpyHostToDevice, st));
-    LWK_HIP(hipMemcpyAsync(b.perm_col, g.perm_col.data(), 4 * n, hipMemcpyHostToDevice, st));
-    LWK_HIP(hipMemcpyAsync(b.col_off, g.col_off.data(), 4 * (kCellsPerBlob + 1), hipMemcpyHostToDevice, st));
+    std::vector<uint8_t> padded(front ? 0 : 48 * n, 0);
+    if (!front) {
+        memcpy(padded.data(), g.distinct.data(), 48 * g.m);
+        for (size_t j = g.m; j < n; j++) padded[48 * j] = 0xc0;
+        LWK_HIP(hipMemcpyAsync(b.comm_in, padded.data(), 48 * n, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(b.rows, g.rows.data(), 4 * n, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(b.perm_row, g.perm_row.data(), 4 * n, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(b.row_off, g.row_off.data(), 4 * (g.m + 1), hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(b.perm_col, g.perm_col.data(), 4 * n, hipMemcpyHostToDevice, st));
+        LWK_HIP(hipMemcpyAsync(b.col_off, g.col_off.data(), 4 * (kCellsPerBlob + 1), hipMemcpyHostToDevice, st));
+    }
     const uint8_t *d_cells = cells, *d_proofs = proofs;
     const uint64_t *d_idx = idx;
-    if (!device_inputs) {
+    if (front) {
+        if ((rc = front->items(c, st, b, nullptr, d_cells, d_proofs)) != C_KZG_OK) return rc;
+        d_idx = b.idx;
+    } else if (!device_inputs) {
         LWK_HIP(hipMemcpyAsync(b.cells, cells, n * kCellBytes, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemcpyAsync(b.proofs, proofs, 48 * n, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemcpyAsync(b.idx, idx, 8 * n, hipMemcpyHostToDevice, st));
@@ -132,6 +140,7 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
     const PointSet set_p{d_proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
     launch_decompress_points(set_p, &set_c, n, st);
     launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st);
+    if (front) front->fold_status(b.status, bad, st);
     clk.mark(2);
     LWK_HIP(hipMemcpyAsync(pin_dig, b.digests, 32 * n, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(pin_status, b.status, 4 * n, hipMemcpyDeviceToHost, st));
@@ -141,7 +150,8 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
     const auto t2 = std::chrono::steady_clock::now();
     for (size_t i = 0; i < n; i++)
         if (pin_status[i] != 0) {
-            set_error("verify_cell_kzg_proof_batch: a commitment or a proof is not a point of G1, or a cell element is not below r (first at %zu)", i);
+            set_error("verify_cell_kzg_proof_batch: a commitment or a proof is not a point of G1, or a cell element is not below r (first at %zu)%s", i,
+                      front ? ", or the front rejected the item's blob" : "");
             return bad_input(mode);
         }
     cell_batch_challenge(r_raw, g.distinct.data(), g.m, pin_dig, n, le);
@@ -177,14 +187,14 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
 
 // the verdict (ok) and / or r and the four sums (partials): one code path up to the pairing
 C_KZG_RET cell_batch_impl(bool *ok, uint8_t *partials, const void *comms, const void *idx, const void *cells, const void *proofs, size_t n,
-                          const KZGSettings *s, bool device_inputs, hipStream_t caller) {
+                          const KZGSettings *s, bool device_inputs, hipStream_t caller, const CellFront *front = nullptr) {
     if (!s) return C_KZG_BADARGS;
     const int mode = mode_of(s);
     if (n == 0) {
         if (ok) *ok = true;   // the consensus specs' and c-kzg-4844 2.x's rule for cells, in both modes
         return C_KZG_OK;
     }
-    if (!comms || !idx || !cells || !proofs) {
+    if (!front && (!comms || !idx || !cells || !proofs)) {
         set_error("verify_cell_kzg_proof_batch: NULL argument");
         return C_KZG_BADARGS;
     }
@@ -192,7 +202,7 @@ C_KZG_RET cell_batch_impl(bool *ok, uint8_t *partials, const void *comms, const 
     uint8_t sums[3][96], rli48[48];
     int infs[3];
     C_KZG_RET rc = cell_batch_sums(r_raw, sums, infs, rli48, (const uint8_t *)comms, (const uint64_t *)idx, (const uint8_t *)cells,
-                                   (const uint8_t *)proofs, n, s, mode, device_inputs, caller);
+                                   (const uint8_t *)proofs, n, s, mode, device_inputs, caller, front);
     if (rc != C_KZG_OK) return rc;
     if (partials) cell_r_bytes(partials, r_raw, mode);
     const auto t0 = std::chrono::steady_clock::now();
@@ -203,6 +213,11 @@ C_KZG_RET cell_batch_impl(bool *ok, uint8_t *partials, const void *comms, const 
 }
 
 }  // namespace
+
+// cells_verify_blobs.h
+C_KZG_RET cell_batch_front(bool *ok, uint8_t *partials, size_t n, const KZGSettings *s, hipStream_t caller, const CellFront &front) {
+    return cell_batch_impl(ok, partials, nullptr, nullptr, nullptr, nullptr, n, s, false, caller, &front);
+}
 
 }  // namespace lwk
 

@@ -18,6 +18,7 @@
 // Both host steps are the cell verifier's (cells_verify_async.hip) on the plan's view of the call, and the tests reach them without a
 // GPU (lwkzg_cell_verifier_groups_host_steps). The buffers behind r are CellgBufs / CellgPin (cells_verify_groups.h), the verifier's too.
 #include "abi_guard.h"
+#include "cells_verify_blobs.h"
 #include "cells_verify_groups.h"
 #include "cells_verify_host.h"
 #include "cellv_bufs.h"
@@ -229,10 +230,11 @@ hipError_t upload(T *dst, const std::vector<T> &src, hipStream_t st) {
 
 // the answers (ok_out, rc_out) or the partials (partials_out, LWKZG_CELL_VERIFY_PARTIAL_BYTES per group): one code path up to the pairing.
 // Host pointers are uploaded into the context's buffer; device pointers (device_inputs) are read where they are, except the commitments
-// and the indices, which come down first.
+// and the indices, which come down first. front (cells_verify_blobs.h): the caller makes the items, the lists and the plan itself; the
+// four item arrays are not read, and offsets are the items' (checked like anybody's).
 C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_out, const void *comms_v, const void *idx_v, const void *cells_v,
                            const void *proofs_v, size_t n, const uint64_t *offsets, size_t g, const KZGSettings *s, bool device_inputs,
-                           hipStream_t caller) {
+                           hipStream_t caller, const CellFront *front = nullptr) {
     // the call-level checks: before any device work, and nothing is written
     if (!s) return C_KZG_BADARGS;
     const bool no_output = partials_out ? false : !ok_out || !rc_out;
@@ -240,7 +242,7 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
         set_error("verify_cell_kzg_proof_groups: NULL argument");
         return C_KZG_BADARGS;
     }
-    if (n > 0 && (!comms_v || !idx_v || !cells_v || !proofs_v)) {
+    if (n > 0 && !front && (!comms_v || !idx_v || !cells_v || !proofs_v)) {
         set_error("verify_cell_kzg_proof_groups: NULL argument");
         return C_KZG_BADARGS;
     }
@@ -260,8 +262,9 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
     }
     const uint8_t *comms = (const uint8_t *)comms_v, *cells = (const uint8_t *)cells_v, *proofs = (const uint8_t *)proofs_v;
     const uint64_t *idx = (const uint64_t *)idx_v;
-    GroupsPlan plan;
-    if (!device_inputs) plan_groups(plan, comms, idx, n, offsets, g);
+    GroupsPlan own;
+    const GroupsPlan &plan = front ? front->plan : own;
+    if (!front && !device_inputs) plan_groups(own, comms, idx, n, offsets, g);
     Ctx *c = ctx_of(s);
     if (!c) return C_KZG_ERROR;
     if (!s->g2_values) {
@@ -279,7 +282,7 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
         LWK_HIP(hipMemcpyAsync(h_comms.data(), comms, 48 * n, hipMemcpyDeviceToHost, st));
         LWK_HIP(hipMemcpyAsync(h_idx.data(), idx, 8 * n, hipMemcpyDeviceToHost, st));
         LWK_HIP(hipStreamSynchronize(st));
-        plan_groups(plan, h_comms.data(), h_idx.data(), n, offsets, g);
+        plan_groups(own, h_comms.data(), h_idx.data(), n, offsets, g);
     }
     const auto t1 = std::chrono::steady_clock::now();
     DevSide dev;
@@ -296,11 +299,17 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
     clk.begin(st);
 
     // ---- first visit: the batch call's digests and validation over all n items ----
-    LWK_HIP(upload(b.comm_in, plan.distinct, st));
-    LWK_HIP(upload(b.rows, plan.rows, st));
+    if (!front) {
+        LWK_HIP(upload(b.comm_in, plan.distinct, st));
+        LWK_HIP(upload(b.rows, plan.rows, st));
+    }
     const uint8_t *d_cells = cells, *d_proofs = proofs;
     const uint64_t *d_idx = idx;
-    if (!device_inputs) {
+    if (front) {   // every list of the call at once, in front of the first visit
+        const CellFrontGroupLists gl{dev.item_group, dev.item_off, gb.slice_off, gb.slices};
+        if ((rc = front->items(c, st, b, &gl, d_cells, d_proofs)) != C_KZG_OK) return rc;
+        d_idx = b.idx;
+    } else if (!device_inputs) {
         LWK_HIP(hipMemcpyAsync(b.cells, cells, n * kCellBytes, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemcpyAsync(b.proofs, proofs, 48 * n, hipMemcpyHostToDevice, st));
         LWK_HIP(hipMemcpyAsync(b.idx, idx, 8 * n, hipMemcpyHostToDevice, st));
@@ -310,19 +319,21 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
     const PointSet set_p{d_proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
     LWK_HIP(launch_cellv_first_visit(d_cells, d_idx, b.rows, set_p, set_c, b.digests, dev.fault, b.status, (int)bad_input(mode), le, n, st,
                                      clk.on ? clk.ev[1] : nullptr));
+    if (front) front->fold_status(dev.fault, (int)bad_input(mode), st);
     clk.mark(2);
     LWK_HIP(hipMemcpyAsync(pin.digests, b.digests, 32 * n, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(pin.fault, dev.fault, 8 * n, hipMemcpyDeviceToHost, st));
-    // the lists of the second visit go up beside the first visit's kernels
-    LWK_HIP(upload(b.perm_row, plan.perm_row, st));
-    LWK_HIP(upload(b.row_off, plan.row_off, st));
-    LWK_HIP(upload(b.perm_col, plan.perm_col, st));
-    LWK_HIP(upload(b.col_off, plan.col_off, st));
-    LWK_HIP(upload(dev.item_group, plan.item_group, st));
-    LWK_HIP(upload(dev.item_off, plan.item_off, st));
-    LWK_HIP(upload(gb.slice_off, plan.slice_off, st));
-    if (!plan.slices.empty())
-        LWK_HIP(hipMemcpyAsync(gb.slices, plan.slices.data(), plan.slices.size() * sizeof(GroupSlice), hipMemcpyHostToDevice, st));
+    if (!front) {   // the lists of the second visit go up beside the first visit's kernels
+        LWK_HIP(upload(b.perm_row, plan.perm_row, st));
+        LWK_HIP(upload(b.row_off, plan.row_off, st));
+        LWK_HIP(upload(b.perm_col, plan.perm_col, st));
+        LWK_HIP(upload(b.col_off, plan.col_off, st));
+        LWK_HIP(upload(dev.item_group, plan.item_group, st));
+        LWK_HIP(upload(dev.item_off, plan.item_off, st));
+        LWK_HIP(upload(gb.slice_off, plan.slice_off, st));
+        if (!plan.slices.empty())
+            LWK_HIP(hipMemcpyAsync(gb.slices, plan.slices.data(), plan.slices.size() * sizeof(GroupSlice), hipMemcpyHostToDevice, st));
+    }
     LWK_HIP(hipGetLastError());
     LWK_HIP(hipStreamSynchronize(st));
     const auto t2 = std::chrono::steady_clock::now();
@@ -385,6 +396,12 @@ C_KZG_RET cell_groups_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_o
 }
 
 }  // namespace
+
+// cells_verify_blobs.h
+C_KZG_RET cell_groups_front(uint8_t *ok_out, int32_t *rc_out, uint8_t *partials_out, size_t n, const uint64_t *item_offsets, size_t g,
+                            const KZGSettings *s, hipStream_t caller, const CellFront &front) {
+    return cell_groups_impl(ok_out, rc_out, partials_out, nullptr, nullptr, nullptr, nullptr, n, item_offsets, g, s, false, caller, &front);
+}
 
 }  // namespace lwk
 

@@ -358,6 +358,7 @@ struct Ctx {
     GrowBuf celleach;                 // cells_verify_each.hip: everything a per-item cell verification keeps on the device, one allocation carved up (cap in items; under mu)
     GrowBuf cellg;                    // cells_verify_groups.hip: everything a grouped cell verification keeps on the device, one allocation carved up (cap in units: items or groups, whichever is more; under mu)
     uint8_t *cellg_pin = nullptr;     // hipHostMalloc, for cellg.cap units: digests and fault words down, the groups' powers and flags up, the sums down
+    GrowBuf blobv;                    // cells_verify_blobs.hip: the cells of a call's blobs (256 KiB each), the host form's upload slice, the blobs' status words and tables, one allocation carved up (cap in blobs; under mu)
     Fk20State fk20;                // fk20_api.hip: the opt-in FK20 cell proof engine (the primary's; a twin's is a copy of the pointers)
     Fr *recover_tab = nullptr;     // recover_api.hip: the table k_recover_setup leaves for the call's other kernels (kRecoverTabElems, with the context)
     GrowBuf recover_sets;          // recover_api.hip: the tables, lists and masks of a mixed recovery's distinct sets, one allocation carved up (cap in sets; under mu)

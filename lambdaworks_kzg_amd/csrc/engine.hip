@@ -288,6 +288,7 @@ void ctx_destroy(Ctx *c) {
     grow_free(c->recover_sets);
     fk20_free(c);
     grow_free(c->cellg);
+    grow_free(c->blobv);
     if (c->cellg_pin) hipHostFree(c->cellg_pin);
     if (c->cellv_pin) hipHostFree(c->cellv_pin);
     if (c->cellv_ev) hipEventDestroy(c->cellv_ev);
