@@ -868,7 +868,8 @@ C_KZG_RET lwkzg_cell_verify_groups_partials(uint8_t *out /* g x LWKZG_CELL_VERIF
  * slice: 128 KiB per blob of the call, at most 8 MiB), beside what the call over 128 n items keeps; a second call of the same size
  * allocates nothing, free_trusted_setup frees it. C_KZG_MALLOC, the error text naming the size, when it does not fit.
  * Use these when you hold blobs; the calls over items when you hold cells.
- * Out of scope: forms that do not block, lwkzg_multi_* forms, stream capture, versioned hashes, column sidecars in their own layout. */
+ * The forms that do not block are lwkzg_cell_verifier_enqueue_blobs / _blobs_groups below.
+ * Out of scope: lwkzg_multi_* forms, stream capture, versioned hashes, column sidecars in their own layout. */
 C_KZG_RET lwkzg_verify_blob_cell_kzg_proofs_batch(bool *ok, const Blob *blobs, const Bytes48 *commitments /* n */,
                                                   const Bytes48 *cell_proofs /* n x 128 */, size_t n, const KZGSettings *s);
 /* the same for inputs already in HBM (device pointers, 16-byte aligned, produced on `stream`, NULL = already complete). The blobs and
@@ -890,6 +891,64 @@ C_KZG_RET lwkzg_verify_blob_cell_kzg_proofs_groups_device(uint8_t *ok_out, int32
 C_KZG_RET lwkzg_blob_cell_verify_groups_partials(uint8_t *out /* g x LWKZG_CELL_VERIFY_PARTIAL_BYTES */, const Blob *blobs,
                                                  const Bytes48 *commitments, const Bytes48 *cell_proofs, size_t n,
                                                  const uint64_t *group_offsets /* in BLOBS, g + 1 */, size_t g, const KZGSettings *s);
+
+/* Cell proofs of WHOLE BLOBS without a parked host thread: the two device forms above on a cell verifier.
+ * Nothing of a call crosses to the host but what the verifier's two host functions read anyway: the blobs are extended into the
+ * verifier's own scratch, the n commitments are de-duplicated by one workgroup on the device, and every list of the 128 n expanded
+ * items is written there from its tables.
+ *   lwkzg_cell_verifier_new_blobs  everything lwkzg_cell_verifier_new_groups(out, s, 128 max_blobs, max_groups) allocates (max_groups == 0:
+ *                                what lwkzg_cell_verifier_new allocates), plus 256 KiB of cell scratch, 1 KiB of indices and 24 bytes of
+ *                                tables and status per blob, and the settings' workspace for the extension of max_blobs blobs (two
+ *                                slots per blob) on both of the settings' contexts. max_blobs is 1 .. 512 -- a call is one extension
+ *                                chunk --, anything else C_KZG_BADARGS before any device work, as are the arguments
+ *                                lwkzg_cell_verifier_new_groups refuses. The only one of these calls that may allocate or synchronise.
+ *                                The verifier still takes lwkzg_cell_verifier_enqueue and, with max_groups > 0, _enqueue_groups;
+ *                                calls of all four kinds share its ring and its depth and complete in order; pending / wait / free
+ *                                are unchanged, and free_trusted_setup waits for blob calls in flight too. A verifier from
+ *                                lwkzg_cell_verifier_new / _new_groups has no blob scratch and refuses a blob call on the spot.
+ *   lwkzg_cell_verifier_enqueue_blobs  n device-resident blobs, n commitments and 128 n cell proofs (16-byte aligned, produced on
+ *                                `stream`; NULL = already complete). *result gets what lwkzg_verify_blob_cell_kzg_proofs_batch_device
+ *                                answers for the same inputs in the settings' mode and on every MSM engine: rc and ok; m, the number
+ *                                of distinct commitments; partials, byte for byte what lwkzg_blob_cell_verify_partials writes (zero
+ *                                unless rc == C_KZG_OK). first_bad counts EXPANDED ITEMS (i = 128 b + k): the lowest item whose own
+ *                                cell, proof or commitment is at fault -- every item of a blob that the extension rejected counts
+ *                                (128 b for the blob), and a bad commitment counts at 128 x the blob it was first seen at. A rejected
+ *                                batch is an answer: the call returns C_KZG_OK and nothing behind r runs on it. n == 0 completes on
+ *                                the spot with ok = 1. Completed on the spot as the return value: n above max_blobs, a NULL array
+ *                                with n > 0, a freed setup, a verifier without blob scratch, and what lwkzg_cell_verifier_enqueue
+ *                                refuses.
+ *   lwkzg_cell_verifier_enqueue_blobs_groups  the same with HOST group_offsets counting BLOBS (g + 1 values, copied into the call's
+ *                                job slot before the call returns). For every j, (rc_out[j], ok_out[j]) and the partials are exactly
+ *                                those of lwkzg_verify_blob_cell_kzg_proofs_groups_device / lwkzg_blob_cell_verify_groups_partials;
+ *                                *result as lwkzg_cell_verifier_enqueue_groups completes it (first_bad the lowest GROUP that is not
+ *                                (C_KZG_OK, 1), m the total of the groups' distinct commitments). The completions on the spot are
+ *                                those of lwkzg_cell_verifier_enqueue_groups with "item array" read as the three blob arrays, g == 0
+ *                                with n == 0 and n == 0 with g > 0 included; a verifier made with max_groups == 0 refuses.
+ * Both return once everything is enqueued: no wait for a stream or an event, no allocation, no copy of the commitments to the host.
+ * Outputs are written before result->state, which is stored last with release order. Up to LWKZG_VERIFIER_DEPTH calls may be in
+ * flight; one more waits for the oldest.
+ * Not covered: host-pointer blobs, versioned hashes, column sidecars in their own layout, lwkzg_multi_* forms, stream capture, more
+ * than one extension chunk per call, a pairing on the device. */
+C_KZG_RET lwkzg_cell_verifier_new_blobs(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_blobs, size_t max_groups);
+C_KZG_RET lwkzg_cell_verifier_enqueue_blobs(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, const void *blobs_dev,
+                                            const void *commitments48_dev, const void *cell_proofs48_dev, size_t n, void *stream);
+C_KZG_RET lwkzg_cell_verifier_enqueue_blobs_groups(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, uint8_t *ok_out /* HOST, g */,
+                                                   int32_t *rc_out /* HOST, g */,
+                                                   uint8_t *partials_out /* HOST, g x LWKZG_CELL_VERIFY_PARTIAL_BYTES, or NULL */,
+                                                   const void *blobs_dev, const void *commitments48_dev, const void *cell_proofs48_dev,
+                                                   size_t n, const uint64_t *group_offsets /* HOST, in BLOBS, g + 1 */, size_t g,
+                                                   void *stream);
+/* Test hook, synchronous: the blob-level grouping and the expansion kernels alone, on n_blobs (1 .. 512) device-resident commitments
+ * and HOST offsets in blobs (valid, g > 0). The outputs are those of lwkzg_cell_group_segmented_device for the 128 n_blobs expanded
+ * items (n = 128 n_blobs in the sizes there; bad_words are zero; the slice table, where asked for, is cut with no group flagged), and,
+ * where not NULL, item_group_out (n words) and cell_indices_out (n uint64). The order inside a list of perm_row / perm_col is not
+ * defined. seed, hash_mask: of the keyed slot hash. C_KZG_BADARGS: NULL pointers, n_blobs 0 or above 512, bad offsets; C_KZG_ERROR:
+ * the kernel's error word was raised. */
+C_KZG_RET lwkzg_blob_group_device(uint32_t *rows, uint32_t *m_out, uint8_t *distinct48, uint32_t *first_item, uint32_t *perm_row,
+                                  uint32_t *row_off, uint32_t *perm_col, uint32_t *col_off, uint32_t *row_base, uint32_t *bad_words,
+                                  uint32_t *slices_out, uint32_t *slice_off_out, uint32_t *item_group_out, uint64_t *cell_indices_out,
+                                  const void *commitments48_dev, size_t n_blobs, const uint64_t *group_offsets /* HOST, in BLOBS, g + 1 */,
+                                  size_t g, uint64_t seed, uint32_t hash_mask, void *stream);
 
 /* The engine behind the cell proofs of lwkzg_compute_cells_and_kzg_proofs* and lwkzg_recover_cells_and_kzg_proofs* (DESIGN.md section 4h),
  * a per-settings choice. FK20 (Feist-Khovratovich): the 128 proofs of a blob as a Toeplitz product over G1 -- 64 coefficient transforms,

@@ -22,7 +22,7 @@ from .capi import (  # noqa: F401
     verify_blob_cell_kzg_proofs_batch, verify_blob_cell_kzg_proofs_batch_device, blob_cell_verify_partials,
     verify_blob_cell_kzg_proofs_groups, verify_blob_cell_kzg_proofs_groups_device, blob_cell_verify_groups_partials,
     CellVerifier, CellVerifyResult, cell_verifier_host_steps, cell_group_device,
-    GroupedCellAnswers, cell_group_segmented_device, cell_verifier_groups_host_steps,
+    GroupedCellAnswers, cell_group_segmented_device, cell_verifier_groups_host_steps, blob_group_device,
     recover_cells_and_kzg_proofs, recover_cells_and_kzg_proofs_batch, recover_cells_and_kzg_proofs_batch_device,
     recover_cells_and_kzg_proofs_mixed, recover_cells_and_kzg_proofs_mixed_device,
     CELL_PROOFS_FK20, CELL_PROOFS_MSM, fk20_chunk_blobs,

@@ -99,6 +99,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_cell_verifier_free", "lwkzg_cell_verifier_host_steps", "lwkzg_cell_group_device",
     "lwkzg_cell_verifier_new_groups", "lwkzg_cell_verifier_enqueue_groups", "lwkzg_cell_group_segmented_device",
     "lwkzg_cell_verifier_groups_host_steps",
+    "lwkzg_cell_verifier_new_blobs", "lwkzg_cell_verifier_enqueue_blobs", "lwkzg_cell_verifier_enqueue_blobs_groups", "lwkzg_blob_group_device",
     "lwkzg_verify_kzg_proof_batch", "lwkzg_verify_kzg_proof_batch_device", "lwkzg_verify_kzg_proof_batch_partial",
     "lwkzg_verifier_enqueue_openings", "lwkzg_verify_kzg_proof_each_device",
 ]
@@ -218,6 +219,11 @@ def lib():
                                                     sz, pu64, sz, C.c_uint64, C.c_uint32, vp]
     l.lwkzg_cell_verifier_groups_host_steps.argtypes = [C.POINTER(CellVerifyResult), pu8, pi32, C.c_char_p, pu64, sz, sz, pu32, pu32, pi32,
                                                         pu32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, ps, C.c_int]
+    l.lwkzg_cell_verifier_new_blobs.argtypes = [C.POINTER(vp), ps, sz, sz]
+    l.lwkzg_cell_verifier_enqueue_blobs.argtypes = [vp, C.POINTER(CellVerifyResult), vp, vp, vp, sz, vp]
+    l.lwkzg_cell_verifier_enqueue_blobs_groups.argtypes = [vp, C.POINTER(CellVerifyResult), pu8, pi32, C.c_char_p, vp, vp, vp, sz, pu64, sz, vp]
+    l.lwkzg_blob_group_device.argtypes = [pu32, pu32, C.c_char_p, pu32, pu32, pu32, pu32, pu32, pu32, pu32, pu32, pu32, pu32, pu64, vp, sz, pu64,
+                                          sz, C.c_uint64, C.c_uint32, vp]
     l.lwkzg_release_context.argtypes = [ps]
     l.lwkzg_reserve.argtypes = [ps, sz]
     l.lwkzg_reserve_streams.argtypes = [ps, sz, ci]
@@ -1221,6 +1227,32 @@ class CellVerifier(_AsyncVerifier):
         self._results = []
         _check(self._PREFIX + "new_groups", self._fn("new_groups")(C.byref(self.h), ts.ref(), max_cells, max_groups))
 
+    @classmethod
+    def for_blobs(cls, ts, max_blobs, max_groups=0):
+        """lwkzg_cell_verifier_new_blobs: a verifier of 128 max_blobs items (and max_groups groups) that also takes WHOLE BLOBS --
+        enqueue_blobs and, with max_groups > 0, enqueue_blobs_groups; max_blobs is 1 .. 512"""
+        self = cls.__new__(cls)
+        self.ts = ts
+        self.h = C.c_void_p()
+        self._results = []
+        _check(cls._PREFIX + "new_blobs", self._fn("new_blobs")(C.byref(self.h), ts.ref(), max_blobs, max_groups))
+        return self
+
+    def enqueue_blobs(self, blobs_ptr, comm_ptr, proofs_ptr, n, stream=None):
+        """verify_blob_cell_kzg_proofs_batch_device without the wait (lwkzg_cell_verifier_enqueue_blobs): n device-resident blobs, n
+        commitments, 128 n cell proofs. Returns at once with a CellVerifyResult; first_bad counts the 128 n expanded items. Raises
+        KzgError (its .result is the completed CellVerifyResult) for what the call itself refuses"""
+        return self._enqueue(blobs_ptr, comm_ptr, proofs_ptr, n, stream, call="enqueue_blobs")
+
+    def enqueue_blobs_groups(self, blobs_ptr, comm_ptr, proofs_ptr, n, group_sizes, stream=None, partials=True):
+        """one answer per group of blobs (lwkzg_cell_verifier_enqueue_blobs_groups): group_sizes (a host list, in BLOBS) cuts the n
+        blobs into consecutive groups -- the blobs of a transaction each. Returns at once with a GroupedCellAnswers, as enqueue_groups"""
+        ans = GroupedCellAnswers(len(group_sizes), partials)
+        off = _group_offsets(group_sizes)
+        ans.result = self._enqueue(ans._ok, ans._rc, ans._partials, blobs_ptr, comm_ptr, proofs_ptr, n, off, len(group_sizes), stream,
+                                   call="enqueue_blobs_groups", keep=ans)
+        return ans
+
     def enqueue(self, comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream=None):
         """returns at once; raises KzgError (its .result is the completed CellVerifyResult) for what the call itself refuses"""
         return self._enqueue(comm_ptr, indices_ptr, cells_ptr, proofs_ptr, n, stream)
@@ -1302,6 +1334,29 @@ def cell_group_segmented_device(comm_ptr, indices_ptr, n, group_sizes, seed, has
     out = {"rows": list(rows), "m": m.value, "distinct": distinct.raw[:48 * n], "first_item": list(first)[:m.value],
            "perm_row": list(perm_row), "row_off": list(row_off)[:m.value + 1], "perm_col": list(perm_col), "col_off": list(col_off),
            "row_base": list(row_base), "bad_words": list(bad)[:g]}
+    if slices:
+        out["slice_off"] = list(sl_off)
+        out["slices"] = [tuple(sl[4 * k:4 * k + 4]) for k in range(sl_off[3 * g])]
+    return out
+
+
+def blob_group_device(comm_ptr, n_blobs, group_sizes, seed, hash_mask=0xffffffff, stream=None, slices=True):
+    """test hook: the blob-level grouping and the expansion kernels of a cell verifier's blob calls on n_blobs DEVICE commitments
+    (group_sizes in blobs). Returns cell_group_segmented_device's dict for the n = 128 n_blobs expanded items, and item_group (n) and
+    idx (n). The order inside a list of perm_row / perm_col is not defined."""
+    u32, g, n = C.c_uint32, len(group_sizes), 128 * n_blobs
+    rows, first, perm_row, row_off, perm_col = (u32 * n)(), (u32 * n)(), (u32 * n)(), (u32 * (n + 1))(), (u32 * n)()
+    col_off, row_base, bad, m = (u32 * (128 * g + 1))(), (u32 * (g + 1))(), (u32 * max(g, 1))(), u32(0)
+    item_group, idx = (u32 * n)(), (C.c_uint64 * n)()
+    max_slices = 3 * (n // 64 + g)
+    sl, sl_off = ((u32 * (4 * max_slices))(), (u32 * (3 * g + 1))()) if slices else (None, None)
+    distinct = C.create_string_buffer(48 * max(n, 1))
+    _check("lwkzg_blob_group_device",
+           lib().lwkzg_blob_group_device(rows, C.byref(m), distinct, first, perm_row, row_off, perm_col, col_off, row_base, bad, sl, sl_off,
+                                         item_group, idx, comm_ptr, n_blobs, _group_offsets(group_sizes), g, seed, hash_mask, stream))
+    out = {"rows": list(rows), "m": m.value, "distinct": distinct.raw[:48 * n], "first_item": list(first)[:m.value],
+           "perm_row": list(perm_row), "row_off": list(row_off)[:m.value + 1], "perm_col": list(perm_col), "col_off": list(col_off),
+           "row_base": list(row_base), "bad_words": list(bad)[:g], "item_group": list(item_group), "idx": list(idx)}
     if slices:
         out["slice_off"] = list(sl_off)
         out["slices"] = [tuple(sl[4 * k:4 * k + 4]) for k in range(sl_off[3 * g])]

@@ -27,9 +27,18 @@
 // lwkzg_verify_cell_kzg_proof_groups_device's answers, one per group, through the same shell -- the segmented grouping and the slice
 // table of cell_group.hip, the launches and the buffers behind r of cells_verify_groups.h (CellgBufs, CellgPin), two host functions
 // of their own around groups_decide and groups_answers (enqueue_groups_on below).
+//
+// A verifier made by lwkzg_cell_verifier_new_blobs also takes WHOLE BLOBS (lwkzg_cell_verifier_enqueue_blobs / _blobs_groups; DESIGN.md
+// section 4t): the answers of lwkzg_verify_blob_cell_kzg_proofs_batch_device / _groups_device through the same two enqueue functions.
+// Where a call's items and lists come from is their parameter (CallItems): the caller's four arrays and the item-level grouping, or
+// blob_items_on -- the blobs extended into the verifier's scratch (cells_verify_blobs.h: launch_blob_cells), their n commitments
+// grouped by one workgroup and every 128 n-entry list written from its tables (cell_blobs_group.hip) -- and, behind the first visit,
+// the rejected blobs' status words folded into the fault words. Nothing of a blob call comes down but what the host functions read.
 #include "abi_guard.h"
 #include "async_verifier.h"
+#include "cell_blobs_group.h"
 #include "cell_group.cuh"
+#include "cells_verify_blobs.h"
 #include "cells_verify_groups.h"
 #include "cells_verify_host.h"
 #include "cellv_bufs.h"
@@ -55,7 +64,29 @@ struct GroupCall {
     uint32_t *h_off = nullptr;   // pinned, gcap + 1 words of this slot alone: the upload reads it after the enqueue has returned
 };
 
+static_assert(kBlobGroupCap == kCellsChunk, "a blob call is one extension chunk, grouped by one workgroup");
+
+// what a BLOB call reads its items from (section 4t); the verifier's own, out of its device block
+struct BlobScratch {
+    uint8_t *cells = nullptr;      // 256 KiB per blob: the 128 cells the extension leaves
+    uint64_t *idx = nullptr;       // the expanded items' indices
+    int32_t *status = nullptr;     // one word per blob: the extension's verdict
+    BlobGroupOut tab = {};         // the per-blob tables of the grouping (cell_blobs_group.h); distinct and head are the call's
+};
+
+// where a call's items and lists come from: the caller's four arrays (an item call), or nb whole blobs (blobs != nullptr), whose
+// cells and indices blob_items_on leaves in the verifier's scratch
+struct CallItems {
+    const uint8_t *comms, *cells, *proofs;
+    const uint64_t *idx;
+    const uint8_t *blobs = nullptr;
+    size_t nb = 0;
+};
+
 struct CellVerifier : AsyncVerifier {
+    // ---- blob calls (lwkzg_cell_verifier_new_blobs; bcap == 0: none) ----
+    size_t bcap = 0;
+    BlobScratch bs;
     // ---- grouped calls (lwkzg_cell_verifier_new_groups; gcap == 0: none) ----
     size_t gcap = 0, max_slices = 0;
     CellGroupSegBufs sg;
@@ -105,6 +136,18 @@ size_t carve_device(CellVerifier *v, uint8_t *base) {
         const size_t gc = v->gcap;
         cell_group_seg_carve(v->sg, v->g, cv, v->cap, gc);
         cellg_carve(v->gb, cv, gc, v->max_slices);
+    }
+    if (v->bcap) {
+        const size_t nb = v->bcap;
+        BlobScratch &s = v->bs;
+        cv.take(s.cells, nb * kBlobCellBytes);
+        cv.take(s.idx, nb * kCellsPerBlob * 8);
+        cv.take(s.status, nb * 4);
+        cv.take(s.tab.brow, nb * 4);
+        cv.take(s.tab.bgroup, nb * 4);
+        cv.take(s.tab.bperm, nb * 4);
+        cv.take(s.tab.brow_off, (nb + 1) * 4);
+        cv.take(s.tab.bfirst, nb * 4);
     }
     return cv.bytes();
 }
@@ -274,8 +317,9 @@ uint64_t draw_seed(const void *salt) {
     return s;
 }
 
-// max_groups == 0: a verifier of batch calls alone (lwkzg_cell_verifier_new)
-C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_cells, size_t max_groups) {
+// max_groups == 0: a verifier of batch calls alone (lwkzg_cell_verifier_new); max_blobs > 0: max_cells is 128 max_blobs and the verifier
+// takes blob calls too (lwkzg_cell_verifier_new_blobs)
+C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_cells, size_t max_groups, size_t max_blobs = 0) {
     if (!out) return C_KZG_BADARGS;
     *out = nullptr;
     if (!s || max_cells == 0 || max_cells >= 0x40000000u || max_groups > 0x40000000u) return C_KZG_BADARGS;
@@ -290,6 +334,7 @@ C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, 
     if (!v) return C_KZG_MALLOC;
     v->slots = group_table_slots(max_cells);
     v->gcap = max_groups;
+    v->bcap = max_blobs;
     v->max_slices = max_groups ? plan_max_slices(max_cells, max_groups) : 0;
     v->seed = draw_seed(v);
     memset(v->g2, 0, sizeof v->g2);
@@ -298,7 +343,8 @@ C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, 
     v->own.fs = nullptr;
     v->own.g1_values = nullptr;
     v->own.g2_values = v->g2;
-    const size_t msm_slots = max_groups ? min_sz(max_groups, kMaxChunk) : 1;
+    // a blob call's extension takes what cells_chunks reserves for a chunk without proofs: two slots per blob
+    const size_t group_slots = max_groups ? min_sz(max_groups, kMaxChunk) : 1, msm_slots = group_slots > 2 * max_blobs ? group_slots : 2 * max_blobs;
     C_KZG_RET rc = C_KZG_OK;
     try {
         v->g_rc.resize(max_groups);
@@ -330,9 +376,33 @@ C_KZG_RET cell_verifier_new_impl(LwkzgCellVerifier **out, const KZGSettings *s, 
     return async_verifier_new_end(out, v, rc);
 }
 
+// ---- the items of a blob call -----------------------------------------------------------------------------------------
+// On st, in front of the first visit, for the it.nb blobs of the call: the extension into the verifier's scratch with a status word per
+// blob; the commitments grouped (k_blob_group, one workgroup); every list of the 128 nb items where the pipeline reads it
+// (k_blob_items_dev). g == 0: a batch call -- the lists of v->g, one group of all blobs; else a grouped call of g groups -- the lists
+// of v->sg, whose item_off the caller has uploaded (in items), and zero bad words. Leaves it.cells and it.idx at the scratch
+C_KZG_RET blob_items_on(CellVerifier *v, Ctx *c, const AsyncJob *j, CallItems &it, size_t g, hipStream_t st) {
+    BlobScratch &s = v->bs;
+    const CellGroupSegBufs &sg = v->sg;
+    C_KZG_RET rc = launch_blob_cells(c, s.cells, s.status, it.blobs, it.nb, j->mode, st);
+    if (rc != C_KZG_OK) return rc;
+    BlobGroupOut tab = s.tab;
+    tab.row_base = g ? sg.row_base : nullptr;
+    tab.distinct = v->b.comm_in;   // (v->g.distinct and v->sg.distinct)
+    tab.head = g ? sg.head : v->g.head;
+    const uint32_t *item_off = g ? sg.item_off : nullptr;
+    if (g) LWK_HIP(hipMemsetAsync(sg.gbad, 0, g * 4, st));
+    LWK_HIP(launch_cell_blobs_group(it.comms, item_off, it.nb, g ? g : 1, v->seed, 0xffffffffu, tab, st));
+    const BlobItemsOut lists{s.idx, v->b.rows, v->b.perm_row, v->b.perm_col, g ? sg.item_group : nullptr, g ? sg.col_off : v->b.col_off,
+                             v->b.row_off, v->g.first_item};   // (the lists of v->g and v->sg are v->b's)
+    LWK_HIP(launch_cell_blobs_items(tab, item_off, it.nb, g ? g : 1, lists, st));
+    it.cells = s.cells;
+    it.idx = s.idx;
+    return C_KZG_OK;
+}
+
 // everything of one call on context c, enqueued; caller holds c->mu. *hf: host functions handed to the runtime so far
-C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t *comms, const uint64_t *idx, const uint8_t *cells, const uint8_t *proofs,
-                     hipStream_t caller, int *hf) {
+C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, AsyncJob *j, CallItems it, hipStream_t caller, int *hf) {
     LWK_HIP(hipSetDevice(c->device));
     C_KZG_RET rc = ctx_reserve(c, 1);   // (at once unless this context was made after the verifier)
     if (rc != C_KZG_OK) return rc;
@@ -349,9 +419,16 @@ C_KZG_RET enqueue_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t *comms,
     }
     WsUse wsu(c, st);
     LWK_HIP(hipMemsetAsync(b.sc_c, 0, 32 * n, st));
-    launch_cell_group(comms, idx, n, v->slots, v->seed, 0xffffffffu, v->g, st);
+    if (it.blobs) {
+        if ((rc = blob_items_on(v, c, j, it, 0, st)) != C_KZG_OK) return rc;
+    } else {
+        launch_cell_group(it.comms, it.idx, n, v->slots, v->seed, 0xffffffffu, v->g, st);
+    }
+    const uint8_t *cells = it.cells, *proofs = it.proofs;
+    const uint64_t *idx = it.idx;
     const PointSet set_p{proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
     LWK_HIP(launch_cellv_first_visit(cells, idx, b.rows, set_p, set_c, b.digests, v->fault, b.status, bad, le, n, st));
+    if (it.blobs) LWK_HIP(launch_blob_fold_status(v->fault, v->bs.status, it.nb, j->mode, bad, st));
     LWK_HIP(hipEventRecord(v->ev_fork, st));
     LWK_HIP(hipStreamWaitEvent(side, v->ev_fork, 0));
     launch_vmsm_multiples2(b.pts_p, b.kind_p, b.tab_p, b.pts_c, b.kind_c, b.tab_c, b.vm_tmp, b.vm_pre, n, side);   // beside the copies and the hash
@@ -395,7 +472,7 @@ C_KZG_RET cell_verifier_enqueue_impl(const LwkzgCellVerifier *handle, LwkzgCellV
     ensure_lagrange(v->ctx, mode);   // (a load unless the mode changed to c-kzg after lwkzg_cell_verifier_new)
     std::lock_guard<std::mutex> enq(v->enq_mu);
     return async_enqueue(v, res, n, mode, caller,
-                         [&](Ctx *c, AsyncJob *j, int *hf) { return enqueue_on(v, c, j, comms, idx, cells, proofs, caller, hf); });
+                         [&](Ctx *c, AsyncJob *j, int *hf) { return enqueue_on(v, c, j, CallItems{comms, cells, proofs, idx}, caller, hf); });
 }
 
 // ---- a grouped call --------------------------------------------------------------------------------------------------
@@ -408,8 +485,7 @@ C_KZG_RET cell_verifier_enqueue_impl(const LwkzgCellVerifier *handle, LwkzgCellV
 //                   live count from memory), k_cellg_fold; sums, flags and RLIs -> pinned, one copy each
 //                   HOST FUNCTION 2: the g pairings on the host threads -- the stream stands still for them --, the outputs, the
 //                   result, state = 1 (release), slot freed
-C_KZG_RET enqueue_groups_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t *comms, const uint64_t *idx, const uint8_t *cells,
-                            const uint8_t *proofs, hipStream_t caller, int *hf) {
+C_KZG_RET enqueue_groups_on(CellVerifier *v, Ctx *c, AsyncJob *j, CallItems it, hipStream_t caller, int *hf) {
     LWK_HIP(hipSetDevice(c->device));
     C_KZG_RET rc = ctx_reserve(c, min_sz(v->gcap, kMaxChunk));   // (at once unless this context was made after the verifier)
     if (rc != C_KZG_OK) return rc;
@@ -429,9 +505,16 @@ C_KZG_RET enqueue_groups_on(CellVerifier *v, Ctx *c, AsyncJob *j, const uint8_t 
     }
     WsUse wsu(c, st);
     LWK_HIP(hipMemcpyAsync(sg.item_off, gc.h_off, (g + 1) * 4, hipMemcpyHostToDevice, st));
-    launch_cell_group_seg(comms, idx, n, g, v->slots, v->seed, 0xffffffffu, sg, st);
+    if (it.blobs) {
+        if ((rc = blob_items_on(v, c, j, it, g, st)) != C_KZG_OK) return rc;
+    } else {
+        launch_cell_group_seg(it.comms, it.idx, n, g, v->slots, v->seed, 0xffffffffu, sg, st);
+    }
+    const uint8_t *cells = it.cells, *proofs = it.proofs;
+    const uint64_t *idx = it.idx;
     const PointSet set_p{proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
     LWK_HIP(launch_cellv_first_visit(cells, idx, sg.rows, set_p, set_c, b.digests, v->fault, b.status, bad, le, n, st));
+    if (it.blobs) LWK_HIP(launch_blob_fold_status(v->fault, v->bs.status, it.nb, j->mode, bad, st));
     LWK_HIP(hipMemcpyAsync(v->h_head, sg.head, kGroupHeadWords * 4, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(v->h_rowbase, sg.row_base, (g + 1) * 4, hipMemcpyDeviceToHost, st));
     LWK_HIP(hipMemcpyAsync(v->h_gbad, sg.gbad, g * 4, hipMemcpyDeviceToHost, st));
@@ -493,7 +576,81 @@ C_KZG_RET cell_verifier_enqueue_groups_impl(const LwkzgCellVerifier *handle, Lwk
         GroupCall &gc = v->gcall[j - v->ring.slots];   // the slot's own: no call in flight reads it
         gc.ok_out = ok_out, gc.rc_out = rc_out, gc.partials_out = partials_out, gc.g = g;
         for (size_t k = 0; k <= g; k++) gc.h_off[k] = (uint32_t)offsets[k];
-        return enqueue_groups_on(v, c, j, comms, idx, cells, proofs, caller, hf);
+        return enqueue_groups_on(v, c, j, CallItems{comms, cells, proofs, idx}, caller, hf);
+    });
+}
+
+// ---- blob calls: the checks of the item calls with blobs for items, then the same two enqueue functions ----
+// what both blob calls decide first: async_enqueue_checks, then that the verifier takes blobs, and nb of them
+C_KZG_RET blob_enqueue_checks(CellVerifier **out, const LwkzgCellVerifier *handle, LwkzgCellVerifyResult *res, size_t nb, const char *fn) {
+    AsyncVerifier *base;
+    const C_KZG_RET refused = async_enqueue_checks(&base, handle, kCellVerifierMagic, res, 0, fn, "blobs");
+    if (refused != C_KZG_OK) return refused;
+    CellVerifier *v = *out = static_cast<CellVerifier *>(base);
+    if (v->bcap == 0 || nb > v->bcap) {
+        set_error(v->bcap ? "%s: %zu blobs, the verifier was created for %zu" : "%s: the verifier was not created by lwkzg_cell_verifier_new_blobs and has no scratch for the cells of blobs",
+                  fn, nb, v->bcap);
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    return C_KZG_OK;
+}
+
+C_KZG_RET cell_verifier_enqueue_blobs_impl(const LwkzgCellVerifier *handle, LwkzgCellVerifyResult *res, const uint8_t *blobs, const uint8_t *comms,
+                                           const uint8_t *proofs, size_t nb, hipStream_t caller) {
+    const char *fn = "lwkzg_cell_verifier_enqueue_blobs";
+    CellVerifier *v;
+    const C_KZG_RET refused = blob_enqueue_checks(&v, handle, res, nb, fn);
+    if (refused != C_KZG_OK) return refused;
+    if (nb == 0) {   // the batch call's answer to no items
+        complete_now(res, C_KZG_OK, true);
+        return C_KZG_OK;
+    }
+    if (!blobs || !comms || !proofs) {
+        set_error("%s: NULL argument", fn);
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    const int mode = mode_of(v->s);
+    ensure_lagrange(v->ctx, mode);
+    std::lock_guard<std::mutex> enq(v->enq_mu);
+    return async_enqueue(v, res, nb * kCellsPerBlob, mode, caller, [&](Ctx *c, AsyncJob *j, int *hf) {
+        return enqueue_on(v, c, j, CallItems{comms, nullptr, proofs, nullptr, blobs, nb}, caller, hf);
+    });
+}
+
+C_KZG_RET cell_verifier_enqueue_blobs_groups_impl(const LwkzgCellVerifier *handle, LwkzgCellVerifyResult *res, uint8_t *ok_out, int32_t *rc_out,
+                                                  uint8_t *partials_out, const uint8_t *blobs, const uint8_t *comms, const uint8_t *proofs,
+                                                  size_t nb, const uint64_t *offsets, size_t g, hipStream_t caller) {
+    const char *fn = "lwkzg_cell_verifier_enqueue_blobs_groups";
+    CellVerifier *v;
+    const C_KZG_RET refused = blob_enqueue_checks(&v, handle, res, nb, fn);
+    if (refused != C_KZG_OK) return refused;
+    if (v->gcap == 0 || g > v->gcap) {
+        set_error(v->gcap ? "%s: %zu groups, the verifier was created for %zu" : "%s: the verifier was created without groups (max_groups == 0)", fn,
+                  g, v->gcap);
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    if ((g > 0 && (!ok_out || !rc_out || !offsets)) || (nb > 0 && (!blobs || !comms || !proofs))) {
+        set_error("%s: NULL argument", fn);
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    if (!group_offsets_valid(offsets, g, nb)) {
+        set_error("%s: group_offsets must be %zu ascending values from 0 to %zu (blobs)", fn, g + 1, nb);
+        return async_refuse(res, C_KZG_BADARGS);
+    }
+    if (nb == 0) {   // no group, or empty groups alone: the batch call's answer to n == 0 for each
+        for (size_t j = 0; j < g; j++) rc_out[j] = (int32_t)C_KZG_OK, ok_out[j] = 1;
+        if (partials_out) memset(partials_out, 0, g * (size_t)LWKZG_CELL_VERIFY_PARTIAL_BYTES);
+        complete_now(res, C_KZG_OK, true);
+        return C_KZG_OK;
+    }
+    const int mode = mode_of(v->s);
+    ensure_lagrange(v->ctx, mode);
+    std::lock_guard<std::mutex> enq(v->enq_mu);
+    return async_enqueue(v, res, nb * kCellsPerBlob, mode, caller, [&](Ctx *c, AsyncJob *j, int *hf) {
+        GroupCall &gc = v->gcall[j - v->ring.slots];   // the slot's own: no call in flight reads it
+        gc.ok_out = ok_out, gc.rc_out = rc_out, gc.partials_out = partials_out, gc.g = g;
+        for (size_t k = 0; k <= g; k++) gc.h_off[k] = (uint32_t)(offsets[k] * kCellsPerBlob);   // in ITEMS, as every reader takes them
+        return enqueue_groups_on(v, c, j, CallItems{comms, nullptr, proofs, nullptr, blobs, nb}, caller, hf);
     });
 }
 
@@ -535,6 +692,36 @@ C_KZG_RET lwkzg_cell_verifier_enqueue(LwkzgCellVerifier *v, LwkzgCellVerifyResul
     return guarded("lwkzg_cell_verifier_enqueue", [&] {
         return cell_verifier_enqueue_impl(v, result, (const uint8_t *)commitments48_dev, (const uint64_t *)cell_indices_dev,
                                           (const uint8_t *)cells_dev, (const uint8_t *)proofs48_dev, n, (hipStream_t)stream);
+    });
+}
+
+C_KZG_RET lwkzg_cell_verifier_new_blobs(LwkzgCellVerifier **out, const KZGSettings *s, size_t max_blobs, size_t max_groups) {
+    return guarded("lwkzg_cell_verifier_new_blobs", [&] {
+        if (max_blobs == 0 || max_blobs > kBlobGroupCap) {   // one extension chunk, one workgroup's grouping
+            if (out) *out = nullptr;
+            if (out && s) set_error("lwkzg_cell_verifier_new_blobs: max_blobs must be 1 .. %u", kBlobGroupCap);
+            return C_KZG_BADARGS;
+        }
+        return cell_verifier_new_impl(out, s, max_blobs * kCellsPerBlob, max_groups, max_blobs);
+    });
+}
+
+C_KZG_RET lwkzg_cell_verifier_enqueue_blobs(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, const void *blobs_dev, const void *commitments48_dev,
+                                            const void *cell_proofs48_dev, size_t n, void *stream) {
+    return guarded("lwkzg_cell_verifier_enqueue_blobs", [&] {
+        return cell_verifier_enqueue_blobs_impl(v, result, (const uint8_t *)blobs_dev, (const uint8_t *)commitments48_dev,
+                                                (const uint8_t *)cell_proofs48_dev, n, (hipStream_t)stream);
+    });
+}
+
+C_KZG_RET lwkzg_cell_verifier_enqueue_blobs_groups(LwkzgCellVerifier *v, LwkzgCellVerifyResult *result, uint8_t *ok_out, int32_t *rc_out,
+                                                   uint8_t *partials_out, const void *blobs_dev, const void *commitments48_dev,
+                                                   const void *cell_proofs48_dev, size_t n, const uint64_t *group_offsets, size_t g,
+                                                   void *stream) {
+    return guarded("lwkzg_cell_verifier_enqueue_blobs_groups", [&] {
+        return cell_verifier_enqueue_blobs_groups_impl(v, result, ok_out, rc_out, partials_out, (const uint8_t *)blobs_dev,
+                                                       (const uint8_t *)commitments48_dev, (const uint8_t *)cell_proofs48_dev, n, group_offsets,
+                                                       g, (hipStream_t)stream);
     });
 }
 

@@ -31,6 +31,13 @@ struct CellFront {
     virtual ~CellFront() {}
 };
 
+// ---- the two device steps of a blob front, shared with the cell verifier's blob calls (cells_verify_async.hip; section 4t) ----
+// nb device-resident blobs to their 128 cells each (cells: 256 KiB per blob) with a status word per blob: the front of the compute
+// call, cells_chunks without proofs. The caller holds the context's lock and its workspace; enqueues on st, reads nothing back
+C_KZG_RET launch_blob_cells(Ctx *c, uint8_t *cells, int32_t *bstatus, const uint8_t *blobs_dev, size_t nb, int mode, hipStream_t st);
+// words[i] = bad_code for the 128 items of every blob whose status word is set (nothing in a mode that rejects no blob)
+hipError_t launch_blob_fold_status(int32_t *words, const int32_t *bstatus, size_t nb, int mode, int bad_code, hipStream_t st);
+
 // lwkzg_verify_cell_kzg_proof_batch / lwkzg_cell_verify_partials over the n items of `front` (n > 0)
 C_KZG_RET cell_batch_front(bool *ok, uint8_t *partials, size_t n, const KZGSettings *s, hipStream_t caller, const CellFront &front);
 // lwkzg_verify_cell_kzg_proof_groups / lwkzg_cell_verify_groups_partials over the n items of `front` in the g groups of item_offsets

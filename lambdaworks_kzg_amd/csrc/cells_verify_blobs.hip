@@ -17,6 +17,8 @@
 //            items of a rejected blob the mode's bad-input code, so that the call (batch) or exactly the blob's group (groups) answers it
 // The scratch (Ctx::blobv, grow-only, freed with the settings): 256 KiB of cells + 16 bytes of tables per blob, and the host forms'
 // upload slice (128 KiB per blob, at most kHostSlice of them). No proofs are computed, so the cell proof engine does not matter.
+// The forms that do not block are the cell verifier's blob calls (cells_verify_async.hip): they share the two
+// device steps at the end of the front below (launch_blob_cells, launch_blob_fold_status) and group on the device instead of here.
 #include "abi_guard.h"
 #include "cell_blobs_plan.h"
 #include "cells_verify_blobs.h"
@@ -58,6 +60,16 @@ __global__ __launch_bounds__(256) void k_blob_fold_status(int32_t *__restrict__ 
 unsigned grid_for(size_t work) {
     const size_t blocks = (work + 255) / 256;
     return (unsigned)(blocks < 1 ? 1 : blocks > 4096 ? 4096 : blocks);
+}
+
+// where the coefficient step of cells_chunks reads the blobs (device memory at src): the front of the compute call
+CoefficientStep coefficient_step(Ctx *c, const uint8_t *src, int mode, hipStream_t st) {
+    const ModeRules rules = mode_rules(mode);
+    return [=](size_t off, size_t m, int32_t *stt) {
+        const uint8_t *in = src + off * (size_t)kBlobBytes;
+        if (!rules.evaluation_form) launch_parse_be_reduce(in, c->ws.scalars, m * kBlobElems, st);
+        else launch_blob_evaluations_to_coefficients(in, c->ws.scalars, c->tw28_inv, stt, m, st, rules.le());
+    };
 }
 
 // ---- the settings' scratch -----------------------------------------------------------------------------------------------------------------
@@ -113,18 +125,11 @@ struct BlobFront : CellFront {
         C_KZG_RET rc = reserve(c, nb, bb);
         if (rc != C_KZG_OK) return rc;
         d_status = bb.status;
-        const ModeRules rules = mode_rules(mode);
-        const uint8_t *src = blobs;   // where the coefficient step reads the blobs of the part at hand
-        const CoefficientStep coefficients = [&](size_t off, size_t m, int32_t *stt) {
-            const uint8_t *in = src + off * (size_t)kBlobBytes;
-            if (!rules.evaluation_form) launch_parse_be_reduce(in, c->ws.scalars, m * kBlobElems, st);
-            else launch_blob_evaluations_to_coefficients(in, c->ws.scalars, c->tw28_inv, stt, m, st, rules.le());
-        };
         if (device_inputs) {
-            if ((rc = cells_chunks(c, bb.cells, nullptr, nb, mode, st, bb.status, coefficients, nb)) != C_KZG_OK) return rc;
+            if ((rc = launch_blob_cells(c, bb.cells, bb.status, blobs, nb, mode, st)) != C_KZG_OK) return rc;
             proofs_out = proofs;
         } else {
-            src = bb.stage;
+            const CoefficientStep coefficients = coefficient_step(c, bb.stage, mode, st);
             for (size_t off = 0; off < nb; off += kHostSlice) {   // (the stream orders a slice's upload behind its predecessor's parse)
                 const size_t m = min_sz(kHostSlice, nb - off);
                 LWK_HIP(hipMemcpyAsync(bb.stage, blobs + off * (size_t)kBlobBytes, m * (size_t)kBlobBytes, hipMemcpyHostToDevice, st));
@@ -161,11 +166,25 @@ struct BlobFront : CellFront {
     }
 
     void fold_status(int32_t *words, int bad_code, hipStream_t st) const override {
-        if (!mode_rules(mode).evaluation_form) return;   // reference mode reduces: no blob is rejected
-        ProfScope p("k_blob_fold_status", st);
-        hipLaunchKernelGGL(k_blob_fold_status, dim3(grid_for(nb * kCellsPerBlob)), dim3(256), 0, st, words, d_status, (uint32_t)nb, bad_code);
+        (void)launch_blob_fold_status(words, d_status, nb, mode, bad_code, st);   // (a failed launch: the pipeline's hipGetLastError)
     }
 };
+
+}  // namespace
+
+// cells_verify_blobs.h: the two device steps, shared with the cell verifier's blob calls
+C_KZG_RET launch_blob_cells(Ctx *c, uint8_t *cells, int32_t *bstatus, const uint8_t *blobs_dev, size_t nb, int mode, hipStream_t st) {
+    return cells_chunks(c, cells, nullptr, nb, mode, st, bstatus, coefficient_step(c, blobs_dev, mode, st), nb);
+}
+
+hipError_t launch_blob_fold_status(int32_t *words, const int32_t *bstatus, size_t nb, int mode, int bad_code, hipStream_t st) {
+    if (!mode_rules(mode).evaluation_form) return hipSuccess;   // reference mode reduces: no blob is rejected
+    ProfScope p("k_blob_fold_status", st);
+    hipLaunchKernelGGL(k_blob_fold_status, dim3(grid_for(nb * kCellsPerBlob)), dim3(256), 0, st, words, bstatus, (uint32_t)nb, bad_code);
+    return hipPeekAtLastError();   // (left standing for the pipeline's own hipGetLastError)
+}
+
+namespace {
 
 // the n commitments on the host: the caller's array, or (device form) brought down on the call's stream
 C_KZG_RET host_commitments(const uint8_t *&comms, std::vector<uint8_t> &down, const void *given, size_t nb, const KZGSettings *s,

@@ -418,4 +418,20 @@ struct GroupSlice;
 void launch_cell_group_slice_table(const uint32_t *item_off, const uint32_t *row_base, const uint32_t *gflag, GroupSlice *slices,
                                    uint32_t *slice_off, size_t g, size_t max_slices, hipStream_t st);
 
+// ---- the same for the commitments of whole blobs (cell_blobs_group.hip, the steps in cell_blobs_group.h): what
+// plan_blobs (cell_blobs_plan.h) makes on the host. nb <= kBlobGroupCap blobs in g groups; item_off: the groups' g + 1 offsets in
+// ITEMS (128 per blob) in device memory, or nullptr for a batch (g == 1, one group of all blobs). One launch of one workgroup for
+// the grouping, one grid-stride launch for the lists; nothing is read back. Each returns its launch's error
+struct BlobGroupOut;
+hipError_t launch_cell_blobs_group(const uint8_t *comms48, const uint32_t *item_off, size_t nb, size_t g, uint64_t seed, uint32_t hash_mask,
+                                   const BlobGroupOut &o, hipStream_t st);
+// the lists of the 128 nb expanded items from o's tables: idx, rows (group-local), perm_row, perm_col, item_group (a grouped call's)
+// per item; col_off 128 g + 1; row_off M + 1 and first_item M, in items; and, in o.distinct, the infinity encodings behind the M
+// distinct commitments up to 128 nb entries
+struct BlobItemsOut {
+    uint64_t *idx;
+    uint32_t *rows, *perm_row, *perm_col, *item_group, *col_off, *row_off, *first_item;
+};
+hipError_t launch_cell_blobs_items(const BlobGroupOut &o, const uint32_t *item_off, size_t nb, size_t g, const BlobItemsOut &x, hipStream_t st);
+
 }  // namespace lwk
