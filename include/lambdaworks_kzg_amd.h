@@ -551,6 +551,28 @@ C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch(Cell *cells, KZGProof *proofs
 C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_batch_device(void *cells_dev, void *proofs48_dev, const void *blobs_dev, size_t n,
                                                           const KZGSettings *s, void *stream, int32_t *status_dev);
 
+/* Chosen columns only: the cells and proofs of columns[0 .. num_columns) of n blobs, blob-major and compact --
+ * cells[b * num_columns + i] and proofs[b * num_columns + i] are byte for byte cells[128 b + columns[i]] and proofs[128 b + columns[i]] of
+ * lwkzg_compute_cells_and_kzg_proofs_batch on the same blobs and settings, in every mode, on every MSM engine and on either cell proof
+ * engine; with all 128 columns the call is that call. columns is a HOST array: num_columns in 1 .. 128, every index below 128, strictly
+ * ascending (the rule cell_indices follows). Either output may be NULL; with proofs == NULL no MSM runs. On the MSM engine a proof is one
+ * 4096-term MSM, so the call costs about num_columns / 128 of the full one; with the FK20 engine on, that engine serves the call when
+ * n * num_columns >= 128 * min_blobs (as many MSMs as a full call at the threshold brings) and the MSM engine below.
+ * C_KZG_BADARGS in both modes, decided before any device work: s NULL; with n > 0 blobs NULL, both outputs NULL, columns NULL, num_columns 0
+ * or above 128, an index of 128 or more, a list not strictly ascending. A c-kzg-mode blob with an element >= r fails the call with the
+ * mode's code (first_bad, if given, gets its index) and nothing is written, as in the full call. n == 0: C_KZG_OK, nothing written,
+ * whatever the other pointers are. Synchronous. */
+C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_columns(Cell *cells, KZGProof *proofs, const Blob *blobs, size_t n, const uint64_t *columns,
+                                                     size_t num_columns, const KZGSettings *s, size_t *first_bad);
+/* the same on device pointers (cells_dev: n x num_columns x 2048 bytes, proofs48_dev: n x num_columns x 48 bytes, either NULL),
+ * asynchronous on `stream` (NULL = the context's own); columns stays a HOST array, read before the call returns and handed to the kernels
+ * by value: calls with different lists may follow each other on one stream with no synchronisation between them. status_dev (optional):
+ * one word per blob, 0 or the mode's rejection code; a good blob's outputs are correct whatever its neighbours' status. A call of
+ * 1024 / num_columns blobs or more fills whole MSM launch sets (lwkzg_reserve: 1024 covers every column call). */
+C_KZG_RET lwkzg_compute_cells_and_kzg_proofs_columns_device(void *cells_dev, void *proofs48_dev, const void *blobs_dev, size_t n,
+                                                            const uint64_t *columns /* HOST */, size_t num_columns, const KZGSettings *s,
+                                                            void *stream, int32_t *status_dev);
+
 /* EIP-7594 recover_cells_and_kzg_proofs: all 128 cells and all 128 proofs of a blob from num_cells of its cells, 64 <= num_cells <= 128.
  * cells[i] is cell cell_indices[i], in the settings' mode's byte order; the indices are below 128 and strictly ascending (c-kzg-4844 2.x's
  * rule and argument order). With p the polynomial of degree < 4096 that takes the given values on the given cells' cosets -- unique if it
@@ -575,6 +597,25 @@ C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_batch(Cell *recovered_cells, KZGPro
 C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_batch_device(void *recovered_cells_dev, void *recovered_proofs48_dev,
                                                           const uint64_t *cell_indices, const void *cells_dev, size_t num_cells, size_t n,
                                                           const KZGSettings *s, void *stream, int32_t *status_dev);
+
+/* Chosen columns only: n blobs through ONE index set, as lwkzg_recover_cells_and_kzg_proofs_batch takes them, and
+ * of the result the cells and proofs of columns[0 .. num_columns) alone, blob-major and compact: cells_out[b * num_columns + i] and
+ * proofs_out[b * num_columns + i] are byte for byte entries 128 b + columns[i] of that call's outputs -- what a node that has just
+ * reconstructed a block needs to re-seed the columns it lacks (pass the complement of cell_indices). columns as in
+ * lwkzg_compute_cells_and_kzg_proofs_columns; it may name given columns too (their cells come back as given). Argument errors
+ * (C_KZG_BADARGS in both modes, before any device work) are those of the full call plus those of the list; a bad blob -- an element not
+ * below r, inconsistent cells: the check does not depend on columns -- fails the call with the mode's code (first_bad, if given, gets its
+ * index) and nothing is written. n == 0: C_KZG_OK, nothing written. Either output may be NULL (proofs_out NULL: no MSM runs).
+ * Synchronous. The _mixed forms have no column variant. */
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_columns(Cell *cells_out, KZGProof *proofs_out, const uint64_t *cell_indices, const Cell *cells,
+                                                     size_t num_cells, size_t n, const uint64_t *columns, size_t num_columns,
+                                                     const KZGSettings *s, size_t *first_bad);
+/* the same on device pointers (16-byte aligned; outputs n x num_columns x 2048 and n x num_columns x 48 bytes), cell_indices and columns
+ * HOST arrays read before the call returns; asynchronous on `stream`; status_dev as in lwkzg_recover_cells_and_kzg_proofs_batch_device. */
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_columns_device(void *cells_out_dev, void *proofs48_out_dev, const uint64_t *cell_indices,
+                                                            const void *cells_dev, size_t num_cells, size_t n,
+                                                            const uint64_t *columns /* HOST */, size_t num_columns, const KZGSettings *s,
+                                                            void *stream, int32_t *status_dev);
 
 /* n blobs, each seen through an index set of its OWN (the rows of several blocks, each block through the columns that reached the node: a
  * node catching up, a backfill, a supernode reconstructing for its peers). num_cells[b] is blob b's count, 64 .. 128; cell_indices

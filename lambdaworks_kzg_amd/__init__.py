@@ -25,6 +25,8 @@ from .capi import (  # noqa: F401
     GroupedCellAnswers, cell_group_segmented_device, cell_verifier_groups_host_steps, blob_group_device,
     recover_cells_and_kzg_proofs, recover_cells_and_kzg_proofs_batch, recover_cells_and_kzg_proofs_batch_device,
     recover_cells_and_kzg_proofs_mixed, recover_cells_and_kzg_proofs_mixed_device,
+    compute_cells_and_kzg_proofs_columns, compute_cells_and_kzg_proofs_columns_device,
+    recover_cells_and_kzg_proofs_columns, recover_cells_and_kzg_proofs_columns_device,
     CELL_PROOFS_FK20, CELL_PROOFS_MSM, fk20_chunk_blobs,
 )
 

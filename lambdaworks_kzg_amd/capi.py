@@ -82,6 +82,8 @@ EXPORTED_SYMBOLS = [
     "lwkzg_verify_blob_kzg_proof_each", "lwkzg_verify_blob_kzg_proof_each_device", "lwkzg_verify_kzg_proof_each",
     "lwkzg_pairing_line_table",
     "lwkzg_compute_cells_and_kzg_proofs", "lwkzg_compute_cells_and_kzg_proofs_batch", "lwkzg_compute_cells_and_kzg_proofs_batch_device",
+    "lwkzg_compute_cells_and_kzg_proofs_columns", "lwkzg_compute_cells_and_kzg_proofs_columns_device",
+    "lwkzg_recover_cells_and_kzg_proofs_columns", "lwkzg_recover_cells_and_kzg_proofs_columns_device",
     "lwkzg_verify_cell_kzg_proof_batch", "lwkzg_verify_cell_kzg_proof_batch_device", "lwkzg_cell_verify_partials",
     "lwkzg_cell_batch_challenge_host",
     "lwkzg_verify_cell_kzg_proof_each", "lwkzg_verify_cell_kzg_proof_each_device", "lwkzg_cell_verify_each_points",
@@ -174,6 +176,10 @@ def lib():
     l.lwkzg_recover_cells_and_kzg_proofs.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, ps]
     l.lwkzg_recover_cells_and_kzg_proofs_batch.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, sz, ps, C.POINTER(sz)]
     l.lwkzg_recover_cells_and_kzg_proofs_batch_device.argtypes = [vp, vp, pu64, vp, sz, sz, ps, vp, vp]
+    l.lwkzg_compute_cells_and_kzg_proofs_columns.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, sz, pu64, sz, ps, C.POINTER(sz)]
+    l.lwkzg_compute_cells_and_kzg_proofs_columns_device.argtypes = [vp, vp, vp, sz, pu64, sz, ps, vp, vp]
+    l.lwkzg_recover_cells_and_kzg_proofs_columns.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, sz, sz, pu64, sz, ps, C.POINTER(sz)]
+    l.lwkzg_recover_cells_and_kzg_proofs_columns_device.argtypes = [vp, vp, pu64, vp, sz, sz, pu64, sz, ps, vp, vp]
     l.lwkzg_recover_cells_and_kzg_proofs_mixed.argtypes = [C.c_char_p, C.c_char_p, pu64, C.c_char_p, C.POINTER(sz), sz, ps, C.POINTER(sz)]
     l.lwkzg_recover_cells_and_kzg_proofs_mixed_device.argtypes = [vp, vp, pu64, vp, C.POINTER(sz), sz, ps, vp, vp]
     l.lwkzg_set_cell_proof_engine.argtypes = [ps, ci, ci, sz]
@@ -850,6 +856,65 @@ def recover_cells_and_kzg_proofs_batch_device(cells_out_ptr, proofs_ptr, cell_in
     idx = (C.c_uint64 * max(num, 1))(*cell_indices)
     _check("lwkzg_recover_cells_and_kzg_proofs_batch_device",
            lib().lwkzg_recover_cells_and_kzg_proofs_batch_device(cells_out_ptr, proofs_ptr, idx, cells_ptr, num, n, ts.ref(), stream, status_ptr))
+
+
+def _columns_split(cells_raw, proofs_raw, n, c):
+    """n x c cells / proofs as a column call returns them -> [(cells, proofs)] per blob, each a list of c bytes objects (or None)"""
+    out = []
+    for b in range(n):
+        cs = None if cells_raw is None else [cells_raw[(c * b + i) * BYTES_PER_CELL:(c * b + i + 1) * BYTES_PER_CELL] for i in range(c)]
+        ps = None if proofs_raw is None else [proofs_raw[(c * b + i) * 48:(c * b + i + 1) * 48] for i in range(c)]
+        out.append((cs, ps))
+    return out
+
+
+def compute_cells_and_kzg_proofs_columns(blobs, columns, ts, cells=True, proofs=True):
+    """the cells and proofs of the chosen columns alone (lwkzg_compute_cells_and_kzg_proofs_columns; columns: 1 .. 128 strictly ascending
+    indices below 128) of n concatenated blobs: a list of (cells, proofs) per blob, each len(columns) long and equal to entries
+    columns[i] of what compute_cells_and_kzg_proofs_batch returns"""
+    n, c = len(blobs) // BYTES_PER_BLOB, len(columns)
+    assert len(blobs) == n * BYTES_PER_BLOB
+    cb = C.create_string_buffer(max(n * c, 1) * BYTES_PER_CELL) if cells else None
+    pb = C.create_string_buffer(max(n * c, 1) * 48) if proofs else None
+    bad = C.c_size_t(0)
+    _check("lwkzg_compute_cells_and_kzg_proofs_columns",
+           lib().lwkzg_compute_cells_and_kzg_proofs_columns(cb, pb, blobs, n, (C.c_uint64 * max(c, 1))(*columns), c, ts.ref(), C.byref(bad)))
+    return _columns_split(cb.raw if cells else None, pb.raw if proofs else None, n, c)
+
+
+def compute_cells_and_kzg_proofs_columns_device(cells_ptr, proofs_ptr, blobs_ptr, n, columns, ts, stream=None, status_ptr=None):
+    """cells (n x len(columns) x 2048 bytes) and proofs (n x len(columns) x 48 bytes) of the chosen columns of n device-resident blobs
+    (columns a host list), asynchronous on `stream`; either output pointer may be None"""
+    c = len(columns)
+    _check("lwkzg_compute_cells_and_kzg_proofs_columns_device",
+           lib().lwkzg_compute_cells_and_kzg_proofs_columns_device(cells_ptr, proofs_ptr, blobs_ptr, n, (C.c_uint64 * max(c, 1))(*columns), c,
+                                                                   ts.ref(), stream, status_ptr))
+
+
+def recover_cells_and_kzg_proofs_columns(cell_indices, cells, n, columns, ts, cells_out=True, proofs=True):
+    """the chosen columns alone of n blobs recovered through one index set (lwkzg_recover_cells_and_kzg_proofs_columns): a list of
+    (cells, proofs) per blob, each len(columns) long and equal to entries columns[i] of what recover_cells_and_kzg_proofs_batch returns"""
+    idx, ce, num = _recover_args(cell_indices, cells, n)
+    c = len(columns)
+    cb = C.create_string_buffer(max(n * c, 1) * BYTES_PER_CELL) if cells_out else None
+    pb = C.create_string_buffer(max(n * c, 1) * 48) if proofs else None
+    bad = C.c_size_t(0)
+    _check("lwkzg_recover_cells_and_kzg_proofs_columns",
+           lib().lwkzg_recover_cells_and_kzg_proofs_columns(cb, pb, idx, ce, num, n, (C.c_uint64 * max(c, 1))(*columns), c, ts.ref(),
+                                                            C.byref(bad)))
+    return _columns_split(cb.raw if cells_out else None, pb.raw if proofs else None, n, c)
+
+
+def recover_cells_and_kzg_proofs_columns_device(cells_out_ptr, proofs_ptr, cell_indices, cells_ptr, n, columns, ts, stream=None,
+                                                status_ptr=None):
+    """cells (n x len(columns) x 2048 bytes) and proofs (n x len(columns) x 48 bytes) of the chosen columns of n blobs from their
+    device-resident cells (n x len(cell_indices) x 2048 bytes, blob-major; both lists stay on the host), asynchronous on `stream`;
+    either output pointer may be None"""
+    num, c = len(cell_indices), len(columns)
+    _check("lwkzg_recover_cells_and_kzg_proofs_columns_device",
+           lib().lwkzg_recover_cells_and_kzg_proofs_columns_device(cells_out_ptr, proofs_ptr, (C.c_uint64 * max(num, 1))(*cell_indices),
+                                                                   cells_ptr, num, n, (C.c_uint64 * max(c, 1))(*columns), c, ts.ref(),
+                                                                   stream, status_ptr))
 
 
 def _mixed_lists(index_lists):

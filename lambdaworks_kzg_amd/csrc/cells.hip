@@ -7,6 +7,8 @@
 //    and the exit from Montgomery form and the serialisation in the mode's byte order.
 //  * Quotients: q_k = p div (X^64 - c_k), c_k = w128^bitrev7(k), by the binomial recurrence q[j] = p[j + 64] + c_k q[j + 64] from
 //    the top down, written as canonical limbs straight into the MSM's scalar slots.
+//  * A call for c of the 128 columns takes the list by value in the extension's exit and in the quotients:
+//    k_cells_extend_out_columns and k_cells_quotients_columns, each one body with its twin that knows no list.
 #include "kernels.h"
 
 namespace lwk {
@@ -54,11 +56,9 @@ __global__ __launch_bounds__(256) void k_cells_extend_in(const uint4 *__restrict
 
 // Exit: lane g is element e of blob b's 8192 (cell e / 64, slot e mod 64); it reads evaluation bitrev12(e mod 4096) of transform
 // 2 b + (e >= 4096) and writes its 32 bytes, little-endian (le) or big-endian. Reads gather, writes are contiguous.
-__global__ __launch_bounds__(256) void k_cells_extend_out(const Fr *__restrict__ evals, uint4 *__restrict__ cells, int le, size_t n) {
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    const size_t b = g / (2 * kBlobElems);
-    const uint32_t e = (uint32_t)(g % (2 * kBlobElems)), h = e / kBlobElems, j = __brev(e % kBlobElems) >> 20;
+// (the body: element e of blob b to output element g; both exit kernels are this)
+__device__ __forceinline__ void cells_extend_store(const Fr *__restrict__ evals, uint4 *__restrict__ cells, int le, size_t b, uint32_t e, size_t g) {
+    const uint32_t h = e / kBlobElems, j = __brev(e % kBlobElems) >> 20;
     uint32_t s[8];
     fe_to_raw<FrParams>(s, evals[(2 * b + h) * kBlobElems + j]);
     if (le) {
@@ -69,8 +69,25 @@ __global__ __launch_bounds__(256) void k_cells_extend_out(const Fr *__restrict__
     }
 }
 
+__global__ __launch_bounds__(256) void k_cells_extend_out(const Fr *__restrict__ evals, uint4 *__restrict__ cells, int le, size_t n) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    cells_extend_store(evals, cells, le, g / (2 * kBlobElems), (uint32_t)(g % (2 * kBlobElems)), g);
+}
+
+// The exit of a call that wants c columns: lane g is slot t of the blob's i-th wanted cell, output element
+// g = 64 (c b + i) + t, and reads what the exit above reads for element 64 cols.k[i] + t. The list comes by value: no buffer to keep
+__global__ __launch_bounds__(256) void k_cells_extend_out_columns(const Fr *__restrict__ evals, uint4 *__restrict__ cells, int le,
+                                                                  CellColumns cols, uint32_t c, size_t n) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const size_t cell = g / kCellElems;
+    const uint32_t i = (uint32_t)(cell % c), t = (uint32_t)(g % kCellElems);
+    cells_extend_store(evals, cells, le, cell / c, (uint32_t)kCellElems * cols.k[i] + t, g);
+}
+
 void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr28 *tw28_fwd, Fr *scratch, Fr *scratch2, uint8_t *cells,
-                         int le, size_t n_blobs, hipStream_t st) {
+                         int le, size_t n_blobs, hipStream_t st, const CellColumns *cols, uint32_t c) {
     const size_t n = 2 * n_blobs * kBlobElems;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     {
@@ -78,6 +95,13 @@ void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr2
         hipLaunchKernelGGL(k_cells_extend_in, dim3(blocks), dim3(256), 0, st, (const uint4 *)coeffs_raw, tw_fwd, scratch, n);
     }
     launch_ntt4096(scratch, scratch2, tw28_fwd, 0, 2 * n_blobs, st);
+    if (cols) {   // the transforms stay whole; only the wanted cells leave
+        ProfScope p("k_cells_extend_out_columns", st);
+        const size_t n_out = n_blobs * c * kCellElems;
+        hipLaunchKernelGGL(k_cells_extend_out_columns, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, (const Fr *)scratch2,
+                           (uint4 *)cells, le, *cols, c, n_out);
+        return;
+    }
     {
         ProfScope p("k_cells_extend_out", st);
         hipLaunchKernelGGL(k_cells_extend_out, dim3(blocks), dim3(256), 0, st, (const Fr *)scratch2, (uint4 *)cells, le, n);
@@ -88,16 +112,11 @@ void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr2
 // quotient coefficients (2 KiB each) per step. q_k has degree < 4032; slots 4032 .. 4095 of its scalar set are zero. Coefficients
 // and quotient are raw canonical integers: the Montgomery product of c_k R (the twiddle w^(32 bitrev7(k)), negated from the
 // table's upper half: w^2048 = -1) with a raw q is c_k q, raw again. 62 products per lane.
-__global__ __launch_bounds__(256) void k_cells_quotients(const uint4 *__restrict__ coeffs_raw, const Fr *__restrict__ tw_fwd,
-                                                         uint4 *__restrict__ quot_raw, size_t n_cells) {
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t cell = g / kCellElems;
-    if (cell >= n_cells) return;
-    const uint32_t t = (uint32_t)(g % kCellElems), k = (uint32_t)(cell % kCellsPerBlob);
+// (the body: lane t of the wave of cell k; p the blob's coefficients, q the scalar set. Both quotient kernels are this)
+__device__ __forceinline__ void cells_quotient(const uint4 *__restrict__ p, const Fr *__restrict__ tw_fwd, uint4 *__restrict__ q, uint32_t k,
+                                               uint32_t t) {
     const uint32_t e = 32 * (__brev(k) >> 25);
     const Fr ck = e < kBlobElems / 2 ? tw_fwd[e] : neg(tw_fwd[e - kBlobElems / 2]);
-    const uint4 *p = coeffs_raw + (cell / kCellsPerBlob) * kBlobElems * 2;
-    uint4 *q = quot_raw + cell * kBlobElems * 2;
     constexpr uint32_t kTop = kBlobElems - kCellElems;   // 4032
     const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     store_raw(q, kTop + t, zero);
@@ -109,11 +128,38 @@ __global__ __launch_bounds__(256) void k_cells_quotients(const uint4 *__restrict
     }
 }
 
+__global__ __launch_bounds__(256) void k_cells_quotients(const uint4 *__restrict__ coeffs_raw, const Fr *__restrict__ tw_fwd,
+                                                         uint4 *__restrict__ quot_raw, size_t n_cells) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t cell = g / kCellElems;
+    if (cell >= n_cells) return;
+    cells_quotient(coeffs_raw + (cell / kCellsPerBlob) * kBlobElems * 2, tw_fwd, quot_raw + cell * kBlobElems * 2,
+                   (uint32_t)(cell % kCellsPerBlob), (uint32_t)(g % kCellElems));
+}
+
+// The quotients of a call that wants c columns: one wave per (blob, i < c), k = cols.k[i], into scalar set c blob + i
+__global__ __launch_bounds__(256) void k_cells_quotients_columns(const uint4 *__restrict__ coeffs_raw, const Fr *__restrict__ tw_fwd,
+                                                                 uint4 *__restrict__ quot_raw, CellColumns cols, uint32_t c, size_t n_sets) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t set = g / kCellElems;
+    if (set >= n_sets) return;
+    cells_quotient(coeffs_raw + (set / c) * kBlobElems * 2, tw_fwd, quot_raw + set * kBlobElems * 2, cols.k[set % c],
+                   (uint32_t)(g % kCellElems));
+}
+
 void launch_cells_quotients(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, size_t n_cells, hipStream_t st) {
     ProfScope p("k_cells_quotients", st);
     const size_t n = n_cells * kCellElems;
     hipLaunchKernelGGL(k_cells_quotients, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)coeffs_raw, tw_fwd,
                        (uint4 *)quot_raw, n_cells);
+}
+
+void launch_cells_quotients_columns(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, const CellColumns &cols, uint32_t c,
+                                    size_t n_blobs, hipStream_t st) {
+    ProfScope p("k_cells_quotients_columns", st);
+    const size_t n_sets = n_blobs * c, n = n_sets * kCellElems;
+    hipLaunchKernelGGL(k_cells_quotients_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)coeffs_raw, tw_fwd,
+                       (uint4 *)quot_raw, cols, c, n_sets);
 }
 
 }  // namespace lwk

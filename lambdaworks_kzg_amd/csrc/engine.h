@@ -410,8 +410,11 @@ bool coefficients_to_msm_form(Ctx *c, int mode, size_t n, hipStream_t st, size_t
 // the cells pipeline behind the parse (cells_api.hip): the canonical coefficients of m blobs in ws.scalars (slots 0 ..) -> their 128 cells
 // each (cells: m x 256 KiB, or nullptr) and 128 proofs each (proofs48: m x 128 x 48 bytes, or nullptr: no MSM runs). m is at most one
 // chunk (8 blobs with proofs, 512 without) and the caller has reserved the workspace for it (128 m slots with proofs, 2 m without).
-// fk20: the proofs come from the FK20 engine instead (a chunk of up to kFk20ChunkBlobs blobs, 2 m slots)
-void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st, bool fk20 = false);
+// fk20: the proofs come from the FK20 engine instead (a chunk of up to kFk20ChunkBlobs blobs, 2 m slots).
+// cols (with ncols, its count): only those columns, compact -- m x ncols cells and proofs, m ncols scalar sets (a chunk as
+// cells_columns_plan.h cuts it); nullptr: all 128, through the kernels that take no list
+void cells_from_coefficients(Ctx *c, uint8_t *cells, uint8_t *proofs48, size_t m, int mode, hipStream_t st, bool fk20 = false,
+                             const CellColumns *cols = nullptr, uint32_t ncols = kCellsPerBlob);
 
 // device-resident pipelines; all pointers device, async on st
 C_KZG_RET commit_batch_device(Ctx *c, uint8_t *out48, const uint8_t *blobs, size_t n, int mode, hipStream_t st,

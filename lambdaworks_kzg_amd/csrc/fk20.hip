@@ -208,4 +208,25 @@ void launch_fk20_transforms(G1Xyzz29 *pts, const uint8_t *roots, G1Xyzz29 *h_out
     hipLaunchKernelGGL(k_fk20_transforms, dim3((unsigned)n_blobs), dim3(kFk20Points), 0, st, pts, roots, fk20_beta29(), h_out);
 }
 
+// The finalize of a column call on this engine: msm.hip's k_finalize_compress with an index map in front, one
+// lane per wanted proof. The points of the unwanted columns stay where the transforms left them
+__global__ __launch_bounds__(64) void k_fk20_columns_compress(const G1Xyzz29 *__restrict__ pts, CellColumns cols, uint32_t c,
+                                                              uint8_t *__restrict__ out48, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    __builtin_amdgcn_s_setprio(2);  // one inversion per lane, a pure latency chain at the end of the call
+    uint8_t b[48];
+    g1_compress(b, pts[(i / c) * kFk20Points + cols.k[i % c]]);
+    uint32_t *o = (uint32_t *)(out48 + 48 * i);
+#pragma unroll
+    for (int k = 0; k < 12; k++)
+        o[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) | ((uint32_t)b[4 * k + 3] << 24);
+}
+
+void launch_fk20_columns_compress(const G1Xyzz29 *pts, const CellColumns &cols, uint32_t c, uint8_t *out48, size_t n_blobs, hipStream_t st) {
+    ProfScope p("k_fk20_columns_compress", st);
+    const size_t n = n_blobs * c;
+    hipLaunchKernelGGL(k_fk20_columns_compress, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pts, cols, c, out48, n);
+}
+
 }  // namespace lwk

@@ -253,13 +253,22 @@ void challenge_midstates_host(uint32_t *mid, const uint8_t *blobs, size_t n, boo
 // ---- EIP-7594 cells (cells.hip)
 constexpr int kCellElems = 64;        // field elements per cell
 constexpr int kCellsPerBlob = 128;    // cells (and cell proofs) per blob: 8192 extended evaluations
+// the wanted columns of a call for c of the 128: k[i], i < c, strictly ascending. By value to the kernels, as the
+// recovery's shared set travels: no device buffer, no lifetime, no synchronisation between calls that follow each other on a stream
+struct CellColumns {
+    uint8_t k[kCellsPerBlob];
+};
 // canonical coefficients of n_blobs blobs -> their 128 cells each (n_blobs x 256 KiB), 32-byte elements little-endian (le) or
-// big-endian; scratch, scratch2: 2 n_blobs x 4096 Fr each
+// big-endian; scratch, scratch2: 2 n_blobs x 4096 Fr each. cols (with c, its count): only cells cols->k[0 .. c) of every blob leave,
+// compact (n_blobs x c x 2 KiB), through the exit kernel that takes the list; the entry and the two transforms are the same
 void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr28 *tw28_fwd, Fr *scratch, Fr *scratch2, uint8_t *cells,
-                         int le, size_t n_blobs, hipStream_t st);
+                         int le, size_t n_blobs, hipStream_t st, const CellColumns *cols = nullptr, uint32_t c = kCellsPerBlob);
 // canonical coefficients of n_cells / 128 blobs -> the monomial quotient q_k = p div (X^64 - c_k) of every cell, canonical limbs in
 // scalar set (blob * 128 + k), zero-padded to 4096
 void launch_cells_quotients(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, size_t n_cells, hipStream_t st);
+// the same for cells cols.k[0 .. c) of n_blobs blobs alone: q of cell cols.k[i] in scalar set (blob * c + i)
+void launch_cells_quotients_columns(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, const CellColumns &cols, uint32_t c,
+                                    size_t n_blobs, hipStream_t st);
 
 // ---- the FK20 cell proof engine (fk20.hip, pieces in fk20.cuh)
 // rows first .. first + n_rows of the 8192 scalar rows whose commitments over the monomial setup are the transformed bases (row 128 i + m:
@@ -274,6 +283,8 @@ void launch_fk20_msm(const G1Affine29 *table, int bits, const uint32_t *scalars,
 // pts[128 blob ..]: E in bit-reversed positions -> the blob's 128 proof points in proof order; roots: the recoded roots (fk20.cuh);
 // h_out (optional): h_0 .. h_63 of every blob
 void launch_fk20_transforms(G1Xyzz29 *pts, const uint8_t *roots, G1Xyzz29 *h_out, size_t n_blobs, hipStream_t st);
+// the finalize of a call that wants c columns: point 128 blob + cols.k[i] of pts, compressed, at out48[48 (c blob + i)]
+void launch_fk20_columns_compress(const G1Xyzz29 *pts, const CellColumns &cols, uint32_t c, uint8_t *out48, size_t n_blobs, hipStream_t st);
 
 // ---- EIP-7594 recovery (recover.hip)
 // the index set of a recovery call, passed to its kernels by value: RecoverSet (recover_sets.h)

@@ -10,6 +10,8 @@
 //   per chunk     the status words cleared; recover.hip: the given cells -> the blob's 4096 coefficients in ws.scalars through
 //                 ws.scalars2 (256 KiB per blob); cells_from_coefficients (cells_api.hip): extension, quotients, MSM
 // Chunks as cells_api.hip has them: 8 blobs with proofs (one launch set of 1024 MSMs), 512 without.
+// The _columns forms (shared set) hand a list of wanted columns to what is behind the coefficients; the setup,
+// the coefficient step and the consistency check do not know of it.
 // The two kinds of call differ in how the sets reach the kernels, in two places (recover_setup and the coefficient step of
 // recover_device). A shared-set call hands its kernels the set by value and keeps its table in the context's recover_tab: a chunk is one
 // launch of each kernel. A mixed call keeps its sets' tables, lists and masks in a grow-only device buffer of the context and hands a
@@ -100,9 +102,11 @@ C_KZG_RET recover_setup(Ctx *c, const Lists &l, const RecoverSets &sets, Recover
 }
 
 // the device pipeline of blobs b0 .. b0 + n of a call on st (caller holds the context's lock and the workspace; recover_setup has run);
-// cells_in: the cells of blob b0 on; status: n words, 0 or the mode's rejection code
+// cells_in: the cells of blob b0 on; status: n words, 0 or the mode's rejection code; use: the wanted columns, which reach only what
+// is behind the coefficients
 C_KZG_RET recover_device(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, const Lists &l, const RecoverSets &sets, const RecoverSetsDev &dev,
-                         const uint8_t *cells_in, size_t b0, size_t n, int mode, hipStream_t st, int32_t *status, size_t n_call) {
+                         const uint8_t *cells_in, size_t b0, size_t n, int mode, hipStream_t st, int32_t *status, size_t n_call,
+                         const ColumnsUse &use) {
     const int le = mode_rules(mode).le(), bad = (int)bad_input(mode);
     return cells_chunks(c, cells_out, proofs48, n, mode, st, status, [&](size_t off, size_t m, int32_t *stt) {
         if (!l.mixed) {   // the whole chunk in one launch of each kernel
@@ -123,15 +127,33 @@ C_KZG_RET recover_device(Ctx *c, uint8_t *cells_out, uint8_t *proofs48, const Li
                                               (Fr *)c->ws.scalars2 + g0 * (size_t)kCellElems * kCellsPerBlob,
                                               c->ws.scalars + g0 * (size_t)kBlobElems * 8, stt + g0, bad, le, gm, st);
         }
-    }, n_call);
+    }, n_call, use);
 }
 
-// host pointers: slices of 64 blobs up and back (cells_api.hip), the call's sets made once, in front of its first slice
-C_KZG_RET recover_host(Cell *cells_out, KZGProof *proofs, const Lists &l, const Cell *cells, size_t n, const KZGSettings *s, size_t *first_bad) {
+// the wanted columns of a call as its entry point got them: a list (the _columns forms) or none (all 128)
+struct Wanted {
+    bool listed = false;
+    const uint64_t *columns = nullptr;
+    size_t num_columns = 0;
+};
+
+// use for the call: the recovery's scratch is two workspace slots per blob whatever is wanted; a list is checked behind the full call's
+// own arguments (C_KZG_BADARGS)
+bool wanted_columns(ColumnsUse &use, const Wanted &w) {
+    use.pair_scratch = true;
+    return !w.listed || columns_from_list(use, w.columns, w.num_columns, "recover_cells_and_kzg_proofs_columns");
+}
+
+// host pointers: slices of 64 blobs (a column call: the plan's slice) up and back (cells_api.hip), the call's sets made once, in front of
+// its first slice
+C_KZG_RET recover_host(Cell *cells_out, KZGProof *proofs, const Lists &l, const Cell *cells, size_t n, const KZGSettings *s, size_t *first_bad,
+                       const Wanted &wanted = Wanted()) {
     if (!s) return C_KZG_BADARGS;
     if (n == 0) return C_KZG_OK;
     RecoverSets sets;
     if (!check_arguments(sets, l, cells_out, proofs, cells, n, first_bad)) return C_KZG_BADARGS;
+    ColumnsUse use;
+    if (!wanted_columns(use, wanted)) return C_KZG_BADARGS;
     const int mode = mode_of(s);
     Ctx *c = ctx_of(s);
     if (!c) return C_KZG_ERROR;
@@ -148,17 +170,19 @@ C_KZG_RET recover_host(Cell *cells_out, KZGProof *proofs, const Lists &l, const 
                 C_KZG_RET rc = recover_setup(c, l, sets, dev, st);
                 if (rc != C_KZG_OK) return rc;
             }
-            return recover_device(c, d_cells, d_proofs, l, sets, dev, d_in, off, m, mode, st, d_status, n);
-        });
+            return recover_device(c, d_cells, d_proofs, l, sets, dev, d_in, off, m, mode, st, d_status, n, use);
+        }, wanted.listed ? &use : nullptr);
 }
 
 // device pointers, on the caller's stream or the context's
 C_KZG_RET recover_on_device(void *cells_out, void *proofs48, const Lists &l, const void *cells, size_t n, const KZGSettings *s, void *stream,
-                            int32_t *status) {
+                            int32_t *status, const Wanted &wanted = Wanted()) {
     if (!s) return C_KZG_BADARGS;
     if (n == 0) return C_KZG_OK;
     RecoverSets sets;
     if (!check_arguments(sets, l, cells_out, proofs48, cells, n, nullptr)) return C_KZG_BADARGS;
+    ColumnsUse use;
+    if (!wanted_columns(use, wanted)) return C_KZG_BADARGS;
     const int mode = mode_of(s);
     Ctx *c = ctx_of(s);
     if (!c) return C_KZG_ERROR;
@@ -170,7 +194,7 @@ C_KZG_RET recover_on_device(void *cells_out, void *proofs48, const Lists &l, con
     RecoverSetsDev dev{};
     C_KZG_RET rc = recover_setup(c, l, sets, dev, st);
     if (rc != C_KZG_OK) return rc;
-    return recover_device(c, (uint8_t *)cells_out, (uint8_t *)proofs48, l, sets, dev, (const uint8_t *)cells, 0, n, mode, st, status, n);
+    return recover_device(c, (uint8_t *)cells_out, (uint8_t *)proofs48, l, sets, dev, (const uint8_t *)cells, 0, n, mode, st, status, n, use);
 }
 
 }  // namespace
@@ -201,6 +225,24 @@ C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_batch_device(void *recovered_cells_
     return guarded("lwkzg_recover_cells_and_kzg_proofs_batch_device", [&] {
         return recover_on_device(recovered_cells_dev, recovered_proofs48_dev, Lists{false, cell_indices, &num_cells}, cells_dev, n, s, stream,
                                  status_dev);
+    });
+}
+
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_columns(Cell *cells_out, KZGProof *proofs_out, const uint64_t *cell_indices, const Cell *cells,
+                                                     size_t num_cells, size_t n, const uint64_t *columns, size_t num_columns,
+                                                     const KZGSettings *s, size_t *first_bad) {
+    return guarded("lwkzg_recover_cells_and_kzg_proofs_columns", [&] {
+        return recover_host(cells_out, proofs_out, Lists{false, cell_indices, &num_cells}, cells, n, s, first_bad,
+                            Wanted{true, columns, num_columns});
+    });
+}
+
+C_KZG_RET lwkzg_recover_cells_and_kzg_proofs_columns_device(void *cells_out_dev, void *proofs48_out_dev, const uint64_t *cell_indices,
+                                                            const void *cells_dev, size_t num_cells, size_t n, const uint64_t *columns,
+                                                            size_t num_columns, const KZGSettings *s, void *stream, int32_t *status_dev) {
+    return guarded("lwkzg_recover_cells_and_kzg_proofs_columns_device", [&] {
+        return recover_on_device(cells_out_dev, proofs48_out_dev, Lists{false, cell_indices, &num_cells}, cells_dev, n, s, stream, status_dev,
+                                 Wanted{true, columns, num_columns});
     });
 }
 
