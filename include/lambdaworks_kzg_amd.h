@@ -1042,7 +1042,8 @@ C_KZG_RET lwkzg_challenge_digests_host_mode(uint8_t *digests32, const uint8_t *b
  * lwkzg_verify_shard_partial; exposed so that a sharded verifier can log / cross-check it (tests hold it against hashlib). */
 C_KZG_RET lwkzg_batch_challenge_host(uint8_t r_out[32], const uint8_t *records_all, size_t n_total, int mode);
 
-/* Engine introspection / profiling (bench.py). Kernel timings use hipEvents on the launch stream. */
+/* Engine introspection / profiling (bench.py). With the profile on, a kernel's time is read from a hipEvent pair bound to its own
+ * dispatch (no packet beside the launch); scopes of more than one launch are timed by two marker packets on the launch stream. */
 int lwkzg_device_count(void);
 int lwkzg_set_device(int ordinal);                 /* device used by subsequent load_* calls */
 const char *lwkzg_version(void);
@@ -1051,6 +1052,11 @@ void lwkzg_profile_enable(int on);
 void lwkzg_profile_reset(void);
 /* JSON: {"kernel": {"launches": n, "total_ms": t}, ...}; returns bytes needed (incl. NUL) */
 size_t lwkzg_profile_report(char *buf, size_t cap);
+/* Test hook. JSON: what the profile has been made of since the last lwkzg_profile_reset -- {"dispatch_pairs": pairs bound to a launch's
+ * own dispatch, "marker_pairs": scopes timed by marker packets, "shared_markers": of those, scopes whose opening marker is the closing
+ * marker of the scope in front, "event_flags": the hipEventCreateWithFlags flags of the pooled event created last}; returns bytes needed
+ * (incl. NUL). tests/test_gpu_dispatch_events.py reads it. */
+size_t lwkzg_profile_sources(char *buf, size_t cap);
 /* JSON: the wall-clock milliseconds of this settings object's load (context, points + tables, G2 + FFT settings, the
  * default engine's table) and of its last lwkzg_enable_direct_table: freeing the old table, the hipMallocs of the new one
  * (one per window, summed: the GPU builds window j while the host allocates window j + 1), scratch, and what was left of the

@@ -65,7 +65,7 @@ EXPORTED_SYMBOLS = [
     "lwkzg_g1_lincomb_setup_device", "lwkzg_fr_ntt4096_device",
     "lwkzg_setup_image_bytes", "lwkzg_setup_export_device", "lwkzg_setup_import_device",
     "lwkzg_device_count", "lwkzg_set_device", "lwkzg_version", "lwkzg_last_error",
-    "lwkzg_profile_enable", "lwkzg_profile_reset", "lwkzg_profile_report",
+    "lwkzg_profile_enable", "lwkzg_profile_reset", "lwkzg_profile_report", "lwkzg_profile_sources",
     "lwkzg_msm_window_bits", "lwkzg_msm_num_windows", "lwkzg_pairing_product_is_one",
     "lwkzg_challenge_digests_host", "lwkzg_challenge_digests_host_mode", "lwkzg_batch_challenge_host", "lwkzg_g1_msm_tiled_device", "lwkzg_g1_sum_compressed",
     "lwkzg_commit_and_prove_batch_device", "lwkzg_enable_direct_table", "lwkzg_direct_table_bits", "lwkzg_direct_table_forms", "lwkzg_enable_direct_table_forms", "lwkzg_direct_num_windows", "lwkzg_direct_row_bytes",
@@ -257,6 +257,8 @@ def lib():
     l.lwkzg_profile_reset.restype = None
     l.lwkzg_profile_report.argtypes = [C.c_char_p, sz]
     l.lwkzg_profile_report.restype = sz
+    l.lwkzg_profile_sources.argtypes = [C.c_char_p, sz]
+    l.lwkzg_profile_sources.restype = sz
     l.lwkzg_pairing_product_is_one.argtypes = [C.POINTER(C.c_bool), C.c_char_p, C.c_char_p, sz]
     l.lwkzg_challenge_digests_host.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, sz]
     l.lwkzg_challenge_digests_host_mode.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, sz, ci]
@@ -1576,6 +1578,14 @@ def profile_enable(on=True):
 
 def profile_reset():
     lib().lwkzg_profile_reset()
+
+
+def profile_sources():
+    """what the profile has been made of since the last reset (lwkzg_profile_sources: dispatch-bound pairs, marker pairs, shared markers)"""
+    n = lib().lwkzg_profile_sources(None, 0)
+    buf = C.create_string_buffer(n)
+    lib().lwkzg_profile_sources(buf, n)
+    return json.loads(buf.value.decode())
 
 
 def profile_report():

@@ -118,19 +118,17 @@ __global__ __launch_bounds__(256) void k_blob_items_dev(const uint32_t *__restri
 hipError_t launch_cell_blobs_group(const uint8_t *comms48, const uint32_t *item_off, size_t nb, size_t g, uint64_t seed, uint32_t hash_mask,
                                    const BlobGroupOut &o, hipStream_t st) {
     if (nb == 0 || nb > kBlobGroupCap || g == 0) return hipErrorInvalidValue;
-    ProfScope p("k_blob_group", st);
-    hipLaunchKernelGGL(k_blob_group, dim3(1), dim3(kBlobGroupCap), 0, st, comms48, item_off, (uint32_t)nb, (uint32_t)g, seed, hash_mask, o);
+    prof_launch("k_blob_group", st, k_blob_group, dim3(1), dim3(kBlobGroupCap), 0, comms48, item_off, (uint32_t)nb, (uint32_t)g, seed, hash_mask, o);
     return hipGetLastError();
 }
 
 hipError_t launch_cell_blobs_items(const BlobGroupOut &o, const uint32_t *item_off, size_t nb, size_t g, const BlobItemsOut &x, hipStream_t st) {
     if (nb == 0 || nb > kBlobGroupCap || g == 0) return hipErrorInvalidValue;
     const size_t blocks = (nb * kGroupColumns + 255) / 256;
-    ProfScope p("k_blob_items_dev", st);
-    hipLaunchKernelGGL(k_blob_items_dev, dim3((unsigned)blocks), dim3(256), 0, st, (const uint32_t *)o.brow, (const uint32_t *)o.bperm,
-                       item_off ? (const uint32_t *)o.bgroup : nullptr, item_off, (const uint32_t *)o.brow_off, (const uint32_t *)o.bfirst,
-                       (const uint32_t *)o.head, (uint32_t)nb, (uint32_t)g, (uint32_t *)o.distinct, x.col_off, x.row_off, x.first_item,
-                       BlobItemLists{x.idx, x.rows, x.perm_row, x.perm_col, item_off ? x.item_group : nullptr});
+    prof_launch("k_blob_items_dev", st, k_blob_items_dev, dim3((unsigned)blocks), dim3(256), 0, (const uint32_t *)o.brow, (const uint32_t *)o.bperm,
+                item_off ? (const uint32_t *)o.bgroup : nullptr, item_off, (const uint32_t *)o.brow_off, (const uint32_t *)o.bfirst,
+                (const uint32_t *)o.head, (uint32_t)nb, (uint32_t)g, (uint32_t *)o.distinct, x.col_off, x.row_off, x.first_item,
+                BlobItemLists{x.idx, x.rows, x.perm_row, x.perm_col, item_off ? x.item_group : nullptr});
     return hipGetLastError();
 }
 

@@ -231,29 +231,16 @@ void launch_cell_group(const uint8_t *comms48, const uint64_t *idx, size_t n, si
     hipMemsetAsync(g.table, 0xff, slots * 4, st);
     hipMemsetAsync(g.row_cnt, 0, n * 4, st);
     hipMemsetAsync(g.col_cnt, 0, (kGroupColumns + kGroupHeadWords) * 4, st);
-    {
-        ProfScope p("k_group_insert", st);
-        hipLaunchKernelGGL(k_group_insert, per_item, dim3(kGroupLanes), 0, st, comms48, idx, g.table, g.slot_of, g.head, n32,
-                           (uint32_t)(slots - 1), seed, hash_mask);
-    }
-    {
-        ProfScope p("k_group_scan", st);
-        hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(kScanLanes), 0, st, comms48, (const uint32_t *)g.table, (const uint32_t *)g.slot_of,
-                           g.slot_row, g.first_item, g.distinct, (uint32_t *)nullptr, g.head, n32);
-    }
-    {
-        ProfScope p("k_group_rows", st);
-        hipLaunchKernelGGL(k_group_rows, per_item, dim3(kGroupLanes), 0, st, idx, (const uint32_t *)g.slot_of, (const uint32_t *)g.slot_row,
-                           g.rows, g.row_cnt, g.col_cnt, g.distinct, g.head, n32);
-    }
-    {
-        ProfScope p("k_group_offsets", st);
-        hipLaunchKernelGGL(k_group_offsets, dim3(2), dim3(kScanLanes), 0, st, (const uint32_t *)g.row_cnt, (const uint32_t *)g.col_cnt,
-                           g.row_off, g.col_off, (const uint32_t *)g.head, n32, kGroupColumns);
-    }
-    ProfScope p("k_group_scatter", st);
-    hipLaunchKernelGGL(k_group_scatter, per_item, dim3(kGroupLanes), 0, st, idx, (const uint32_t *)g.rows, (const uint32_t *)g.row_off,
-                       (const uint32_t *)g.col_off, g.row_cnt, g.col_cnt, g.perm_row, g.perm_col, n32);
+    prof_launch("k_group_insert", st, k_group_insert, per_item, dim3(kGroupLanes), 0, comms48, idx, g.table, g.slot_of, g.head, n32,
+                (uint32_t)(slots - 1), seed, hash_mask);
+    prof_launch("k_group_scan", st, k_group_scan, dim3(1), dim3(kScanLanes), 0, comms48, (const uint32_t *)g.table, (const uint32_t *)g.slot_of,
+                g.slot_row, g.first_item, g.distinct, (uint32_t *)nullptr, g.head, n32);
+    prof_launch("k_group_rows", st, k_group_rows, per_item, dim3(kGroupLanes), 0, idx, (const uint32_t *)g.slot_of, (const uint32_t *)g.slot_row,
+                g.rows, g.row_cnt, g.col_cnt, g.distinct, g.head, n32);
+    prof_launch("k_group_offsets", st, k_group_offsets, dim3(2), dim3(kScanLanes), 0, (const uint32_t *)g.row_cnt, (const uint32_t *)g.col_cnt,
+                g.row_off, g.col_off, (const uint32_t *)g.head, n32, kGroupColumns);
+    prof_launch("k_group_scatter", st, k_group_scatter, per_item, dim3(kGroupLanes), 0, idx, (const uint32_t *)g.rows, (const uint32_t *)g.row_off,
+                (const uint32_t *)g.col_off, g.row_cnt, g.col_cnt, g.perm_row, g.perm_col, n32);
 }
 
 // ---- the segmented grouping: a call of g groups ---------------------------------------------------------------------
@@ -418,42 +405,26 @@ void launch_cell_group_seg(const uint8_t *comms48, const uint64_t *idx, size_t n
     hipMemsetAsync(s.row_cnt, 0, n * 4, st);
     hipMemsetAsync(s.head, 0, (kGroupHeadWords + kGroupColumns * g) * 4, st);   // (col_cnt behind it: one piece)
     hipMemsetAsync(s.gbad, 0, g * 4, st);
-    {
-        ProfScope p("k_seg_mark", st);
-        hipLaunchKernelGGL(k_seg_mark, per_item, dim3(kGroupLanes), 0, st, idx, (const uint32_t *)s.item_off, s.item_group, s.gbad, n32, g32);
-    }
-    {
-        ProfScope p("k_seg_insert", st);
-        hipLaunchKernelGGL(k_seg_insert, per_item, dim3(kGroupLanes), 0, st, comms48, (const uint32_t *)s.item_off,
-                           (const uint32_t *)s.item_group, (const uint32_t *)s.gbad, s.table, s.slot_of, s.head, n32, (uint32_t)(slots - 1), seed,
-                           hash_mask);
-    }
-    {   // (the two shared kernels keep this call's names in the profile)
-        ProfScope p("k_seg_scan", st);
-        hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(kScanLanes), 0, st, comms48, (const uint32_t *)s.table, (const uint32_t *)s.slot_of,
-                           s.slot_row, s.first_item, s.distinct, s.pre, s.head, n32);
-    }
-    {
-        ProfScope p("k_seg_rows", st);
-        hipLaunchKernelGGL(k_seg_rows, dim3((unsigned)((lanes + kGroupLanes - 1) / kGroupLanes)), dim3(kGroupLanes), 0, st, idx,
-                           (const uint32_t *)s.item_off, (const uint32_t *)s.item_group, s.slot_of, (const uint32_t *)s.slot_row,
-                           (const uint32_t *)s.pre, s.rows, s.row_base, s.row_cnt, s.col_cnt, s.distinct, s.head, n32, g32);
-    }
-    {
-        ProfScope p("k_seg_offsets", st);
-        hipLaunchKernelGGL(k_group_offsets, dim3(2), dim3(kScanLanes), 0, st, (const uint32_t *)s.row_cnt, (const uint32_t *)s.col_cnt, s.row_off,
-                           s.col_off, (const uint32_t *)s.head, n32, (uint32_t)(kGroupColumns * g));
-    }
-    ProfScope p("k_seg_scatter", st);
-    hipLaunchKernelGGL(k_seg_scatter, per_item, dim3(kGroupLanes), 0, st, idx, (const uint32_t *)s.item_group, (const uint32_t *)s.slot_of,
-                       (const uint32_t *)s.row_off, (const uint32_t *)s.col_off, s.row_cnt, s.col_cnt, s.perm_row, s.perm_col, n32);
+    prof_launch("k_seg_mark", st, k_seg_mark, per_item, dim3(kGroupLanes), 0, idx, (const uint32_t *)s.item_off, s.item_group, s.gbad, n32, g32);
+    prof_launch("k_seg_insert", st, k_seg_insert, per_item, dim3(kGroupLanes), 0, comms48, (const uint32_t *)s.item_off,
+                (const uint32_t *)s.item_group, (const uint32_t *)s.gbad, s.table, s.slot_of, s.head, n32, (uint32_t)(slots - 1), seed,
+                hash_mask);
+    // (the two shared kernels keep this call's names in the profile)
+    prof_launch("k_seg_scan", st, k_group_scan, dim3(1), dim3(kScanLanes), 0, comms48, (const uint32_t *)s.table, (const uint32_t *)s.slot_of,
+                s.slot_row, s.first_item, s.distinct, s.pre, s.head, n32);
+    prof_launch("k_seg_rows", st, k_seg_rows, dim3((unsigned)((lanes + kGroupLanes - 1) / kGroupLanes)), dim3(kGroupLanes), 0, idx,
+                (const uint32_t *)s.item_off, (const uint32_t *)s.item_group, s.slot_of, (const uint32_t *)s.slot_row, (const uint32_t *)s.pre,
+                s.rows, s.row_base, s.row_cnt, s.col_cnt, s.distinct, s.head, n32, g32);
+    prof_launch("k_seg_offsets", st, k_group_offsets, dim3(2), dim3(kScanLanes), 0, (const uint32_t *)s.row_cnt, (const uint32_t *)s.col_cnt,
+                s.row_off, s.col_off, (const uint32_t *)s.head, n32, (uint32_t)(kGroupColumns * g));
+    prof_launch("k_seg_scatter", st, k_seg_scatter, per_item, dim3(kGroupLanes), 0, idx, (const uint32_t *)s.item_group, (const uint32_t *)s.slot_of,
+                (const uint32_t *)s.row_off, (const uint32_t *)s.col_off, s.row_cnt, s.col_cnt, s.perm_row, s.perm_col, n32);
 }
 
 void launch_cell_group_slice_table(const uint32_t *item_off, const uint32_t *row_base, const uint32_t *gflag, GroupSlice *slices,
                                    uint32_t *slice_off, size_t g, size_t max_slices, hipStream_t st) {
-    ProfScope p("k_seg_slice_table", st);
-    hipLaunchKernelGGL(k_seg_slice_table, dim3(1), dim3(kScanLanes), 0, st, item_off, row_base, gflag, slices, slice_off, (uint32_t)(3 * g),
-                       (uint32_t)max_slices);
+    prof_launch("k_seg_slice_table", st, k_seg_slice_table, dim3(1), dim3(kScanLanes), 0, item_off, row_base, gflag, slices, slice_off,
+                (uint32_t)(3 * g), (uint32_t)max_slices);
 }
 
 namespace {

@@ -90,22 +90,15 @@ void launch_cells_extend(const uint32_t *coeffs_raw, const Fr *tw_fwd, const Fr2
                          int le, size_t n_blobs, hipStream_t st, const CellColumns *cols, uint32_t c) {
     const size_t n = 2 * n_blobs * kBlobElems;
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    {
-        ProfScope p("k_cells_extend_in", st);
-        hipLaunchKernelGGL(k_cells_extend_in, dim3(blocks), dim3(256), 0, st, (const uint4 *)coeffs_raw, tw_fwd, scratch, n);
-    }
+    prof_launch("k_cells_extend_in", st, k_cells_extend_in, dim3(blocks), dim3(256), 0, (const uint4 *)coeffs_raw, tw_fwd, scratch, n);
     launch_ntt4096(scratch, scratch2, tw28_fwd, 0, 2 * n_blobs, st);
     if (cols) {   // the transforms stay whole; only the wanted cells leave
-        ProfScope p("k_cells_extend_out_columns", st);
         const size_t n_out = n_blobs * c * kCellElems;
-        hipLaunchKernelGGL(k_cells_extend_out_columns, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, (const Fr *)scratch2,
-                           (uint4 *)cells, le, *cols, c, n_out);
+        prof_launch("k_cells_extend_out_columns", st, k_cells_extend_out_columns, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0,
+                    (const Fr *)scratch2, (uint4 *)cells, le, *cols, c, n_out);
         return;
     }
-    {
-        ProfScope p("k_cells_extend_out", st);
-        hipLaunchKernelGGL(k_cells_extend_out, dim3(blocks), dim3(256), 0, st, (const Fr *)scratch2, (uint4 *)cells, le, n);
-    }
+    prof_launch("k_cells_extend_out", st, k_cells_extend_out, dim3(blocks), dim3(256), 0, (const Fr *)scratch2, (uint4 *)cells, le, n);
 }
 
 // One lane per (blob, cell k, t = j mod 64): a wave is one (blob, cell) and reads 64 consecutive coefficients / writes 64 consecutive
@@ -148,18 +141,16 @@ __global__ __launch_bounds__(256) void k_cells_quotients_columns(const uint4 *__
 }
 
 void launch_cells_quotients(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, size_t n_cells, hipStream_t st) {
-    ProfScope p("k_cells_quotients", st);
     const size_t n = n_cells * kCellElems;
-    hipLaunchKernelGGL(k_cells_quotients, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)coeffs_raw, tw_fwd,
-                       (uint4 *)quot_raw, n_cells);
+    prof_launch("k_cells_quotients", st, k_cells_quotients, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint4 *)coeffs_raw, tw_fwd,
+                (uint4 *)quot_raw, n_cells);
 }
 
 void launch_cells_quotients_columns(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *quot_raw, const CellColumns &cols, uint32_t c,
                                     size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_cells_quotients_columns", st);
     const size_t n_sets = n_blobs * c, n = n_sets * kCellElems;
-    hipLaunchKernelGGL(k_cells_quotients_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)coeffs_raw, tw_fwd,
-                       (uint4 *)quot_raw, cols, c, n_sets);
+    prof_launch("k_cells_quotients_columns", st, k_cells_quotients_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                (const uint4 *)coeffs_raw, tw_fwd, (uint4 *)quot_raw, cols, c, n_sets);
 }
 
 }  // namespace lwk

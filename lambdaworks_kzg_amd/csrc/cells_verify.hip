@@ -101,9 +101,8 @@ __global__ __launch_bounds__(64) void k_cellv_digests(const uint4 *__restrict__ 
 
 void launch_cellv_digests(const uint8_t *cells, const uint8_t *proofs48, const uint32_t *rows, const uint64_t *idx, uint8_t *digests32,
                           int32_t *status, int bad_code, int le, size_t n, hipStream_t st) {
-    ProfScope p("k_cellv_digests", st);
-    hipLaunchKernelGGL(k_cellv_digests, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const uint4 *)cells, (const uint4 *)proofs48, rows,
-                       idx, (uint32_t *)digests32, status, bad_code, le, (uint32_t)n);
+    prof_launch("k_cellv_digests", st, k_cellv_digests, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (const uint4 *)cells, (const uint4 *)proofs48,
+                rows, idx, (uint32_t *)digests32, status, bad_code, le, (uint32_t)n);
 }
 
 // ---- behind r: a_i = r^i, b_i = a_i c_{k_i} ------------------------------------------------------------------------------------------
@@ -146,19 +145,15 @@ __global__ __launch_bounds__(64) void k_cellv_row_weights(const Fr *__restrict__
 void launch_cellv_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b,
                           const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t n, size_t m, hipStream_t st,
                           const uint32_t *m_dev, const uint32_t *skip) {
-    {
-        ProfScope p("k_cellv_scalars", st);
-        hipLaunchKernelGGL(k_cellv_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pw, idx, tw_fwd, a_mont, sc_a, sc_b, (uint32_t)n,
-                           skip);
-    }
+    prof_launch("k_cellv_scalars", st, k_cellv_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pw, idx, tw_fwd, a_mont, sc_a, sc_b,
+                (uint32_t)n, skip);
     launch_cellv_row_weights(a_mont, perm_row, row_off, sc_c, m_dev ? n : m, st, m_dev, skip);
 }
 
 void launch_cellv_row_weights(const Fr *a_mont, const uint32_t *perm_row, const uint32_t *row_off, uint32_t *sc_c, size_t rows, hipStream_t st,
                               const uint32_t *m_dev, const uint32_t *skip) {
     if (rows == 0) return;
-    ProfScope p("k_cellv_row_weights", st);
-    hipLaunchKernelGGL(k_cellv_row_weights, dim3((unsigned)rows), dim3(64), 0, st, a_mont, perm_row, row_off, sc_c, m_dev, skip);
+    prof_launch("k_cellv_row_weights", st, k_cellv_row_weights, dim3((unsigned)rows), dim3(64), 0, a_mont, perm_row, row_off, sc_c, m_dev, skip);
 }
 
 // ---- the fault words of an asynchronous verifier ------------------------------------------------------------------------------------
@@ -174,8 +169,8 @@ __global__ __launch_bounds__(256) void k_cellv_fault_words(int32_t *__restrict__
 }
 
 void launch_cellv_fault_words(int32_t *fault, const int32_t *kind_p, const int32_t *kind_c, int bad_code, size_t n, hipStream_t st) {
-    ProfScope p("k_cellv_fault_words", st);
-    hipLaunchKernelGGL(k_cellv_fault_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fault, kind_p, kind_c, bad_code, (uint32_t)n);
+    prof_launch("k_cellv_fault_words", st, k_cellv_fault_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fault, kind_p, kind_c, bad_code,
+                (uint32_t)n);
 }
 
 hipError_t launch_cellv_first_visit(const uint8_t *cells, const uint64_t *idx, const uint32_t *rows, const PointSet &set_p, const PointSet &set_c,
@@ -187,7 +182,7 @@ hipError_t launch_cellv_first_visit(const uint8_t *cells, const uint64_t *idx, c
     launch_cellv_digests(cells, set_p.in48, rows, idx, digests32, fault, bad_code, le, n, st);
     if (digests_done) e = hipEventRecord(digests_done, st);
     launch_decompress_points(set_p, &set_c, n, st);
-    launch_subgroup_canon(set_p, &set_c, status, bad_code, n, st);
+    launch_subgroup_canon(set_p, &set_c, status, bad_code, n, st, false, true);
     launch_cellv_fault_words(fault, set_p.kind, set_c.kind, bad_code, n, st);
     return e;
 }
@@ -252,14 +247,10 @@ __global__ __launch_bounds__(256) void k_cellv_coeffs(const Fr *__restrict__ col
 
 void launch_cellv_interpolant(const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off, const Fr *tw_inv,
                               Fr *colcoef, uint32_t *slot_raw, int le, hipStream_t st, const uint32_t *flag, size_t first, size_t groups) {
-    {
-        ProfScope p("k_cellv_columns", st);
-        hipLaunchKernelGGL(k_cellv_columns, dim3(kCellsPerBlob, (unsigned)groups), dim3(256), 0, st, (const uint4 *)cells, a_mont, perm_col,
-                           col_off, flag, tw_inv, colcoef, le, (uint32_t)first);
-    }
-    ProfScope p("k_cellv_coeffs", st);
-    hipLaunchKernelGGL(k_cellv_coeffs, dim3(kBlobElems / 256, (unsigned)groups), dim3(256), 0, st, (const Fr *)colcoef, flag, (Fr *)slot_raw,
-                       (uint32_t)first);
+    prof_launch("k_cellv_columns", st, k_cellv_columns, dim3(kCellsPerBlob, (unsigned)groups), dim3(256), 0, (const uint4 *)cells, a_mont,
+                perm_col, col_off, flag, tw_inv, colcoef, le, (uint32_t)first);
+    prof_launch("k_cellv_coeffs", st, k_cellv_coeffs, dim3(kBlobElems / 256, (unsigned)groups), dim3(256), 0, (const Fr *)colcoef, flag,
+                (Fr *)slot_raw, (uint32_t)first);
 }
 
 }  // namespace lwk

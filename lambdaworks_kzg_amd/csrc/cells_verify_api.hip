@@ -139,7 +139,7 @@ C_KZG_RET cell_batch_sums(uint32_t r_raw[8], uint8_t sums[3][96], int infs[3], u
     clk.mark(1);
     const PointSet set_p{d_proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{b.comm_in, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
     launch_decompress_points(set_p, &set_c, n, st);
-    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st);
+    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st, false, true);
     if (front) front->fold_status(b.status, bad, st);
     clk.mark(2);
     LWK_HIP(hipMemcpyAsync(pin_dig, b.digests, 32 * n, hipMemcpyDeviceToHost, st));

@@ -153,14 +153,10 @@ struct BlobFront : CellFront {
             LWK_HIP(upload(gl->slice_off, plan.slice_off, st));
             LWK_HIP(upload(gl->slices, plan.slices, st));
         }
-        {
-            ProfScope p("k_blob_items", st);
-            hipLaunchKernelGGL(k_blob_items, dim3(grid_for(nb * kCellsPerBlob)), dim3(256), 0, st, (const uint32_t *)bb.brow,
-                               (const uint32_t *)bb.bperm, grouped ? (const uint32_t *)bb.bgroup : nullptr,
-                               grouped ? (const uint32_t *)gl->item_off : nullptr, (uint32_t)nb, (uint32_t)m, (uint32_t)t.groups,
-                               (uint32_t *)b.comm_in, b.col_off,
-                               BlobItemLists{b.idx, b.rows, b.perm_row, b.perm_col, grouped ? gl->item_group : nullptr});
-        }
+        prof_launch("k_blob_items", st, k_blob_items, dim3(grid_for(nb * kCellsPerBlob)), dim3(256), 0, (const uint32_t *)bb.brow,
+                    (const uint32_t *)bb.bperm, grouped ? (const uint32_t *)bb.bgroup : nullptr,
+                    grouped ? (const uint32_t *)gl->item_off : nullptr, (uint32_t)nb, (uint32_t)m, (uint32_t)t.groups, (uint32_t *)b.comm_in,
+                    b.col_off, BlobItemLists{b.idx, b.rows, b.perm_row, b.perm_col, grouped ? gl->item_group : nullptr});
         LWK_HIP(hipGetLastError());
         return C_KZG_OK;
     }
@@ -179,8 +175,7 @@ C_KZG_RET launch_blob_cells(Ctx *c, uint8_t *cells, int32_t *bstatus, const uint
 
 hipError_t launch_blob_fold_status(int32_t *words, const int32_t *bstatus, size_t nb, int mode, int bad_code, hipStream_t st) {
     if (!mode_rules(mode).evaluation_form) return hipSuccess;   // reference mode reduces: no blob is rejected
-    ProfScope p("k_blob_fold_status", st);
-    hipLaunchKernelGGL(k_blob_fold_status, dim3(grid_for(nb * kCellsPerBlob)), dim3(256), 0, st, words, bstatus, (uint32_t)nb, bad_code);
+    prof_launch("k_blob_fold_status", st, k_blob_fold_status, dim3(grid_for(nb * kCellsPerBlob)), dim3(256), 0, words, bstatus, (uint32_t)nb, bad_code);
     return hipPeekAtLastError();   // (left standing for the pipeline's own hipGetLastError)
 }
 

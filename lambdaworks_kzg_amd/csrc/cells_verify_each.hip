@@ -216,21 +216,15 @@ C_KZG_RET cell_each_impl(uint8_t *ok_out, int32_t *rc_out, uint8_t *points_out, 
     const int bad = (int)bad_input(mode);
     const PointSet set_p{d_proofs, b.pts_p, b.kind_p, b.canon_p, b.verdict_p}, set_c{d_comms, b.pts_c, b.kind_c, b.canon_c, b.verdict_c};
     launch_decompress_points(set_p, &set_c, n, st);
-    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st);
+    launch_subgroup_canon(set_p, &set_c, b.status, bad, n, st, false, true);
     uint32_t braw[12];
     g1_beta_raw(braw);
     const Fp beta = fe_from_raw<FpParams>(braw);
-    {
-        ProfScope p("k_celleach_commit", st);
-        hipLaunchKernelGGL(k_celleach_commit, dim3((unsigned)n), dim3(kCellElems), 0, st, (const uint4 *)d_cells, d_idx, (const Fr *)c->tw_inv,
-                           (const G1Affine *)c->points, beta, b.status, bad, le, b.isum);
-    }
-    {
-        ProfScope p("k_celleach_combine", st);
-        hipLaunchKernelGGL(k_celleach_combine, dim3(each_blocks(n)), dim3(kEachBlock), 0, st, (const G1Affine29 *)b.pts_c,
-                           (const int32_t *)b.kind_c, (const G1Affine29 *)b.pts_p, (const int32_t *)b.kind_p, (const int32_t *)b.status, d_idx,
-                           (const Fr *)c->tw_fwd, (const G1Xyzz *)b.isum, beta, b.pts, n);
-    }
+    prof_launch("k_celleach_commit", st, k_celleach_commit, dim3((unsigned)n), dim3(kCellElems), 0, (const uint4 *)d_cells, d_idx,
+                (const Fr *)c->tw_inv, (const G1Affine *)c->points, beta, b.status, bad, le, b.isum);
+    prof_launch("k_celleach_combine", st, k_celleach_combine, dim3(each_blocks(n)), dim3(kEachBlock), 0, (const G1Affine29 *)b.pts_c,
+                (const int32_t *)b.kind_c, (const G1Affine29 *)b.pts_p, (const int32_t *)b.kind_p, (const int32_t *)b.status, d_idx,
+                (const Fr *)c->tw_fwd, (const G1Xyzz *)b.isum, beta, b.pts, n);
     LWK_HIP(hipGetLastError());
     if (points_out) {
         LWK_HIP(hipMemcpyAsync(h_pts.data(), b.pts, n * sizeof(EachPoints), hipMemcpyDeviceToHost, st));

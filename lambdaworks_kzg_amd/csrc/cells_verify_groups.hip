@@ -127,9 +127,8 @@ size_t cellg_colcoef_bytes() { return kInterpChunk * kInterpGroupBytes; }
 
 void launch_cellg_scalars(const Fr *pw, const uint64_t *idx, const Fr *tw_fwd, const uint32_t *item_group, const uint32_t *item_off,
                           const uint32_t *gflag, Fr *a_mont, uint32_t *sc_a, uint32_t *sc_b, size_t n, hipStream_t st) {
-    ProfScope p("k_cellg_scalars", st);
-    hipLaunchKernelGGL(k_cellg_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pw, idx, tw_fwd, item_group, item_off, gflag, a_mont,
-                       sc_a, sc_b, (uint32_t)n);
+    prof_launch("k_cellg_scalars", st, k_cellg_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pw, idx, tw_fwd, item_group, item_off, gflag,
+                a_mont, sc_a, sc_b, (uint32_t)n);
 }
 
 void launch_cellg_interpolants(Ctx *c, int mode, const uint8_t *cells, const Fr *a_mont, const uint32_t *perm_col, const uint32_t *col_off,
@@ -153,13 +152,11 @@ void launch_cellg_sums(const GroupSlice *slices, const uint32_t *slice_off, cons
     g1_beta_raw(braw);
     const Fp beta = fe_from_raw<FpParams>(braw);
     if (workgroups) {
-        ProfScope p("k_cellg_slices", st);
-        hipLaunchKernelGGL(k_cellg_slices, dim3((unsigned)workgroups), dim3(kCellElems), 0, st, slices, gflag, sc_a, sc_b, sc_c, pts_p, kind_p,
-                           pts_c, kind_c, beta, part, live);
+        prof_launch("k_cellg_slices", st, k_cellg_slices, dim3((unsigned)workgroups), dim3(kCellElems), 0, slices, gflag, sc_a, sc_b, sc_c, pts_p,
+                    kind_p, pts_c, kind_c, beta, part, live);
     }
-    ProfScope p("k_cellg_fold", st);
-    hipLaunchKernelGGL(k_cellg_fold, dim3((unsigned)((3 * g + 63) / 64)), dim3(64), 0, st, (const G1Xyzz *)part, slice_off, gflag, out96, inf,
-                       (uint32_t)(3 * g));
+    prof_launch("k_cellg_fold", st, k_cellg_fold, dim3((unsigned)((3 * g + 63) / 64)), dim3(64), 0, (const G1Xyzz *)part, slice_off, gflag, out96,
+                inf, (uint32_t)(3 * g));
 }
 
 namespace {

@@ -112,6 +112,19 @@ size_t lwkzg_profile_report(char *buf, size_t cap) {
     return s.size() + 1;
 }
 
+size_t lwkzg_profile_sources(char *buf, size_t cap) {
+    const ProfSources p = prof_sources();
+    char s[256];
+    const int n = snprintf(s, sizeof s, "{\"dispatch_pairs\": %llu, \"marker_pairs\": %llu, \"shared_markers\": %llu, \"event_flags\": %u}",
+                           (unsigned long long)p.dispatch_pairs, (unsigned long long)p.marker_pairs, (unsigned long long)p.shared_markers, p.event_flags);
+    if (buf && cap) {
+        const size_t k = (size_t)n < cap - 1 ? (size_t)n : cap - 1;
+        memcpy(buf, s, k);
+        buf[k] = 0;
+    }
+    return (size_t)n + 1;
+}
+
 // first use of the HIP runtime by this process (device context, this library's code object): what a fresh process pays
 // once, whichever call comes first. Returns 0, or -1 without a GPU.
 __global__ void k_runtime_init(int *p) {

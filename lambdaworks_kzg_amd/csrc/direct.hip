@@ -170,10 +170,7 @@ hipError_t build_direct_table(int bits, const G1Affine *points, DirectTable &t, 
     const double t1 = wall_ms();
     double malloc_ms = 0, t_last_malloc = t1;
     if (e == hipSuccess) {
-        {
-            ProfScope p("k_direct_qbase", st);
-            hipLaunchKernelGGL(k_direct_qbase, dim3(kBlobElems / 64), dim3(64), 0, st, points, qbase, P.c, P.nw);
-        }
+        prof_launch("k_direct_qbase", st, k_direct_qbase, dim3(kBlobElems / 64), dim3(64), 0, points, qbase, P.c, P.nw);
         // window by window: the host allocates window j + 1 while the GPU builds window j (the launches are asynchronous)
         for (int j = 0; j < P.nw && e == hipSuccess; j++) {
             const bool top = j == P.nw - 1;
@@ -186,9 +183,8 @@ hipError_t build_direct_table(int bits, const G1Affine *points, DirectTable &t, 
                 if (e != hipSuccess) break;
                 t.bytes += rows * row_bytes;
             }
-            ProfScope p("k_direct_build", st);
-            hipLaunchKernelGGL(k_direct_build, dim3((unsigned)(n_threads / 256)), dim3(256), 0, st, qbase + (size_t)j * kBlobElems,
-                               (G1Affine29 *)t.win[j], (size_t)kBlobElems, scratch, n_threads, (int)(top ? P.htop : P.h), row_bytes);
+            prof_launch("k_direct_build", st, k_direct_build, dim3((unsigned)(n_threads / 256)), dim3(256), 0, qbase + (size_t)j * kBlobElems,
+                        (G1Affine29 *)t.win[j], (size_t)kBlobElems, scratch, n_threads, (int)(top ? P.htop : P.h), row_bytes);
         }
         if (e == hipSuccess && !in_place) {
             uint64_t h[kDirectMaxWindows] = {};
@@ -702,23 +698,16 @@ static bool launch_direct_t(const DirectPlanRt &plan, const uint64_t *table, siz
             // a one-blob call (r06, host_api.hip: combine_run): the hand-off counters have been cleared by the parse kernel in front of this
             // launch, the redo flag is a word of pinned host memory the caller cleared and will look at after its one synchronisation -- no
             // fill launch, and no second-pass launch that would exit at its first instruction (the caller repeats a flagged call the long way)
-            ProfScope p("k_coop_msm_asm", st);
-            hipLaunchKernelGGL(k_coop_msm_asm, dim3(prm.n0 / 4, (unsigned)n_blobs), dim3(256), 0, st, table, (const uint4 *)scalars_raw,
-                               (uint32_t *)lane_scratch, ctr, sums, redo_flag_out, prm);
+            prof_launch("k_coop_msm_asm", st, k_coop_msm_asm, dim3(prm.n0 / 4, (unsigned)n_blobs), dim3(256), 0, table, (const uint4 *)scalars_raw,
+                        (uint32_t *)lane_scratch, ctr, sums, redo_flag_out, prm);
             return false;
         }
         hipMemsetAsync(redo, 0, n_blobs * (1 + (size_t)counters) * sizeof(uint32_t), st);
-        {
-            ProfScope p("k_coop_msm_asm", st);
-            hipLaunchKernelGGL(k_coop_msm_asm, dim3(prm.n0 / 4, (unsigned)n_blobs), dim3(256), 0, st, table, (const uint4 *)scalars_raw,
-                               (uint32_t *)lane_scratch, ctr, sums, redo, prm);
-        }
-        {
-            // (one workgroup per flagged blob: slow and complete; none on honest data)
-            ProfScope p("k_direct_redo", st);
-            hipLaunchKernelGGL(k_direct_accumulate<CT>, dim3(1, (unsigned)n_blobs, 1), dim3(kDirThreads), 0, st, table,
-                               (const uint4 *)scalars_raw, sums, kBlobElems / kDirThreads, plan, (uint32_t)row_bytes, (const uint32_t *)redo);
-        }
+        prof_launch("k_coop_msm_asm", st, k_coop_msm_asm, dim3(prm.n0 / 4, (unsigned)n_blobs), dim3(256), 0, table, (const uint4 *)scalars_raw,
+                    (uint32_t *)lane_scratch, ctr, sums, redo, prm);
+        // (one workgroup per flagged blob: slow and complete; none on honest data)
+        prof_launch("k_direct_redo", st, k_direct_accumulate<CT>, dim3(1, (unsigned)n_blobs, 1), dim3(kDirThreads), 0, table,
+                    (const uint4 *)scalars_raw, sums, kBlobElems / kDirThreads, plan, (uint32_t)row_bytes, (const uint32_t *)redo);
         return false;
     }
     int blocks_per_blob = 1, wsplit = 1;
@@ -731,28 +720,16 @@ static bool launch_direct_t(const DirectPlanRt &plan, const uint64_t *table, siz
         // one workgroup per blob: accumulate, second pass, tail (k_commit_tail). The second pass is at most one workgroup per compute unit,
         // each walking its share of the flags, instead of one dispatch (with its LDS) per blob that reads one flag and leaves
         if (!redo_cleared) hipMemsetAsync(redo, 0, n_blobs * sizeof(uint32_t), st);   // (else the parse kernel in front cleared them)
-        {
-            ProfScope p("k_direct_accumulate_asm", st);
-            hipLaunchKernelGGL(k_direct_accumulate_asm, dim3(1, (unsigned)n_blobs), dim3(kDirThreads), 0, st, table, (const uint4 *)scalars_raw,
-                               (uint32_t *)lane_scratch, redo, kBlobElems / kDirThreads, plan, (uint32_t)row_bytes);
-        }
-        {
-            ProfScope p("k_direct_redo", st);
-            const unsigned rows = n_blobs < (size_t)kRedoRows ? (unsigned)n_blobs : (unsigned)kRedoRows;
-            hipLaunchKernelGGL(k_direct_second_pass<CT>, dim3(1, rows, 1), dim3(kDirThreads), 0, st, table, (const uint4 *)scalars_raw, sums,
-                               plan, (uint32_t)row_bytes, (const uint32_t *)redo, (uint32_t)n_blobs);
-        }
-        {
-            ProfScope p("k_commit_tail", st);
-            // (tests/test_gpu_full_chunk_flags.py runs flagged blobs through BOTH instantiations and relies on this condition to reach them:
-            // 1024 blobs on a settings object with one context take <true>, 1023 take <false>)
-            if (n_blobs >= 1024 && !fill)   // a chip's worth of blobs and nobody beside us: one wave per SIMD
-                hipLaunchKernelGGL(k_commit_tail<true>, dim3((unsigned)n_blobs), dim3(64), 0, st, (const uint32_t *)lane_scratch, sums, redo, out48,
-                                   kDirThreads);
-            else
-                hipLaunchKernelGGL(k_commit_tail<false>, dim3((unsigned)n_blobs), dim3(64), 0, st, (const uint32_t *)lane_scratch, sums, redo, out48,
-                                   kDirThreads);
-        }
+        prof_launch("k_direct_accumulate_asm", st, k_direct_accumulate_asm, dim3(1, (unsigned)n_blobs), dim3(kDirThreads), 0, table,
+                    (const uint4 *)scalars_raw, (uint32_t *)lane_scratch, redo, kBlobElems / kDirThreads, plan, (uint32_t)row_bytes);
+        const unsigned rows = n_blobs < (size_t)kRedoRows ? (unsigned)n_blobs : (unsigned)kRedoRows;
+        prof_launch("k_direct_redo", st, k_direct_second_pass<CT>, dim3(1, rows, 1), dim3(kDirThreads), 0, table, (const uint4 *)scalars_raw, sums,
+                    plan, (uint32_t)row_bytes, (const uint32_t *)redo, (uint32_t)n_blobs);
+        // (tests/test_gpu_full_chunk_flags.py runs flagged blobs through BOTH instantiations and relies on this condition to reach them:
+        // 1024 blobs on a settings object with one context take <true>, 1023 take <false>)
+        const bool alone = n_blobs >= 1024 && !fill;   // a chip's worth of blobs and nobody beside us: one wave per SIMD
+        prof_launch("k_commit_tail", st, alone ? k_commit_tail<true> : k_commit_tail<false>, dim3((unsigned)n_blobs), dim3(64), 0,
+                    (const uint32_t *)lane_scratch, sums, redo, out48, kDirThreads);
         return true;
     }
     if (direct_asm_enabled() && wsplit == 1) {
@@ -762,42 +739,25 @@ static bool launch_direct_t(const DirectPlanRt &plan, const uint64_t *table, siz
         // in the fold: profiles/r03_experiments.md.)
         const int threads = kDirThreads;
         hipMemsetAsync(redo, 0, n_blobs * sizeof(uint32_t), st);
-        {
-            ProfScope p("k_direct_accumulate_asm", st);
-            hipLaunchKernelGGL(k_direct_accumulate_asm, dim3(blocks_per_blob, (unsigned)n_blobs), dim3(threads), 0, st, table,
-                               (const uint4 *)scalars_raw, (uint32_t *)lane_scratch, redo, kBlobElems / (threads * blocks_per_blob), plan,
-                               (uint32_t)row_bytes);
+        prof_launch("k_direct_accumulate_asm", st, k_direct_accumulate_asm, dim3(blocks_per_blob, (unsigned)n_blobs), dim3(threads), 0, table,
+                    (const uint4 *)scalars_raw, (uint32_t *)lane_scratch, redo, kBlobElems / (threads * blocks_per_blob), plan,
+                    (uint32_t)row_bytes);
+        const int n_units = (int)n_blobs * blocks_per_blob;
+        if (knobs().fold_asm) {
+            const bool alone = n_units >= 1024 && !fill;   // a chip's worth of units and nobody beside us: one wave per SIMD
+            prof_launch("k_direct_fold_lanes", st, alone ? k_direct_fold_lanes_asm_alone : k_direct_fold_lanes_asm, dim3((unsigned)n_units),
+                        dim3(64), 0, (const uint32_t *)lane_scratch, dest, redo, threads, blocks_per_blob);
+        } else {
+            prof_launch("k_direct_fold_lanes", st, k_direct_fold_lanes, dim3((unsigned)n_units), dim3(64), 0, (const uint32_t *)lane_scratch, dest,
+                        (const uint32_t *)redo, threads, blocks_per_blob);
         }
-        {
-            ProfScope p("k_direct_fold_lanes", st);
-            const int n_units = (int)n_blobs * blocks_per_blob;
-            const bool fold_asm = knobs().fold_asm;
-            if (fold_asm) {
-                if (n_units >= 1024 && !fill)   // a chip's worth of units and nobody beside us: one wave per SIMD
-                    hipLaunchKernelGGL(k_direct_fold_lanes_asm_alone, dim3((unsigned)n_units), dim3(64), 0, st, (const uint32_t *)lane_scratch,
-                                       dest, redo, threads, blocks_per_blob);
-                else
-                    hipLaunchKernelGGL(k_direct_fold_lanes_asm, dim3((unsigned)n_units), dim3(64), 0, st, (const uint32_t *)lane_scratch, dest,
-                                       redo, threads, blocks_per_blob);
-            } else {
-                hipLaunchKernelGGL(k_direct_fold_lanes, dim3((unsigned)n_units), dim3(64), 0, st, (const uint32_t *)lane_scratch, dest,
-                                   (const uint32_t *)redo, threads, blocks_per_blob);
-            }
-        }
-        {
-            ProfScope p("k_direct_redo", st);
-            hipLaunchKernelGGL(k_direct_accumulate<CT>, dim3(blocks_per_blob, (unsigned)n_blobs, 1), dim3(kDirThreads), 0, st, table,
-                               (const uint4 *)scalars_raw, dest, scalars_per_lane, plan, (uint32_t)row_bytes, (const uint32_t *)redo);
-        }
+        prof_launch("k_direct_redo", st, k_direct_accumulate<CT>, dim3(blocks_per_blob, (unsigned)n_blobs, 1), dim3(kDirThreads), 0, table,
+                    (const uint4 *)scalars_raw, dest, scalars_per_lane, plan, (uint32_t)row_bytes, (const uint32_t *)redo);
     } else {
-        ProfScope p("k_direct_accumulate", st);
-        hipLaunchKernelGGL(k_direct_accumulate<CT>, dim3(blocks_per_blob, (unsigned)n_blobs, wsplit), dim3(kDirThreads), 0, st,
-                           table, (const uint4 *)scalars_raw, dest, scalars_per_lane, plan, (uint32_t)row_bytes, (const uint32_t *)nullptr);
+        prof_launch("k_direct_accumulate", st, k_direct_accumulate<CT>, dim3(blocks_per_blob, (unsigned)n_blobs, wsplit), dim3(kDirThreads), 0,
+                    table, (const uint4 *)scalars_raw, dest, scalars_per_lane, plan, (uint32_t)row_bytes, (const uint32_t *)nullptr);
     }
-    if (parts > 1) {
-        ProfScope p("k_direct_fold", st);
-        hipLaunchKernelGGL(k_direct_fold, dim3((unsigned)n_blobs), dim3(64), 0, st, partials, sums, parts);
-    }
+    if (parts > 1) prof_launch("k_direct_fold", st, k_direct_fold, dim3((unsigned)n_blobs), dim3(64), 0, partials, sums, parts);
     return false;
 }
 
@@ -839,9 +799,8 @@ uint32_t direct_one_blob_counter_words(int bits) {
 template <int CT>
 static void launch_direct_only_t(const DirectPlanRt &plan, const uint64_t *table, size_t row_bytes, const uint32_t *scalars_raw, G1Xyzz29 *sums,
                                  const uint32_t *only_if, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_direct_redo", st);
-    hipLaunchKernelGGL(k_direct_accumulate<CT>, dim3(1, (unsigned)n_blobs, 1), dim3(kDirThreads), 0, st, table, (const uint4 *)scalars_raw, sums,
-                       kBlobElems / kDirThreads, plan, (uint32_t)row_bytes, only_if);
+    prof_launch("k_direct_redo", st, k_direct_accumulate<CT>, dim3(1, (unsigned)n_blobs, 1), dim3(kDirThreads), 0, table, (const uint4 *)scalars_raw, sums,
+                kBlobElems / kDirThreads, plan, (uint32_t)row_bytes, only_if);
 }
 
 void launch_direct_msm_only(int bits, const uint64_t *table, size_t row_bytes, const uint32_t *scalars_raw, G1Xyzz29 *sums, const uint32_t *only_if,

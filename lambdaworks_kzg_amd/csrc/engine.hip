@@ -39,7 +39,10 @@ void set_error(const char *fmt, ...) {
 const char *get_error() { return g_err; }
 
 // ------------------------------------------------------------------------------------------------
-// profiling: hipEvent pairs around every kernel launch, on the launch stream
+// profiling: a hipEvent pair per profile name and use, read by prof_drain. A scope of ONE kernel launch binds its pair to the dispatch
+// packet (kernels.h: prof_launch): the pair reads the kernel's own duration and the stream carries no packet for it. A scope of several
+// launches or of a copy (ProfScope) records its pair as two marker packets on the launch stream.
+// LWKZG_PROF_MARKERS=1 is the arm of before: marker pairs on default-flag events around every scope.
 
 struct ProfRec {
     const char *name;
@@ -57,6 +60,10 @@ static std::map<std::string, ProfAgg> g_prof_agg;
 // lwkzg_profile_reset destroys what the pools hold.
 static std::map<int, std::vector<hipEvent_t>> g_prof_pool;
 
+// what the profile was made of since the last reset (lwkzg_profile_sources: a test hook, so that the shipped arm itself is checked)
+static std::atomic<uint64_t> g_prof_n_dispatch{0}, g_prof_n_marker{0}, g_prof_n_shared{0};
+static std::atomic<unsigned> g_prof_event_flags{0};   // creation flags of the event the pools got last
+
 static bool prof_event(hipEvent_t *e, int dev) {
     {
         std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -67,7 +74,15 @@ static bool prof_event(hipEvent_t *e, int dev) {
             return true;
         }
     }
-    return hipEventCreate(e) == hipSuccess;
+    if (knobs().prof_markers) {
+        g_prof_event_flags.store(hipEventDefault);
+        return hipEventCreate(e) == hipSuccess;
+    }
+    // the events are read for their times alone (hipEventElapsedTime): a marker that records one needs no system-scope fence with its
+    // cache write-back and invalidation between the kernels being timed. (hipEventReleaseToDevice beside it: ROCm 7.2 refuses the pair
+    // with hipErrorInvalidValue -- the release flags exclude each other there.)
+    g_prof_event_flags.store(hipEventDisableSystemFence);
+    return hipEventCreateWithFlags(e, hipEventDisableSystemFence) == hipSuccess;
 }
 
 static void prof_pool_free() {
@@ -77,9 +92,54 @@ static void prof_pool_free() {
     g_prof_pool.clear();
 }
 
-ProfScope::ProfScope(const char *n, hipStream_t s)
-    : name(n), st(s), e0(nullptr), e1(nullptr), dev(0), on(g_prof_on.load(std::memory_order_relaxed)) {
+// An event that two pairs read -- the closing marker of one scope that is the opening marker of the next -- has a second holder: it goes
+// back to the pool when the last holder lets go of it. Callers hold g_prof_mu.
+static std::map<hipEvent_t, int> g_prof_extra_holders;
+static void prof_release(hipEvent_t e, int dev) {
+    auto it = g_prof_extra_holders.find(e);
+    if (it != g_prof_extra_holders.end()) {
+        if (--it->second == 0) g_prof_extra_holders.erase(it);
+        return;
+    }
+    g_prof_pool[dev].push_back(e);
+}
+// the closing marker a kProfHandsOver scope of this thread recorded last, for a kProfTakesOver scope that opens directly behind it
+struct ProfTail {
+    hipEvent_t e = nullptr;
+    hipStream_t st = nullptr;
+    int dev = 0;
+};
+static thread_local ProfTail tl_prof_tail;
+static void prof_tail_drop() {
+    if (!tl_prof_tail.e) return;
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    prof_release(tl_prof_tail.e, tl_prof_tail.dev);
+    tl_prof_tail.e = nullptr;
+}
+
+ProfScope::ProfScope(const char *n, hipStream_t s, unsigned lnk)
+    : name(n), st(s), e0(nullptr), e1(nullptr), dev(0), link(lnk), on(g_prof_on.load(std::memory_order_relaxed)) {
+    if (knobs().prof_markers) link = 0;   // the arm of before: every scope records its own two markers
+    // the tail is good for the scope that opens directly behind the one that left it, and for nothing later
+    ProfTail tail = tl_prof_tail;
+    tl_prof_tail.e = nullptr;
+    const bool take = on && (link & kProfTakesOver) && tail.e && tail.st == st && hipGetDevice(&dev) == hipSuccess && tail.dev == dev;
+    if (tail.e && !take) {
+        std::lock_guard<std::mutex> lk(g_prof_mu);
+        prof_release(tail.e, tail.dev);
+    }
     if (!on) return;
+    if (take) {
+        if (!prof_event(&e1, dev)) {
+            std::lock_guard<std::mutex> lk(g_prof_mu);
+            prof_release(tail.e, tail.dev);
+            on = false;
+            return;
+        }
+        e0 = tail.e;   // (the tail's hold on it is this scope's now)
+        g_prof_n_shared++;
+        return;
+    }
     if (hipGetDevice(&dev) != hipSuccess || !prof_event(&e0, dev) || !prof_event(&e1, dev)) {
         if (e0) hipEventDestroy(e0);
         e0 = nullptr;
@@ -91,6 +151,28 @@ ProfScope::ProfScope(const char *n, hipStream_t s)
 ProfScope::~ProfScope() {
     if (!on) return;
     hipEventRecord(e1, st);
+    g_prof_n_marker++;
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof_pending.push_back({name, e0, e1, dev});
+    if (link & kProfHandsOver) {
+        g_prof_extra_holders[e1]++;
+        tl_prof_tail = {e1, st, dev};
+    }
+}
+
+bool prof_on() { return g_prof_on.load(std::memory_order_relaxed); }
+bool prof_dispatch_events(hipEvent_t *e0, hipEvent_t *e1, int *dev) {
+    prof_tail_drop();   // a launch is being enqueued: whatever marker closed last is no longer the one directly in front
+    if (knobs().prof_markers) return false;
+    if (hipGetDevice(dev) != hipSuccess || !prof_event(e0, *dev)) return false;
+    if (!prof_event(e1, *dev)) {
+        hipEventDestroy(*e0);
+        return false;
+    }
+    return true;
+}
+void prof_dispatch_pending(const char *name, hipEvent_t e0, hipEvent_t e1, int dev) {
+    g_prof_n_dispatch++;
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_pending.push_back({name, e0, e1, dev});
 }
@@ -104,9 +186,8 @@ void prof_drain() {
             a.launches++;
             a.total_ms += ms;
         }
-        auto &pool = g_prof_pool[r.dev];
-        pool.push_back(r.e0);
-        pool.push_back(r.e1);
+        prof_release(r.e0, r.dev);
+        prof_release(r.e1, r.dev);
     }
     g_prof_pending.clear();
 }
@@ -117,6 +198,10 @@ void prof_reset() {
     prof_pool_free();
     std::lock_guard<std::mutex> lk(g_prof_mu);
     g_prof_agg.clear();
+    g_prof_n_dispatch = g_prof_n_marker = g_prof_n_shared = 0;
+}
+ProfSources prof_sources() {
+    return {g_prof_n_dispatch.load(), g_prof_n_marker.load(), g_prof_n_shared.load(), g_prof_event_flags.load()};
 }
 std::map<std::string, ProfAgg> prof_totals() {
     std::lock_guard<std::mutex> lk(g_prof_mu);

@@ -20,6 +20,11 @@ void prof_drain();
 void prof_set_on(bool on);
 void prof_reset();                                // the event pools and the totals
 std::map<std::string, ProfAgg> prof_totals();     // a copy, taken under the profiling lock
+struct ProfSources {                              // since the last prof_reset
+    uint64_t dispatch_pairs, marker_pairs, shared_markers;
+    unsigned event_flags;                         // creation flags of the pooled event made last
+};
+ProfSources prof_sources();
 
 // ---- engine.hip: registry, devices, context lifetime ------------------------------------------------------------------------------
 int ctx_mode_override(const KZGSettings *s);                 // under the registry's lock; -1: none

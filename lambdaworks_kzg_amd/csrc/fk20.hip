@@ -34,10 +34,9 @@ __global__ __launch_bounds__(256) void k_fk20_base_rows(uint4 *__restrict__ rows
 }
 
 void launch_fk20_base_rows(uint32_t *rows_raw, const uint32_t *roots_raw, uint32_t first, size_t n_rows, hipStream_t st) {
-    ProfScope p("k_fk20_base_rows", st);
     const size_t n = n_rows * kBlobElems;
-    hipLaunchKernelGGL(k_fk20_base_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (uint4 *)rows_raw, (const uint4 *)roots_raw, first,
-                       n);
+    prof_launch("k_fk20_base_rows", st, k_fk20_base_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (uint4 *)rows_raw, (const uint4 *)roots_raw,
+                first, n);
 }
 
 // One lane per (base, window): Q = [2^(c j)]B by doublings, then rows d = 1 .. h as Q, 2Q, .. by mixed additions, each brought to
@@ -63,10 +62,9 @@ __global__ __launch_bounds__(256) void k_fk20_table(const G1Affine *__restrict__
 }
 
 void launch_fk20_table(const G1Affine *bases, G1Affine29 *table, int bits, hipStream_t st) {
-    ProfScope p("k_fk20_table", st);
     const Fk20Plan plan = fk20_plan(bits);
     const size_t n = (size_t)kFk20Bases * plan.nw;
-    hipLaunchKernelGGL(k_fk20_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, bases, table, plan);
+    prof_launch("k_fk20_table", st, k_fk20_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, bases, table, plan);
 }
 
 // ---- coefficient transforms ----------------------------------------------------------------------------------------------------------
@@ -121,9 +119,8 @@ __global__ __launch_bounds__(64 * kCoeffWaves) void k_fk20_coeffs(const uint4 *_
 }
 
 void launch_fk20_coeffs(const uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t *scalars_out, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_fk20_coeffs", st);
-    hipLaunchKernelGGL(k_fk20_coeffs, dim3((unsigned)(n_blobs * kFk20Terms / kCoeffWaves)), dim3(64 * kCoeffWaves), 0, st,
-                       (const uint4 *)coeffs_raw, tw_fwd, (uint4 *)scalars_out);
+    prof_launch("k_fk20_coeffs", st, k_fk20_coeffs, dim3((unsigned)(n_blobs * kFk20Terms / kCoeffWaves)), dim3(64 * kCoeffWaves), 0,
+                (const uint4 *)coeffs_raw, tw_fwd, (uint4 *)scalars_out);
 }
 
 // ---- the 64-term MSMs ----------------------------------------------------------------------------------------------------------------
@@ -162,9 +159,8 @@ __global__ __launch_bounds__(64) void k_fk20_msm(const G1Affine29 *__restrict__ 
 }
 
 void launch_fk20_msm(const G1Affine29 *table, int bits, const uint32_t *scalars, G1Xyzz29 *e_out, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_fk20_msm", st);
-    hipLaunchKernelGGL(k_fk20_msm, dim3((unsigned)(n_blobs * kFk20Points)), dim3(64), 0, st, table, fk20_plan(bits), (const uint4 *)scalars,
-                       e_out, (uint32_t)n_blobs);
+    prof_launch("k_fk20_msm", st, k_fk20_msm, dim3((unsigned)(n_blobs * kFk20Points)), dim3(64), 0, table, fk20_plan(bits), (const uint4 *)scalars,
+                e_out, (uint32_t)n_blobs);
 }
 
 // ---- the two G1 transforms -----------------------------------------------------------------------------------------------------------
@@ -204,8 +200,7 @@ __global__ __launch_bounds__(kFk20Points) void k_fk20_transforms(G1Xyzz29 *__res
 }
 
 void launch_fk20_transforms(G1Xyzz29 *pts, const uint8_t *roots, G1Xyzz29 *h_out, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_fk20_transforms", st);
-    hipLaunchKernelGGL(k_fk20_transforms, dim3((unsigned)n_blobs), dim3(kFk20Points), 0, st, pts, roots, fk20_beta29(), h_out);
+    prof_launch("k_fk20_transforms", st, k_fk20_transforms, dim3((unsigned)n_blobs), dim3(kFk20Points), 0, pts, roots, fk20_beta29(), h_out);
 }
 
 // The finalize of a column call on this engine: msm.hip's k_finalize_compress with an index map in front, one
@@ -224,9 +219,8 @@ __global__ __launch_bounds__(64) void k_fk20_columns_compress(const G1Xyzz29 *__
 }
 
 void launch_fk20_columns_compress(const G1Xyzz29 *pts, const CellColumns &cols, uint32_t c, uint8_t *out48, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_fk20_columns_compress", st);
     const size_t n = n_blobs * c;
-    hipLaunchKernelGGL(k_fk20_columns_compress, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, pts, cols, c, out48, n);
+    prof_launch("k_fk20_columns_compress", st, k_fk20_columns_compress, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, pts, cols, c, out48, n);
 }
 
 }  // namespace lwk

@@ -44,8 +44,7 @@ __global__ __launch_bounds__(256) void k_build_twiddles(Fr *__restrict__ tw_fwd,
 }
 
 void launch_build_twiddles(Fr *tw_fwd, Fr *tw_inv, hipStream_t st) {
-    ProfScope p("k_build_twiddles", st);
-    hipLaunchKernelGGL(k_build_twiddles, dim3(kBlobElems / 2 / 256), dim3(256), 0, st, tw_fwd, tw_inv);
+    prof_launch("k_build_twiddles", st, k_build_twiddles, dim3(kBlobElems / 2 / 256), dim3(256), 0, tw_fwd, tw_inv);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -72,8 +71,7 @@ __global__ __launch_bounds__(256) void k_twiddles_to28(const Fr *__restrict__ tw
 }
 
 void launch_twiddles_to28(const Fr *tw, Fr28 *tw28, hipStream_t st) {
-    ProfScope p("k_twiddles_to28", st);
-    hipLaunchKernelGGL(k_twiddles_to28, dim3(kBlobElems / 2 / 256), dim3(256), 0, st, tw, tw28, kBlobElems / 2);
+    prof_launch("k_twiddles_to28", st, k_twiddles_to28, dim3(kBlobElems / 2 / 256), dim3(256), 0, tw, tw28, kBlobElems / 2);
 }
 
 // a 32-byte BIG-endian element as its two 16-byte loads (first = the most significant half) -> eight limbs, least significant first
@@ -154,12 +152,11 @@ __global__ __launch_bounds__(kNttThreads) void k_ntt4096(const void *__restrict_
 
 template <bool FROM_BLOB, bool BLOB_BE = false>
 static void launch_ntt_t(const void *in, Fr *out, const Fr28 *tw, int scale_to_raw, int32_t *status, size_t n_blobs, hipStream_t st) {
-    ProfScope p(BLOB_BE ? "k_ntt4096_be" : "k_ntt4096", st);
     static const hipError_t attr_set =
         hipFuncSetAttribute((const void *)k_ntt4096<FROM_BLOB, BLOB_BE>, hipFuncAttributeMaxDynamicSharedMemorySize, kNttLdsBytes);
     (void)attr_set;
-    hipLaunchKernelGGL((k_ntt4096<FROM_BLOB, BLOB_BE>), dim3((unsigned)n_blobs), dim3(kNttThreads), kNttLdsBytes, st, in, out, tw, scale_to_raw,
-                       status);
+    prof_launch(BLOB_BE ? "k_ntt4096_be" : "k_ntt4096", st, k_ntt4096<FROM_BLOB, BLOB_BE>, dim3((unsigned)n_blobs), dim3(kNttThreads), kNttLdsBytes, in,
+                out, tw, scale_to_raw, status);
 }
 
 void launch_ntt4096(const Fr *in, Fr *out, const Fr28 *tw, int inverse_scale_to_raw, size_t n_blobs, hipStream_t st) {
@@ -184,9 +181,8 @@ __global__ __launch_bounds__(256) void k_bitrev_permute(const Fr *__restrict__ i
 }
 
 void launch_bitrev_permute(const Fr *in, Fr *out, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_bitrev_permute", st);
     size_t n = n_blobs * kBlobElems;
-    hipLaunchKernelGGL(k_bitrev_permute, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, out, n);
+    prof_launch("k_bitrev_permute", st, k_bitrev_permute, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, in, out, n);
 }
 
 __global__ __launch_bounds__(256) void k_fr_be_to_mont(const uint4 *__restrict__ in, Fr *__restrict__ out, size_t n) {
@@ -198,9 +194,7 @@ __global__ __launch_bounds__(256) void k_fr_be_to_mont(const uint4 *__restrict__
     out[i] = fe_from_raw<FrParams>(s);
 }
 void launch_fr_be_to_mont(const uint8_t *in_be, Fr *out, size_t n_elems, hipStream_t st) {
-    ProfScope p("k_fr_be_to_mont", st);
-    hipLaunchKernelGGL(k_fr_be_to_mont, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, (const uint4 *)in_be,
-                       out, n_elems);
+    prof_launch("k_fr_be_to_mont", st, k_fr_be_to_mont, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, (const uint4 *)in_be, out, n_elems);
 }
 
 __global__ __launch_bounds__(256) void k_fr_mont_to_be(const Fr *__restrict__ in, uint4 *__restrict__ out, size_t n) {
@@ -214,9 +208,7 @@ __global__ __launch_bounds__(256) void k_fr_mont_to_be(const Fr *__restrict__ in
                                 __builtin_bswap32(s[0]));
 }
 void launch_fr_mont_to_be(const Fr *in, uint8_t *out_be, size_t n_elems, hipStream_t st) {
-    ProfScope p("k_fr_mont_to_be", st);
-    hipLaunchKernelGGL(k_fr_mont_to_be, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, in, (uint4 *)out_be,
-                       n_elems);
+    prof_launch("k_fr_mont_to_be", st, k_fr_mont_to_be, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, in, (uint4 *)out_be, n_elems);
 }
 
 __global__ __launch_bounds__(256) void k_raw_to_be(const uint4 *__restrict__ in, uint4 *__restrict__ out, size_t n) {
@@ -229,9 +221,7 @@ __global__ __launch_bounds__(256) void k_raw_to_be(const uint4 *__restrict__ in,
                                 __builtin_bswap32(lo.x));
 }
 void launch_raw_to_be(const uint32_t *raw, uint8_t *out_be, size_t n_elems, hipStream_t st) {
-    ProfScope p("k_raw_to_be", st);
-    hipLaunchKernelGGL(k_raw_to_be, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, st, (const uint4 *)raw,
-                       (uint4 *)out_be, n_elems);
+    prof_launch("k_raw_to_be", st, k_raw_to_be, dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, (const uint4 *)raw, (uint4 *)out_be, n_elems);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -401,19 +391,17 @@ __global__ __launch_bounds__(kThreads) void k_eval_quotient(const uint4 *__restr
 
 void launch_eval_quotient(const uint32_t *coeffs_raw, const Fr *z_mont, uint32_t *quot_raw, uint8_t *y_out, int le,
                           size_t n_blobs, hipStream_t st, const uint32_t *only_if) {
-    ProfScope p(only_if ? "k_eval_quotient_redo" : "k_eval_quotient", st);
     // (512 and 1024 lanes per blob -- a chain of 37 / 29 products instead of 51 -- measured SLOWER for one blob, 0.061 / 0.077 ms against 0.054:
     // the barriers of 8 / 16 waves cost more than the shorter chain saves; gpurun_out r05)
-    hipLaunchKernelGGL(k_eval_quotient<256>, dim3((unsigned)n_blobs), dim3(256), 0, st, (const uint4 *)coeffs_raw, z_mont, (uint4 *)quot_raw,
-                       y_out, le, only_if, 0);
+    prof_launch(only_if ? "k_eval_quotient_redo" : "k_eval_quotient", st, k_eval_quotient<256>, dim3((unsigned)n_blobs), dim3(256), 0,
+                (const uint4 *)coeffs_raw, z_mont, (uint4 *)quot_raw, y_out, le, only_if, 0);
 }
 
 // y = p(z) of n reference-mode blobs straight from their bytes (big-endian coefficients), no workspace: the evaluation of a
 // device-resident batch verification as ONE launch (r05; it was a parse and an evaluation per chunk of 1024)
 void launch_eval_y_from_blobs_be(const uint8_t *blobs, const Fr *z_mont, uint8_t *y_out, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_eval_quotient_from_blobs", st);
-    hipLaunchKernelGGL(k_eval_quotient<256>, dim3((unsigned)n_blobs), dim3(256), 0, st, (const uint4 *)blobs, z_mont, (uint4 *)nullptr, y_out, 0,
-                       (const uint32_t *)nullptr, 1);
+    prof_launch("k_eval_quotient_from_blobs", st, k_eval_quotient<256>, dim3((unsigned)n_blobs), dim3(256), 0, (const uint4 *)blobs, z_mont,
+                (uint4 *)nullptr, y_out, 0, (const uint32_t *)nullptr, 1);
 }
 
 // ---- the quotient in EVALUATION form (r05) --------------------------------------------------------------------
@@ -708,9 +696,8 @@ __global__ __launch_bounds__(kThreads) void k_eval_quotient_evalform(const uint4
 
 void launch_eval_quotient_evalform(const uint32_t *evals_raw, const Fr *z_mont, const Fr28 *roots_brp28, uint32_t *quot_raw, uint8_t *y_out, int le,
                                    size_t n_blobs, hipStream_t st, const uint32_t *only_if) {
-    ProfScope p(only_if ? "k_eval_quotient_evalform_redo" : "k_eval_quotient_evalform", st);
-    hipLaunchKernelGGL(k_eval_quotient_evalform<256>, dim3((unsigned)n_blobs), dim3(256), 0, st, (const uint4 *)evals_raw, z_mont, roots_brp28,
-                       (uint4 *)quot_raw, y_out, le, only_if, (int32_t *)nullptr);
+    prof_launch(only_if ? "k_eval_quotient_evalform_redo" : "k_eval_quotient_evalform", st, k_eval_quotient_evalform<256>, dim3((unsigned)n_blobs),
+                dim3(256), 0, (const uint4 *)evals_raw, z_mont, roots_brp28, (uint4 *)quot_raw, y_out, le, only_if, (int32_t *)nullptr);
 }
 
 // y = p(z) of n c-kzg-mode blobs straight from their bytes (little-endian evaluations; an element >= r: status[blob] = BADARGS), no workspace,
@@ -719,13 +706,11 @@ void launch_eval_quotient_evalform(const uint32_t *evals_raw, const Fr *z_mont, 
 void launch_eval_y_from_blobs_evalform(const uint8_t *blobs, const Fr *z_mont, const Fr28 *roots_brp28, uint8_t *y_out, int32_t *status,
                                        size_t n_blobs, hipStream_t st, int le) {
     if (le) {
-        ProfScope p("k_eval_quotient_evalform_from_blobs", st);
-        hipLaunchKernelGGL(k_eval_quotient_evalform<256>, dim3((unsigned)n_blobs), dim3(256), 0, st, (const uint4 *)blobs, z_mont, roots_brp28,
-                           (uint4 *)nullptr, y_out, 1, (const uint32_t *)nullptr, status);
+        prof_launch("k_eval_quotient_evalform_from_blobs", st, k_eval_quotient_evalform<256>, dim3((unsigned)n_blobs), dim3(256), 0,
+                    (const uint4 *)blobs, z_mont, roots_brp28, (uint4 *)nullptr, y_out, 1, (const uint32_t *)nullptr, status);
     } else {
-        ProfScope p("k_eval_quotient_evalform_from_blobs_be", st);
-        hipLaunchKernelGGL((k_eval_quotient_evalform<256, true>), dim3((unsigned)n_blobs), dim3(256), 0, st, (const uint4 *)blobs, z_mont, roots_brp28,
-                           (uint4 *)nullptr, y_out, 0, (const uint32_t *)nullptr, status);
+        prof_launch("k_eval_quotient_evalform_from_blobs_be", st, (k_eval_quotient_evalform<256, true>), dim3((unsigned)n_blobs), dim3(256), 0,
+                    (const uint4 *)blobs, z_mont, roots_brp28, (uint4 *)nullptr, y_out, 0, (const uint32_t *)nullptr, status);
     }
 }
 
@@ -740,8 +725,8 @@ __global__ __launch_bounds__(256) void k_flag_differs48(const uint32_t *__restri
     flags[i] = d != 0;
 }
 void launch_flag_differs48(const uint8_t *a, const uint8_t *b, uint32_t *flags, size_t n, hipStream_t st) {
-    ProfScope p("k_flag_differs48", st);
-    hipLaunchKernelGGL(k_flag_differs48, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint32_t *)a, (const uint32_t *)b, flags, n);
+    prof_launch("k_flag_differs48", st, k_flag_differs48, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint32_t *)a, (const uint32_t *)b,
+                flags, n);
 }
 
 // ---- c-kzg mode without the transform: the Lagrange form of the setup ------------------------------------------
@@ -776,10 +761,9 @@ __global__ __launch_bounds__(256) void k_idft_columns(uint4 *__restrict__ coeffs
 }
 
 void launch_idft_columns(uint32_t *coeffs_raw, const Fr *tw_inv, uint32_t first, size_t n_rows, hipStream_t st) {
-    ProfScope p("k_idft_columns", st);
     uint32_t n4096[8] = {4096, 0, 0, 0, 0, 0, 0, 0};
     const Fr ninv = inv(fe_from_raw<FrParams>(n4096));                    // 1 / 4096 (Montgomery form), on the host
-    hipLaunchKernelGGL(k_idft_columns, dim3((unsigned)n_rows), dim3(256), 0, st, (uint4 *)coeffs_raw, tw_inv, first, ninv);
+    prof_launch("k_idft_columns", st, k_idft_columns, dim3((unsigned)n_rows), dim3(256), 0, (uint4 *)coeffs_raw, tw_inv, first, ninv);
 }
 
 // The opposite direction: a c-kzg-4844 setup arrives in LAGRANGE form and the monomial points are derived from it (tables.hip:
@@ -801,9 +785,8 @@ __global__ __launch_bounds__(256) void k_dft_rows(uint4 *__restrict__ coeffs_raw
 }
 
 void launch_dft_rows(uint32_t *coeffs_raw, const Fr *tw_fwd, uint32_t first, size_t n_rows, hipStream_t st) {
-    ProfScope p("k_dft_rows", st);
     const size_t n = n_rows * kBlobElems;
-    hipLaunchKernelGGL(k_dft_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (uint4 *)coeffs_raw, tw_fwd, first, n);
+    prof_launch("k_dft_rows", st, k_dft_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (uint4 *)coeffs_raw, tw_fwd, first, n);
 }
 
 // c-kzg blobs on the Lagrange form: the canonical little-endian elements ARE the scalars the MSM reads (32-bit words, least
@@ -820,9 +803,9 @@ __global__ __launch_bounds__(256) void k_copy_le_check(const uint4 *__restrict__
 }
 
 void launch_copy_le_check(const uint8_t *blobs, uint32_t *scalars_raw, int32_t *status, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_copy_le_check", st);
     const size_t n = n_blobs * kBlobElems;
-    hipLaunchKernelGGL(k_copy_le_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)blobs, (uint4 *)scalars_raw, status, n);
+    prof_launch("k_copy_le_check", st, k_copy_le_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint4 *)blobs, (uint4 *)scalars_raw,
+                status, n);
 }
 
 // eth-mode blobs on the Lagrange form: canonical BIG-endian elements. The same two 16-byte loads per element, the eight words
@@ -841,9 +824,9 @@ __global__ __launch_bounds__(256) void k_copy_be_check(const uint4 *__restrict__
 }
 
 void launch_copy_be_check(const uint8_t *blobs, uint32_t *scalars_raw, int32_t *status, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_copy_be_check", st);
     const size_t n = n_blobs * kBlobElems;
-    hipLaunchKernelGGL(k_copy_be_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)blobs, (uint4 *)scalars_raw, status, n);
+    prof_launch("k_copy_be_check", st, k_copy_be_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint4 *)blobs, (uint4 *)scalars_raw,
+                status, n);
 }
 
 // Quotients of a proof call whose MSM runs on the Lagrange form while the quotient was computed in coefficient form (a Lagrange-form
@@ -872,15 +855,11 @@ __global__ __launch_bounds__(256) void k_mont_to_raw_bitrev(const Fr *__restrict
 // coeffs_raw (in place) <- evaluations on the bit-reversed domain; `scratch`, `scratch2`: n_blobs x 4096 Fr each
 void launch_coefficients_to_evaluations(uint32_t *coeffs_raw, Fr *scratch, Fr *scratch2, const Fr28 *tw28_fwd, size_t n_blobs, hipStream_t st) {
     const size_t n = n_blobs * kBlobElems;
-    {
-        ProfScope p("k_raw_to_mont_bitrev", st);
-        hipLaunchKernelGGL(k_raw_to_mont_bitrev, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint4 *)coeffs_raw, scratch, n);
-    }
+    prof_launch("k_raw_to_mont_bitrev", st, k_raw_to_mont_bitrev, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint4 *)coeffs_raw,
+                scratch, n);
     launch_ntt4096(scratch, scratch2, tw28_fwd, 0, n_blobs, st);
-    {
-        ProfScope p("k_mont_to_raw_bitrev", st);
-        hipLaunchKernelGGL(k_mont_to_raw_bitrev, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const Fr *)scratch2, (uint4 *)coeffs_raw, n);
-    }
+    prof_launch("k_mont_to_raw_bitrev", st, k_mont_to_raw_bitrev, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const Fr *)scratch2,
+                (uint4 *)coeffs_raw, n);
 }
 
 // Montgomery Fr -> 32 bytes in the requested byte order, one lane each (z of a batch going back to the host)
@@ -893,8 +872,7 @@ __global__ __launch_bounds__(64) void k_fr_mont_to_bytes(const Fr *__restrict__ 
     if (le) raw_to_le<8>(out + 32 * i, s); else raw_to_be<8>(out + 32 * i, s);
 }
 void launch_fr_mont_to_bytes(const Fr *in, uint8_t *out, int le, size_t n, hipStream_t st) {
-    ProfScope p("k_fr_mont_to_bytes", st);
-    hipLaunchKernelGGL(k_fr_mont_to_bytes, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, in, out, le, n);
+    prof_launch("k_fr_mont_to_bytes", st, k_fr_mont_to_bytes, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, in, out, le, n);
 }
 
 __global__ __launch_bounds__(64) void k_z_from_bytes(const uint8_t *__restrict__ zb, Fr *__restrict__ z_mont,
@@ -913,8 +891,7 @@ __global__ __launch_bounds__(64) void k_z_from_bytes(const uint8_t *__restrict__
 }
 
 void launch_z_from_bytes(const uint8_t *z_bytes, Fr *z_mont, int32_t *status, int scalar_rule, size_t n, hipStream_t st) {
-    ProfScope p("k_z_from_bytes", st);
-    hipLaunchKernelGGL(k_z_from_bytes, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, z_bytes, z_mont, status, scalar_rule, n);
+    prof_launch("k_z_from_bytes", st, k_z_from_bytes, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, z_bytes, z_mont, status, scalar_rule, n);
 }
 
 }  // namespace lwk

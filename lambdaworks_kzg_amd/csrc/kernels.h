@@ -2,6 +2,7 @@
 // Every launcher only enqueues work on `st`; nothing here synchronises or allocates.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include "g1.cuh"
 #include "fr28.cuh"
@@ -11,16 +12,45 @@
 
 namespace lwk {
 
-// ---- profiling hook (engine.hip): wraps a launch in hipEvents when profiling is on
+// ---- profiling hooks (engine.hip). Nothing is enqueued for them while profiling is off.
+// ProfScope: a pair of marker packets (hipEventRecord) around whatever the scope enqueues on `st` -- several launches, or a copy.
+// Where one such scope closes and the next opens on the same stream with NOTHING enqueued between them, one marker serves as both times:
+// the first scope is built with kProfHandsOver, the second with kProfTakesOver -- the caller's word that it opens directly behind. The
+// hand-over is per thread and lasts until the next scope or prof_launch of that thread, whichever it is.
+constexpr unsigned kProfHandsOver = 1u, kProfTakesOver = 2u;
 struct ProfScope {
-    ProfScope(const char *name, hipStream_t st);
+    ProfScope(const char *name, hipStream_t st, unsigned link = 0);
     ~ProfScope();
     const char *name;
     hipStream_t st;
     hipEvent_t e0, e1;
     int dev;   // the device current at the scope's start: its events were created on it and go back to that device's pool
+    unsigned link;
     bool on;
 };
+// prof_launch: ONE kernel launch under a profile name. Profiling on: the dispatch itself carries a pooled start and stop event
+// (hipExtLaunchKernelGGL, flags 0: in stream order like any launch), so its time is the kernel's own and no marker packet sits between
+// the launches of the region being timed. Profiling off, or LWKZG_PROF_MARKERS=1 (the A/B arm: ProfScope's marker pair on
+// default-flag events): a plain hipLaunchKernelGGL.
+bool prof_on();
+bool prof_dispatch_events(hipEvent_t *e0, hipEvent_t *e1, int *dev);   // profiling is on; false: the marker arm, or no events to be had
+void prof_dispatch_pending(const char *name, hipEvent_t e0, hipEvent_t e1, int dev);
+template <typename... Formals, typename... Args>
+inline void prof_launch(const char *name, hipStream_t st, void (*kernel)(Formals...), dim3 grid, dim3 block, uint32_t shmem, const Args &...args) {
+    if (!prof_on()) {
+        hipLaunchKernelGGL(kernel, grid, block, shmem, st, args...);
+        return;
+    }
+    hipEvent_t e0, e1;
+    int dev;
+    if (prof_dispatch_events(&e0, &e1, &dev)) {
+        hipExtLaunchKernelGGL(kernel, grid, block, shmem, st, e0, e1, 0, args...);
+        prof_dispatch_pending(name, e0, e1, dev);
+        return;
+    }
+    ProfScope p(name, st);
+    hipLaunchKernelGGL(kernel, grid, block, shmem, st, args...);
+}
 
 // ---- scalar ingest (msm.hip)
 // Mode R: 32-byte big-endian elements -> canonical 8xu32 little-endian limbs, reduced mod r
@@ -169,7 +199,10 @@ void launch_validate_commitments(const uint8_t *comm48, uint8_t *canon48, int32_
 // the same in two steps, each ONE launch per kernel over one point set or two (b: a verification's proofs and commitments together): the
 // linear combinations' multiples can start after the first. One set without verdict scratch, or validate_coop off: k_subgroup_canon alone
 void launch_decompress_points(const PointSet &a, const PointSet *b, size_t n, hipStream_t st, bool apart = false);
-void launch_subgroup_canon(const PointSet &a, const PointSet *b, int32_t *status, int bad_code, size_t n, hipStream_t st, bool apart = false);
+// behind_decompress: the caller enqueues nothing on `st` between launch_decompress_points and this call (the two padded launches' profile
+// scopes then share one marker)
+void launch_subgroup_canon(const PointSet &a, const PointSet *b, int32_t *status, int bad_code, size_t n, hipStream_t st, bool apart = false,
+                           bool behind_decompress = false);
 
 // ---- the verification's linear combinations, r05's arm (setup.hip)
 // verify side: three variable-base linear combinations in one launch (setup.hip).

@@ -34,6 +34,7 @@ struct Knobs {
     bool direct_asm = true;          // LWKZG_DIRECT_ASM=0: compiler-scheduled k_direct_accumulate
     bool fold_asm = true;            // LWKZG_FOLD_ASM=0: compiler-scheduled lane fold
     bool commit_tail = true;         // LWKZG_COMMIT_TAIL=0: fold, second pass and finalize as launches of their own, clears by fill launches (the A/B arm of k_commit_tail)
+    bool prof_markers = false;       // LWKZG_PROF_MARKERS=1: the library's profile times every scope with a pair of marker packets on default-flag events (the A/B arm of prof_launch)
     bool bucket_asm = true;          // LWKZG_BUCKET_ASM=0: compiler-scheduled k_bucket_accumulate
     int direct_fill = 0;             // LWKZG_DIRECT_FILL: workgroups-per-blob geometry override
     int coop = 1;                    // LWKZG_COOP=0: no cooperative kernel for <= 8 blobs

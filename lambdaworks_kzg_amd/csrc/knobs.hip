@@ -69,6 +69,7 @@ Knobs read_env() {
     r.flag(k.direct_asm, "LWKZG_DIRECT_ASM", EXP);
     r.flag(k.fold_asm, "LWKZG_FOLD_ASM", EXP);
     r.flag(k.commit_tail, "LWKZG_COMMIT_TAIL", EXP);
+    r.flag(k.prof_markers, "LWKZG_PROF_MARKERS", EXP);
     r.flag(k.bucket_asm, "LWKZG_BUCKET_ASM", EXP);
     r.num(k.direct_fill, "LWKZG_DIRECT_FILL", EXP);
     r.num(k.coop, "LWKZG_COOP", EXP);
@@ -137,7 +138,7 @@ const char *knob_names_operational() {
 }
 
 const char *knob_names_experimental() {
-    return "LWKZG_DIRECT_ASM LWKZG_FOLD_ASM LWKZG_COMMIT_TAIL LWKZG_BUCKET_ASM LWKZG_DIRECT_FILL LWKZG_COOP LWKZG_COOP_MAX LWKZG_COOP_RPQ LWKZG_SORT_STAGE "
+    return "LWKZG_DIRECT_ASM LWKZG_FOLD_ASM LWKZG_COMMIT_TAIL LWKZG_PROF_MARKERS LWKZG_BUCKET_ASM LWKZG_DIRECT_FILL LWKZG_COOP LWKZG_COOP_MAX LWKZG_COOP_RPQ LWKZG_SORT_STAGE "
            "LWKZG_REDUCE_LANES LWKZG_HASH_PAIRS LWKZG_HASH_PRIO LWKZG_VALIDATE_COOP LWKZG_VALIDATE_LDS_PAD LWKZG_CKZG_EVAL_PROOFS "
            "LWKZG_MID_PROOF_PIPE LWKZG_MID_PROOF_PIPE_MIN LWKZG_MID_PROOF_PARTS LWKZG_MID_PROOF_CHUNKS LWKZG_HEAVY_SERIAL LWKZG_PROOF_SCHEDULE LWKZG_SPLIT "
            "LWKZG_SLICE0 LWKZG_SET_MODE_IN_PLACE LWKZG_PAIRING_GENERIC_SQR LWKZG_PAIRING_NAIVE LWKZG_PAIRING_NO_PRECOMP "
@@ -154,13 +155,13 @@ extern "C" __attribute__((visibility("default"))) size_t lwkzg_knob_report(char 
         tmp, sizeof tmp,
         "{\"experimental\": %s, \"mode\": %d, \"direct_bits\": %s%d, \"direct_row\": %d, \"coalesce\": %d, \"twin\": %d, "
         "\"small_proof_host\": %zu, \"mid_proof_host\": %zu, \"host_threads\": %d, \"host_warm_ms\": %d, \"host_finish\": %zu, "
-        "\"timing\": %d, \"verbose\": %d, \"direct_asm\": %d, \"fold_asm\": %d, \"commit_tail\": %d, \"bucket_asm\": %d, \"coop\": %d, \"coop_max\": %d, "
+        "\"timing\": %d, \"verbose\": %d, \"direct_asm\": %d, \"fold_asm\": %d, \"commit_tail\": %d, \"prof_markers\": %d, \"bucket_asm\": %d, \"coop\": %d, \"coop_max\": %d, "
         "\"hash_pairs\": %d, \"hash_prio\": %d, \"validate_coop\": %d, \"ckzg_eval_proofs\": %d, \"mid_proof_pipe\": %d, "
         "\"verify_msm\": %d, \"verify_fused\": %d, \"verify_pad_kb\": [%d, %d, %d], \"verify_order\": %d, \"vmsm_list_cap\": %d, "
         "\"host_stage\": %d, \"operational\": \"%s\", \"experimental_names\": \"%s\"}",
         k.experimental ? "true" : "false", k.mode, k.has_direct_bits ? "" : "null, \"direct_bits_unset_default\": ", k.direct_bits, k.direct_row,
         (int)k.coalesce, (int)k.twin, k.small_proof_host, k.mid_proof_host, k.host_threads, k.host_warm_ms, k.host_finish, (int)k.timing,
-        (int)k.verbose, (int)k.direct_asm, (int)k.fold_asm, (int)k.commit_tail, (int)k.bucket_asm, k.coop, k.coop_max, (int)k.hash_pairs, k.hash_prio,
+        (int)k.verbose, (int)k.direct_asm, (int)k.fold_asm, (int)k.commit_tail, (int)k.prof_markers, (int)k.bucket_asm, k.coop, k.coop_max, (int)k.hash_pairs, k.hash_prio,
         (int)k.validate_coop, (int)k.ckzg_eval_proofs, (int)k.mid_proof_pipe, k.verify_msm, k.verify_fused, k.verify_pad_kb[0],
         k.verify_pad_kb[1], k.verify_pad_kb[2], k.verify_order, k.vmsm_list_cap, (int)k.host_stage, lwk::knob_names_operational(),
         lwk::knob_names_experimental());

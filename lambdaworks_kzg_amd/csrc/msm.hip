@@ -62,11 +62,10 @@ __global__ __launch_bounds__(256) void k_parse_be_reduce(const uint4 *__restrict
 
 void launch_parse_be_reduce(const uint8_t *blobs, uint32_t *scalars_raw, size_t n_elems, hipStream_t st, uint32_t *zero, uint32_t zero_words,
                             uint32_t *zero2, uint32_t zero2_words) {
-    ProfScope p("k_parse_be_reduce", st);
     unsigned grid = (unsigned)((n_elems + 255) / 256);
-    hipLaunchKernelGGL(k_parse_be_reduce, dim3(grid), dim3(256), 0, st, (const uint4 *)blobs, (uint4 *)scalars_raw,
-                       n_elems, zero, zero_words < n_elems ? zero_words : (uint32_t)n_elems, zero2,
-                       zero2_words < n_elems ? zero2_words : (uint32_t)n_elems);
+    prof_launch("k_parse_be_reduce", st, k_parse_be_reduce, dim3(grid), dim3(256), 0, (const uint4 *)blobs, (uint4 *)scalars_raw,
+                n_elems, zero, zero_words < n_elems ? zero_words : (uint32_t)n_elems, zero2,
+                zero2_words < n_elems ? zero2_words : (uint32_t)n_elems);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -259,12 +258,8 @@ __global__ __launch_bounds__(kSortThreads) void k_digit_sort(const uint4 *__rest
 
 void launch_digit_sort(const uint32_t *scalars_raw, uint32_t *sorted, uint32_t *bucket_start, uint32_t *perm,
                        size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_digit_sort", st);
-    const bool staged = knobs().sort_stage;
-    if (staged)
-        hipLaunchKernelGGL(k_digit_sort<true>, dim3((unsigned)n_blobs), dim3(kSortThreads), 0, st, (const uint4 *)scalars_raw, sorted, bucket_start, perm);
-    else
-        hipLaunchKernelGGL(k_digit_sort<false>, dim3((unsigned)n_blobs), dim3(kSortThreads), 0, st, (const uint4 *)scalars_raw, sorted, bucket_start, perm);
+    prof_launch("k_digit_sort", st, knobs().sort_stage ? k_digit_sort<true> : k_digit_sort<false>, dim3((unsigned)n_blobs), dim3(kSortThreads), 0,
+                (const uint4 *)scalars_raw, sorted, bucket_start, perm);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -430,11 +425,9 @@ void launch_bucket_accumulate(const G1Affine29 *table, const uint32_t *sorted, c
                               const uint32_t *perm, G1Xyzz29 *buckets, size_t n_blobs, hipStream_t st) {
     const dim3 grid(kHeavyBlocks + kLightBlocks, (unsigned)n_blobs);
     if (bucket_asm_enabled()) {
-        ProfScope p("k_bucket_accumulate_asm", st);
-        hipLaunchKernelGGL(k_bucket_accumulate_asm, grid, dim3(kAccThreads), 0, st, table, sorted, bucket_start, perm, buckets);
+        prof_launch("k_bucket_accumulate_asm", st, k_bucket_accumulate_asm, grid, dim3(kAccThreads), 0, table, sorted, bucket_start, perm, buckets);
     } else {
-        ProfScope p("k_bucket_accumulate", st);
-        hipLaunchKernelGGL(k_bucket_accumulate, grid, dim3(kAccThreads), 0, st, table, sorted, bucket_start, perm, buckets);
+        prof_launch("k_bucket_accumulate", st, k_bucket_accumulate, grid, dim3(kAccThreads), 0, table, sorted, bucket_start, perm, buckets);
     }
 }
 
@@ -498,15 +491,14 @@ static int reduce_lanes_override() {
 }
 
 void launch_bucket_reduce(const G1Xyzz29 *buckets, G1Xyzz29 *sums, size_t n_blobs, hipStream_t st) {
-    ProfScope p("k_bucket_reduce", st);
     int lanes = reduce_lanes_override();
     if (lanes == 0) lanes = n_blobs <= 256 ? 512 : 128;  // r02, 1024 blobs: 2.40 ms with 128 lanes, 2.91 with 64, 3.86 with 512
     if (lanes >= 512)
-        hipLaunchKernelGGL(k_bucket_reduce<512>, dim3((unsigned)n_blobs), dim3(512), 0, st, buckets, sums);
+        prof_launch("k_bucket_reduce", st, k_bucket_reduce<512>, dim3((unsigned)n_blobs), dim3(512), 0, buckets, sums);
     else if (lanes >= 128)
-        hipLaunchKernelGGL(k_bucket_reduce<128>, dim3((unsigned)n_blobs), dim3(128), 0, st, buckets, sums);
+        prof_launch("k_bucket_reduce", st, k_bucket_reduce<128>, dim3((unsigned)n_blobs), dim3(128), 0, buckets, sums);
     else
-        hipLaunchKernelGGL(k_bucket_reduce<64>, dim3((unsigned)n_blobs), dim3(64), 0, st, buckets, sums);
+        prof_launch("k_bucket_reduce", st, k_bucket_reduce<64>, dim3((unsigned)n_blobs), dim3(64), 0, buckets, sums);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -530,8 +522,7 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_points(const G1Xyzz29 *__re
 }
 
 void launch_sum_points(const G1Xyzz29 *in, size_t n, G1Xyzz29 *total, int accumulate, hipStream_t st) {
-    ProfScope p("k_sum_points", st);
-    hipLaunchKernelGGL(k_sum_points, dim3(1), dim3(kSumThreads), 0, st, in, n, total, accumulate);
+    prof_launch("k_sum_points", st, k_sum_points, dim3(1), dim3(kSumThreads), 0, in, n, total, accumulate);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -552,8 +543,7 @@ __global__ __launch_bounds__(64) void k_finalize_compress(const G1Xyzz29 *__rest
 }
 
 void launch_finalize_compress(const G1Xyzz29 *sums, uint8_t *out48, size_t n, hipStream_t st) {
-    ProfScope p("k_finalize_compress", st);
-    hipLaunchKernelGGL(k_finalize_compress, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, sums, out48, n);
+    prof_launch("k_finalize_compress", st, k_finalize_compress, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, sums, out48, n);
 }
 
 }  // namespace lwk

@@ -222,39 +222,29 @@ __global__ __launch_bounds__(64) void k_recover_mixed_solve(const Fr *__restrict
 }
 
 void launch_recover_setup(const RecoverSet &set, const Fr *tw_fwd, Fr *tab, hipStream_t st) {
-    ProfScope p("k_recover_setup", st);
-    hipLaunchKernelGGL(k_recover_setup, dim3(1), dim3(kCellsPerBlob), 0, st, set, tw_fwd, tab);
+    prof_launch("k_recover_setup", st, k_recover_setup, dim3(1), dim3(kCellsPerBlob), 0, set, tw_fwd, tab);
 }
 
 void launch_recover_coefficients(const uint8_t *cells, const RecoverSet &set, size_t num_cells, const Fr *tw_fwd, const Fr *tw_inv, const Fr *tab,
                                  Fr *scratch, uint32_t *coeffs_raw, int32_t *status, int bad_code, int le, size_t n_blobs, hipStream_t st) {
-    {
-        ProfScope p("k_recover_interp", st);
-        hipLaunchKernelGGL(k_recover_interp, dim3((unsigned)(n_blobs * num_cells)), dim3(kCellElems), 0, st, (const uint4 *)cells, set,
-                           (uint32_t)num_cells, tw_inv, tab, scratch, status, bad_code, le);
-    }
-    ProfScope p("k_recover_solve", st);
-    hipLaunchKernelGGL(k_recover_solve, dim3((unsigned)(n_blobs * kCellElems)), dim3(kCellElems), 0, st, (const Fr *)scratch, set, tw_fwd, tw_inv,
-                       tab, (uint4 *)coeffs_raw, status, bad_code);
+    prof_launch("k_recover_interp", st, k_recover_interp, dim3((unsigned)(n_blobs * num_cells)), dim3(kCellElems), 0, (const uint4 *)cells, set,
+                (uint32_t)num_cells, tw_inv, tab, scratch, status, bad_code, le);
+    prof_launch("k_recover_solve", st, k_recover_solve, dim3((unsigned)(n_blobs * kCellElems)), dim3(kCellElems), 0, (const Fr *)scratch, set, tw_fwd,
+                tw_inv, tab, (uint4 *)coeffs_raw, status, bad_code);
 }
 
 void launch_recover_mixed_setup(const RecoverMasks &masks, size_t first, size_t n_sets, const Fr *tw_fwd, const RecoverSetsDev &dev, hipStream_t st) {
-    ProfScope p("k_recover_mixed_setup", st);
-    hipLaunchKernelGGL(k_recover_mixed_setup, dim3((unsigned)n_sets), dim3(kCellsPerBlob), 0, st, masks, (uint32_t)first, tw_fwd, dev.tab, dev.k,
-                       dev.given);
+    prof_launch("k_recover_mixed_setup", st, k_recover_mixed_setup, dim3((unsigned)n_sets), dim3(kCellsPerBlob), 0, masks, (uint32_t)first, tw_fwd,
+                dev.tab, dev.k, dev.given);
 }
 
 void launch_recover_mixed_coefficients(const uint8_t *cells, const RecoverGroup &g, size_t n_cells, const Fr *tw_fwd, const Fr *tw_inv,
                                        const RecoverSetsDev &dev, Fr *scratch, uint32_t *coeffs_raw, int32_t *status, int bad_code, int le,
                                        size_t n_blobs, hipStream_t st) {
-    {
-        ProfScope p("k_recover_mixed_interp", st);
-        hipLaunchKernelGGL(k_recover_mixed_interp, dim3((unsigned)n_cells), dim3(kCellElems), 0, st, (const uint4 *)cells, g, (uint32_t)n_blobs,
-                           tw_inv, (const Fr *)dev.tab, (const uint8_t *)dev.k, scratch, status, bad_code, le);
-    }
-    ProfScope p("k_recover_mixed_solve", st);
-    hipLaunchKernelGGL(k_recover_mixed_solve, dim3((unsigned)(n_blobs * kCellElems)), dim3(kCellElems), 0, st, (const Fr *)scratch, g, tw_fwd,
-                       tw_inv, (const Fr *)dev.tab, (const uint32_t *)dev.given, (uint4 *)coeffs_raw, status, bad_code);
+    prof_launch("k_recover_mixed_interp", st, k_recover_mixed_interp, dim3((unsigned)n_cells), dim3(kCellElems), 0, (const uint4 *)cells, g,
+                (uint32_t)n_blobs, tw_inv, (const Fr *)dev.tab, (const uint8_t *)dev.k, scratch, status, bad_code, le);
+    prof_launch("k_recover_mixed_solve", st, k_recover_mixed_solve, dim3((unsigned)(n_blobs * kCellElems)), dim3(kCellElems), 0, (const Fr *)scratch,
+                g, tw_fwd, tw_inv, (const Fr *)dev.tab, (const uint32_t *)dev.given, (uint4 *)coeffs_raw, status, bad_code);
 }
 
 }  // namespace lwk

@@ -38,9 +38,7 @@ __global__ __launch_bounds__(64) void k_g1_decompress(const uint8_t *__restrict_
 
 void launch_g1_decompress(const uint8_t *in48, G1Affine *out, int32_t *status, size_t n, int subgroup_check,
                           hipStream_t st) {
-    ProfScope p("k_g1_decompress", st);
-    hipLaunchKernelGGL(k_g1_decompress, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, in48, out, status, n,
-                       subgroup_check);
+    prof_launch("k_g1_decompress", st, k_g1_decompress, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, in48, out, status, n, subgroup_check);
 }
 
 // reference blst_fp: 6 x u64, most-significant limb first, canonical integer
@@ -73,8 +71,7 @@ __global__ __launch_bounds__(64) void k_g1_from_blst(const uint64_t *__restrict_
 }
 
 void launch_g1_from_blst(const uint64_t *blst_p1, G1Affine *out, int32_t *status, size_t n, hipStream_t st) {
-    ProfScope p("k_g1_from_blst", st);
-    hipLaunchKernelGGL(k_g1_from_blst, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, blst_p1, out, status, n);
+    prof_launch("k_g1_from_blst", st, k_g1_from_blst, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, blst_p1, out, status, n);
 }
 
 __global__ __launch_bounds__(64) void k_g1_to_blst(const G1Affine *__restrict__ in, const int32_t *__restrict__ status,
@@ -97,8 +94,7 @@ __global__ __launch_bounds__(64) void k_g1_to_blst(const G1Affine *__restrict__ 
 }
 
 void launch_g1_to_blst(const G1Affine *in, const int32_t *status, uint64_t *blst_p1, size_t n, hipStream_t st) {
-    ProfScope p("k_g1_to_blst", st);
-    hipLaunchKernelGGL(k_g1_to_blst, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, in, status, blst_p1, n);
+    prof_launch("k_g1_to_blst", st, k_g1_to_blst, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, in, status, blst_p1, n);
 }
 
 // T[j][i] = 2^(13 j) * P_i, affine. One lane per point walks its 20 windows.
@@ -230,10 +226,9 @@ size_t lincomb3_blocks(size_t n) { return (n + kLincombTerms - 1) / kLincombTerm
 void launch_lincomb3(const G1Affine29 *proofs, const int32_t *proof_kind, const G1Affine29 *proof_mult, const G1Affine29 *comms,
                      const int32_t *comm_kind, const G1Affine29 *comm_mult, const uint8_t *sc_r_be, const uint8_t *sc_rz_be,
                      G1Xyzz29 *partial, size_t n, hipStream_t st) {
-    ProfScope p("k_lincomb3", st);
     unsigned grid = (unsigned)lincomb3_blocks(n);
-    hipLaunchKernelGGL(k_lincomb3, dim3(grid, 3), dim3(kLincombThreads), 0, st, proofs, proof_kind, proof_mult, comms, comm_kind,
-                       comm_mult, sc_r_be, sc_rz_be, partial, n);
+    prof_launch("k_lincomb3", st, k_lincomb3, dim3(grid, 3), dim3(kLincombThreads), 0, proofs, proof_kind, proof_mult, comms, comm_kind,
+                comm_mult, sc_r_be, sc_rz_be, partial, n);
 }
 
 __global__ __launch_bounds__(64) void k_xyzz29_to_affine_be(const G1Xyzz29 *__restrict__ in, uint8_t *__restrict__ out96,
@@ -257,13 +252,11 @@ __global__ __launch_bounds__(64) void k_xyzz29_to_affine_be(const G1Xyzz29 *__re
 }
 
 void launch_xyzz29_to_affine_be(const G1Xyzz29 *in, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st) {
-    ProfScope p("k_xyzz29_to_affine_be", st);
-    hipLaunchKernelGGL(k_xyzz29_to_affine_be, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, in, out96, inf, n);
+    prof_launch("k_xyzz29_to_affine_be", st, k_xyzz29_to_affine_be, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, in, out96, inf, n);
 }
 
 void launch_build_table(const G1Affine *points, G1Affine29 *table, hipStream_t st) {
-    ProfScope p("k_build_table", st);
-    hipLaunchKernelGGL(k_build_table, dim3(kBlobElems / 64), dim3(64), 0, st, points, table);
+    prof_launch("k_build_table", st, k_build_table, dim3(kBlobElems / 64), dim3(64), 0, points, table);
 }
 
 }  // namespace lwk

@@ -334,18 +334,14 @@ void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, 
     const int prio = knobs().hash_prio;
     const bool be_deg = (hash_rule & kHashFieldsBe) != 0;   // (mode_rules.h)
     const int le = hash_rule & kHashDigestLe;                // the digest's byte order, as the kernels take it
-    ProfScope p(only_if_differs_from ? "k_challenge_fixup" : "k_challenge", st);
+    const char *name = only_if_differs_from ? "k_challenge_fixup" : "k_challenge";
     const dim3 grid((unsigned)((n + 63) / 64));
-    if (pairs && be_deg)
-        hipLaunchKernelGGL((k_challenge_pairs<false, true>), grid, dim3(256), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from, prio,
-                           (uint32_t *)nullptr);
-    else if (pairs)
-        hipLaunchKernelGGL(k_challenge_pairs<false>, grid, dim3(256), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from, prio,
-                           (uint32_t *)nullptr);
-    else if (be_deg)
-        hipLaunchKernelGGL(k_challenge<true>, grid, dim3(128), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from);
+    if (pairs)
+        prof_launch(name, st, be_deg ? k_challenge_pairs<false, true> : k_challenge_pairs<false>, grid, dim3(256), 0, blobs, canon48, z_mont, le, n,
+                    only_if_differs_from, prio, (uint32_t *)nullptr);
     else
-        hipLaunchKernelGGL(k_challenge<false>, grid, dim3(128), 0, st, blobs, canon48, z_mont, le, n, only_if_differs_from);
+        prof_launch(name, st, be_deg ? k_challenge<true> : k_challenge<false>, grid, dim3(128), 0, blobs, canon48, z_mont, le, n,
+                    only_if_differs_from);
 }
 
 // ---- the challenge in two parts (fused commit-and-prove: proof_calls.hip) ------------------------------------------------
@@ -353,13 +349,8 @@ void launch_challenge(const uint8_t *blobs, const uint8_t *canon48, Fr *z_mont, 
 void launch_challenge_midstate(const uint8_t *blobs, uint32_t *midstate, size_t n, hipStream_t st, bool be_fields) {
     if (n == 0) return;
     const int prio = knobs().hash_prio;
-    ProfScope p("k_challenge_midstate", st);
-    if (be_fields)
-        hipLaunchKernelGGL((k_challenge_pairs<true, true>), dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, blobs, (const uint8_t *)nullptr,
-                           (Fr *)nullptr, 0, n, (const uint8_t *)nullptr, prio, midstate);
-    else
-        hipLaunchKernelGGL(k_challenge_pairs<true>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, blobs, (const uint8_t *)nullptr,
-                           (Fr *)nullptr, 0, n, (const uint8_t *)nullptr, prio, midstate);
+    prof_launch("k_challenge_midstate", st, be_fields ? k_challenge_pairs<true, true> : k_challenge_pairs<true>, dim3((unsigned)((n + 63) / 64)),
+                dim3(256), 0, blobs, (const uint8_t *)nullptr, (Fr *)nullptr, 0, n, (const uint8_t *)nullptr, prio, midstate);
 }
 
 // part 2: the last two blocks (32 bytes of blob, the 48 commitment bytes, padding and length), one lane per blob
@@ -408,9 +399,9 @@ __global__ __launch_bounds__(64) void k_challenge_finish(const uint8_t *__restri
 void launch_challenge_finish(const uint8_t *blobs, const uint8_t *canon48, const uint32_t *midstate, Fr *z_mont, int hash_rule, size_t n,
                              hipStream_t st) {
     if (n == 0) return;
-    ProfScope p("k_challenge_finish", st);
     // (the last two blocks hold no degree field: of the hash rule only the digest's byte order matters here)
-    hipLaunchKernelGGL(k_challenge_finish, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, blobs, canon48, midstate, z_mont, hash_rule & kHashDigestLe, n);
+    prof_launch("k_challenge_finish", st, k_challenge_finish, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, blobs, canon48, midstate, z_mont,
+                hash_rule & kHashDigestLe, n);
 }
 
 }  // namespace lwk

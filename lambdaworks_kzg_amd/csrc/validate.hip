@@ -62,7 +62,7 @@ void launch_validate_commitments(const uint8_t *comm48, uint8_t *canon48, int32_
     if (aff_out && kind_out && verdict_scratch && n && knobs().validate_coop) {
         const PointSet set{comm48, aff_out, kind_out, canon48, verdict_scratch};
         launch_decompress_points(set, nullptr, n, st, apart);
-        launch_subgroup_canon(set, nullptr, status, bad_code, n, st, apart);
+        launch_subgroup_canon(set, nullptr, status, bad_code, n, st, apart, true);
         return;
     }
     ProfScope p("k_validate_commitments", st);
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64) void k_subgroup_canon(G1Affine29 *__restrict__ 
 
 void launch_decompress_points(const PointSet &a, const PointSet *b2, size_t n, hipStream_t st, bool apart) {
     const PointSet &b = b2 ? *b2 : a;
-    ProfScope p("k_decompress_points", st);
+    ProfScope p("k_decompress_points", st, kProfHandsOver);
     static PadCache cache;
     launch_padded(cache, (const void *)k_decompress_points, apart ? knobs().verify_pad_kb[0] * 1024u : 0u, [&](unsigned lds) {
         hipLaunchKernelGGL(k_decompress_points, dim3((unsigned)((n + 63) / 64), b2 ? 2 : 1), dim3(64), lds, st, a.in48, a.pts, a.kind, b.in48,
@@ -236,20 +236,20 @@ __global__ __launch_bounds__(256) void k_subgroup_coop_asm(const G1Affine29 *__r
 }
 
 // the quad test (two sets: always, as r06 shipped it; one set: with verdict scratch and validate_coop on), then canonical bytes and verdicts
-void launch_subgroup_canon(const PointSet &a, const PointSet *b2, int32_t *status, int bad_code, size_t n, hipStream_t st, bool apart) {
+void launch_subgroup_canon(const PointSet &a, const PointSet *b2, int32_t *status, int bad_code, size_t n, hipStream_t st, bool apart,
+                           bool behind_decompress) {
     const PointSet &b = b2 ? *b2 : a;
     const dim3 grid((unsigned)((n + 63) / 64), b2 ? 2 : 1);
     const bool coop = b2 || (a.verdict && knobs().validate_coop);
     if (coop) {
-        ProfScope p("k_subgroup_coop_asm", st);
+        ProfScope p("k_subgroup_coop_asm", st, behind_decompress ? kProfTakesOver : 0u);
         static PadCache cache;
         launch_padded(cache, (const void *)k_subgroup_coop_asm, apart ? knobs().verify_pad_kb[1] * 1024u : 0u, [&](unsigned lds) {
             hipLaunchKernelGGL(k_subgroup_coop_asm, grid, dim3(256), lds, st, a.pts, a.kind, a.verdict, b.pts, b.kind, b.verdict, (uint32_t)n);
         });
     }
-    ProfScope p("k_subgroup_canon", st);
-    hipLaunchKernelGGL(k_subgroup_canon, grid, dim3(64), 0, st, a.pts, a.kind, a.canon48, coop ? a.verdict : nullptr, b.pts, b.kind, b.canon48,
-                       coop ? b.verdict : nullptr, status, bad_code, n);
+    prof_launch("k_subgroup_canon", st, k_subgroup_canon, grid, dim3(64), 0, a.pts, a.kind, a.canon48, coop ? a.verdict : nullptr, b.pts, b.kind,
+                b.canon48, coop ? b.verdict : nullptr, status, bad_code, n);
 }
 
 }  // namespace lwk

@@ -49,8 +49,7 @@ __global__ __launch_bounds__(kYsumLanes) void k_verify_ysum(const uint8_t *__res
 }
 
 void launch_verify_ysum(const uint8_t *y32, int le, const Fr *pw, uint8_t *out32, size_t n, hipStream_t st, const uint32_t *skip) {
-    ProfScope p("k_verify_ysum", st);
-    hipLaunchKernelGGL(k_verify_ysum, dim3(1), dim3(kYsumLanes), 0, st, y32, le, pw, out32, (uint32_t)n, skip);
+    prof_launch("k_verify_ysum", st, k_verify_ysum, dim3(1), dim3(kYsumLanes), 0, y32, le, pw, out32, (uint32_t)n, skip);
 }
 
 // ---- the verifier --------------------------------------------------------------------------------------------------------------------

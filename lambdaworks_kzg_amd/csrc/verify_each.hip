@@ -156,8 +156,7 @@ C_KZG_RET each_line_tables(const KZGSettings *s, int power, void **slot, const P
 }
 
 void launch_each_pairing(const EachPoints *pts, const PairingLine *lines, uint8_t *ok, size_t n, hipStream_t st) {
-    ProfScope p("k_each_pairing", st);
-    k_each_pairing<<<each_blocks(n), kEachBlock, 0, st>>>(pts, lines, ok, n);
+    prof_launch("k_each_pairing", st, k_each_pairing, each_blocks(n), kEachBlock, 0, pts, lines, ok, n);
 }
 
 namespace {

@@ -702,7 +702,7 @@ C_KZG_RET verify_openings_prepare_device(Ctx *c, const uint8_t *d_comm, const ui
     LWK_HIP(hipMemsetAsync(vb.status_all, 0, n * 4, st));
     const PointSet set_p{d_proofs, vb.pts_p, vb.kind_p, vb.canon_dev + 48 * n, vb.verdict_p}, set_c{d_comm, vb.pts_c, vb.kind_c, vb.canon_dev, vb.verdict_c};
     launch_decompress_points(set_p, &set_c, n, st);
-    launch_subgroup_canon(set_p, &set_c, vb.status_all, bad, n, st);
+    launch_subgroup_canon(set_p, &set_c, vb.status_all, bad, n, st, false, true);
     launch_each_openings(d_z, d_y, vb.d_rz, vb.d_r, vb.status_all, bad, mr.scalar_rule(), n, st);
     LWK_HIP(hipGetLastError());
     return C_KZG_OK;

@@ -100,10 +100,9 @@ C_KZG_RET openings_entry(bool *done, bool *ok, const void *comm, const void *z, 
 void launch_opening_records(const uint8_t *z_in, const uint8_t *y_in, const uint8_t *canon_c, const uint8_t *canon_p, uint8_t *z_out,
                             uint8_t *y_out, int32_t *status, int bad_code, int scalar_rule, uint8_t *records, uint32_t *first_bad, size_t n,
                             hipStream_t st) {
-    ProfScope p("k_opening_records", st);
-    hipLaunchKernelGGL(k_opening_records, dim3((unsigned)((n + kOpeningBlock - 1) / kOpeningBlock)), dim3(kOpeningBlock), 0, st,
-                       (const uint4 *)z_in, (const uint4 *)y_in, (const uint4 *)canon_c, (const uint4 *)canon_p, (uint4 *)z_out, (uint4 *)y_out,
-                       status, bad_code, scalar_rule, (uint4 *)records, first_bad, (uint32_t)n);
+    prof_launch("k_opening_records", st, k_opening_records, dim3((unsigned)((n + kOpeningBlock - 1) / kOpeningBlock)), dim3(kOpeningBlock), 0,
+                (const uint4 *)z_in, (const uint4 *)y_in, (const uint4 *)canon_c, (const uint4 *)canon_p, (uint4 *)z_out, (uint4 *)y_out, status,
+                bad_code, scalar_rule, (uint4 *)records, first_bad, (uint32_t)n);
 }
 
 }  // namespace lwk

@@ -135,8 +135,7 @@ __global__ __launch_bounds__(64) void k_vmsm_scalars(const uint8_t *__restrict__
 
 void launch_vmsm_scalars(const uint8_t *z_bytes, int le, const Fr *pw, uint32_t *sc_a, uint32_t *sc_b, size_t n, hipStream_t st,
                          const uint32_t *skip) {
-    ProfScope p("k_vmsm_scalars", st);
-    hipLaunchKernelGGL(k_vmsm_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, z_bytes, le, pw, sc_a, sc_b, (uint32_t)n, skip);
+    prof_launch("k_vmsm_scalars", st, k_vmsm_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, z_bytes, le, pw, sc_a, sc_b, (uint32_t)n, skip);
 }
 
 // ---- behind r: bucket accumulation -------------------------------------------------------------------------------------------------
@@ -217,13 +216,11 @@ size_t vmsm_max_slices(size_t cap) {
 void launch_vmsm_accumulate(const uint32_t *sc_a, const uint32_t *sc_b, const G1Affine29 *tab_p, const int32_t *kind_p,
                             const G1Affine29 *tab_c, const int32_t *kind_c, G1Xyzz29 *partial, size_t n, hipStream_t st,
                             const uint32_t *sc_c, const uint32_t *skip) {
-    ProfScope p("k_vmsm_accumulate", st);
     const uint32_t terms = vmsm_terms_per_slice(n);
     const int lc = knobs().vmsm_list_cap;
     const uint32_t list_cap = lc > 0 && lc < kVmsmListCap ? (uint32_t)lc : (uint32_t)kVmsmListCap;
-    hipLaunchKernelGGL(k_vmsm_accumulate, dim3((unsigned)vmsm_slices(n), 3), dim3(256), 0, st, sc_a, sc_b, sc_c ? sc_c : sc_a, tab_p, kind_p, tab_c,
-                       kind_c,
-                       partial, (uint32_t)n, terms, list_cap, skip);
+    prof_launch("k_vmsm_accumulate", st, k_vmsm_accumulate, dim3((unsigned)vmsm_slices(n), 3), dim3(256), 0, sc_a, sc_b, sc_c ? sc_c : sc_a, tab_p,
+                kind_p, tab_c, kind_c, partial, (uint32_t)n, terms, list_cap, skip);
 }
 
 // ---- behind r: the slices' sums per bucket (a wave per bucket) ----------------------------------------------------------------------
@@ -286,12 +283,8 @@ __global__ __launch_bounds__(256) void k_vmsm_weighted(const G1Xyzz29 *__restric
 }
 
 void launch_vmsm_reduce(const G1Xyzz29 *partial, G1Xyzz29 *bsum, uint8_t *out96, int32_t *inf, size_t n, hipStream_t st, const uint32_t *skip) {
-    {
-        ProfScope p("k_vmsm_bucket_sums", st);
-        hipLaunchKernelGGL(k_vmsm_bucket_sums, dim3(255, 3), dim3(64), 0, st, partial, bsum, (uint32_t)vmsm_slices(n), skip);
-    }
-    ProfScope p("k_vmsm_weighted", st);
-    hipLaunchKernelGGL(k_vmsm_weighted, dim3(3), dim3(256), 0, st, bsum, out96, inf, skip);
+    prof_launch("k_vmsm_bucket_sums", st, k_vmsm_bucket_sums, dim3(255, 3), dim3(64), 0, partial, bsum, (uint32_t)vmsm_slices(n), skip);
+    prof_launch("k_vmsm_weighted", st, k_vmsm_weighted, dim3(3), dim3(256), 0, bsum, out96, inf, skip);
 }
 
 // ---- the transcript, assembled where its pieces are (device-resident verification) -----------------------------------------------------
@@ -315,9 +308,8 @@ __global__ __launch_bounds__(256) void k_verify_records(const uint8_t *__restric
 
 void launch_verify_records(const uint8_t *canon_c, const uint8_t *z32, const uint8_t *y32, const uint8_t *canon_p, const int32_t *status,
                            uint8_t *records, uint32_t *first_bad, size_t n, hipStream_t st) {
-    ProfScope p("k_verify_records", st);
-    hipLaunchKernelGGL(k_verify_records, dim3((unsigned)((10 * n + 255) / 256)), dim3(256), 0, st, canon_c, z32, y32, canon_p, status,
-                       (uint4 *)records, first_bad, (uint32_t)n);
+    prof_launch("k_verify_records", st, k_verify_records, dim3((unsigned)((10 * n + 255) / 256)), dim3(256), 0, canon_c, z32, y32, canon_p, status,
+                (uint4 *)records, first_bad, (uint32_t)n);
 }
 
 }  // namespace lwk
