@@ -21,6 +21,12 @@
 //     instead of seven: -3.4 % on the accumulate kernel, same-box A/B against W = 29.
 //
 // Invariants of F29<B, INL, LB>: integer value < B*p; limbs 0..12 < LB * 2^W; Montgomery radix R = 2^(14 W).
+// ONE exception: neg(a) and cneg(a, true) of the LITERAL zero return exactly K*p (K = sub_offset), the bound itself; of any other a they
+// are < K*p. A product takes such a factor all the same (kProdBound leaves R / p = 2520 against 2048), but is_zero() scans k < B and
+// would miss it. No call site tests such a value: they multiply it by one() first (fk20.cuh, setup.hip, vmsm.hip, direct.hip's commit
+// tail, g1_decompress29_nocheck_t) or hand it to a mixed addition as y (msm.hip, direct.hip, fk20.hip), whose only test of y is
+// xyzz_dbl_affine's order-2 guard -- and y = 0 is on no point of this curve (#E(Fp) is odd). tests/prims_check.hip runs every claim
+// of this header at operands that sit AT the bounds, on the host build and on the device build (tests/test_gpu_prims.py).
 #pragma once
 #include "field.cuh"
 

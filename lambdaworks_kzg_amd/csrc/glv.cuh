@@ -46,13 +46,17 @@ LWK_GLV_FN void split_by_z2(uint32_t lo[4], uint32_t hi[4], const uint32_t k[8])
 // The same split by Barrett's reduction (r06: k_vmsm_scalars sits on the critical path behind r, and the 256 rounds of the restoring
 // division above were most of its 82 us): q' = ((k >> 127) mu) >> 129 with mu = floor(2^256 / z^2) (129 bits) is floor(k / z^2) or one
 // less for every k < 2^256, so ONE conditional correction finishes it (tests/glv_split_check.cpp: edge values and 10^6 random ones
-// against the restoring division; tools' arithmetic: max corrections 1).
+// against the restoring division; tools' arithmetic: max corrections 1). k >> 127 has 129 bits: bit 255 of k is its fifth limb t4.
+// Beyond z^2 2^128 (no scalar: r < 2^255) the quotient has 129 bits and hi is its low 128, as split_by_z2's; lo is exact (the lost
+// bit times z^2 starts at bit 160, z^2's low word being zero, above the five limbs of the remainder).
+// The DEVICE build of both splits is held to divmod(k, z^2) by tests/prims_check.hip (tests/test_gpu_prims.py, family E).
 LWK_GLV_FN void split_by_z2_barrett(uint32_t lo[4], uint32_t hi[4], const uint32_t k[8]) {
     const uint32_t d[4] = {0x00000000u, 0x00000001u, 0x0001a402u, 0xac45a401u};
     const uint32_t mu[4] = {0xf6cfee2eu, 0x63f6e522u, 0xe01faaddu, 0x7c6becf1u};  // + 2^128
     uint32_t t[4];  // k >> 127
 #pragma unroll
     for (int i = 0; i < 4; i++) t[i] = (k[3 + i] >> 31) | (k[4 + i] << 1);
+    const uint32_t t4 = k[7] >> 31;
     // p = t * (2^128 + mu'), 9 limbs; only p >> 129 is wanted, but every column carries
     uint32_t p[9];
     {
@@ -68,11 +72,11 @@ LWK_GLV_FN void split_by_z2_barrett(uint32_t lo[4], uint32_t hi[4], const uint32
                 acc += (uint32_t)m;
                 carry += m >> 32;
             }
-            if (c >= 4) acc += t[c - 4];  // the 2^128 term
+            if (c >= 4) acc += (uint64_t)t[c - 4] + (t4 ? mu[c - 4] : 0u);  // the 2^128 term of mu, and t4 2^128 times mu's low limbs
             p[c] = (uint32_t)acc;
             acc = (acc >> 32) + carry;
         }
-        p[8] = (uint32_t)acc;
+        p[8] = (uint32_t)acc + t4;  // t4 2^128 times the 2^128 term
     }
     uint32_t q[4];  // p >> 129
 #pragma unroll

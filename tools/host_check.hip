@@ -9,6 +9,9 @@
 //   4. the transform's scalar field (fr28.cuh: 10 lazy limbs of 28 bits): products, butterflies and a whole 4096-point
 //      transform in the kernel's stage order (one carry ripple at stage 6, nothing else reduced) == the 8 x 32-bit CIOS field
 //   hipcc -O2 -std=c++17 --offload-arch=gfx950 -I lambdaworks_kzg_amd/csrc tools/host_check.hip -o /tmp/host_check
+// This file sees the HOST compile only, on pseudo-random canonical values. The DEVICE build of the same sources (operator* as a call or
+// inlined, the fused mul_sub, fe_mul_call, the G1Xyzz29i instantiations) and operands at the bounds the types declare are
+// tests/prims_check.hip's: tests/test_prims_cpu.py (host) and tests/test_gpu_prims.py (device), against Python integers.
 #include <stdio.h>
 #include <stdint.h>
 #include <string.h>
